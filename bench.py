@@ -9,11 +9,22 @@ One "step" = one pass of the hot path over one global batch of 128 synthetic pat
 normalise, forward, loss, backward, (sync-BN / gradient all-reduce when N > 1), momentum update, confusion
 matrix.  The global batch is fixed, so N ranks take 128/N patches each ("scaling": "strong").  Inputs (the
 2048x2048x5 tile, labels, instance table) are resident in HBM before the timed region.  Rank 0 prints ONE JSON
-line with the contract's keys plus "roofline" (dominant kernel: the fp32-MFMA implicit-GEMM convolution, timed
-live with HIP events on the launch stream), "kernels" (the same figures for every kernel family) and
-"cpu_baseline" (the oracle's PyTorch-CPU port of the reference step, bounded sample, rank 0 at N=1 only), and at N=1
-`extra.configs`: BASELINE.json's configs 2-5 on this one GPU (outside the timed region, ~15 s).  `--opt-in` adds
-"opt_in_arithmetic": the same step on the split-bf16 convolution kernels (op-level path), never the headline `value`.
+line with the contract's keys (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall time of
+the timed region / steps).  A plain run does only that: set up, warm up, time the K steps, print the line.
+
+`--full` adds what the headline does not need, each outside the timed region: "roofline" (dominant kernel: the
+fp32-MFMA implicit-GEMM convolution, timed live with HIP events on the launch stream), "kernels" (the same figures for
+every kernel family), "val_pixels_per_sec" (forward-only validation rate), "cpu_baseline" (the oracle's PyTorch-CPU
+port of the reference step, bounded sample, rank 0 at N=1 only), and at N=1 `extra.per_rank_size_table` and
+`extra.configs` (BASELINE.json's configs 2-5 on this one GPU, ~15 s); at N > 1 the second pass described below.
+Without `--full` those keys are null.  `--opt-in` adds "opt_in_arithmetic": the same step on the split-bf16
+convolution kernels (op-level path), never the headline `value`.
+
+`--dump-outputs DIR` writes what the last timed step computed, copied off the device right after the timed region,
+as DIR/<name>.npy (float32 / float64, ~19 MB; rank 0's at N > 1): loss_parts (mean cross-entropy, sum of the l2 terms),
+pred (arg-max labels, B x 64 x 64), conf (the confusion matrix), params, momentum and bn (the parameters, the momentum
+accumulators and the batch-norm moving statistics after the update).  Every input is seeded, so two runs with the same
+arguments feed the same data and can be compared output for output.
 
 N > 1 cannot be lost to a hang in the collectives.  Every rank process of the launcher is a SUPERVISOR that never touches the
 GPU: it starts the measuring process as a fresh child, relays its output, and watches its progress markers on stderr.  If a child
@@ -241,8 +252,9 @@ def _fallback_port(port0, i):
     return derived
 
 
-def supervise(argv):
-    """one rank of the launcher: start the measuring process as a child, fall back on a hang or a crash.  Never touches the GPU."""
+def supervise(argv, full=False):
+    """one rank of the launcher: start the measuring process as a child, fall back on a hang or a crash.  Never touches the GPU.
+    `full` (--full): a default run that worked is followed by the second pass (_second_pass)."""
     limit = float(os.environ.get("DRS_BENCH_WATCHDOG_S", "300"))
     chain = [("default", {})] + [(k, FALLBACK_ENV[k]) for k in os.environ.get("DRS_BENCH_FALLBACKS", "torch,async").split(",") if k in FALLBACK_ENV]
     port0 = int(os.environ.get("MASTER_PORT", "29500"))
@@ -266,7 +278,7 @@ def supervise(argv):
             # stdout carries the ONE JSON line (rank 0's) and nothing else: whatever a library printed to the child's descriptor 1 goes to stderr
             lines = out.splitlines()
             _PENDING["lines"] = lines       # from here on the line gets out whatever happens (signal handler, exception below)
-            if label == "default" and os.environ.get("DRS_BENCH_SECOND_PASS", "1") != "0":
+            if full and label == "default" and os.environ.get("DRS_BENCH_SECOND_PASS", "1") != "0":
                 try:
                     _PENDING["lines"] = _second_pass(argv, port0, lines)
                 except Exception as e:      # the optional pass must never cost the first one
@@ -291,7 +303,7 @@ def supervise(argv):
 
 
 def _second_pass(argv, port0, first_lines):
-    """After a default run that WORKED (library-side RCCL, inline form) every supervisor starts one more fresh measuring process with
+    """--full: after a default run that WORKED (library-side RCCL, inline form) every supervisor starts one more fresh measuring process with
     DRS_RCCL_BUCKETS=2 -- the inline form with the gradient buffer as two overlapped all-reduces on a side stream -- so that the one
     multi-GPU lease a round gets returns both numbers.  Its line goes INTO the first line (`extra.second_pass`); whatever happens to
     it (a hang is cut after DRS_BENCH_SECOND_PASS_LIMIT_S of silence, default 120) the first line stands as it is.  The headline
@@ -302,7 +314,13 @@ def _second_pass(argv, port0, first_lines):
                MASTER_PORT=str(_fallback_port(port0, 7)), TORCHELASTIC_USE_AGENT_STORE="False")
     limit = float(os.environ.get("DRS_BENCH_SECOND_PASS_LIMIT_S", "120"))
     wall = float(os.environ.get("DRS_BENCH_SECOND_PASS_WALL_S", "240"))       # silence AND total time are bounded: the driver's own limit is not ours to spend
-    rc, out, stage, lim = _run_watched([sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--no-opt-in", "--no-size-table", "--no-configs"],
+    argv2 = []          # (the outputs the first run dumped stay the first run's)
+    for a in argv:
+        if argv2 and argv2[-1] == "--dump-outputs":
+            argv2.pop()
+        elif not a.startswith("--dump-outputs="):
+            argv2.append(a)
+    rc, out, stage, lim = _run_watched([sys.executable, os.path.abspath(__file__)] + argv2 + ["--no-cpu-baseline", "--no-opt-in", "--no-size-table", "--no-configs"],
                                        env, limit, rendezvous_slack=1.5, wall_limit_s=wall)
     if os.environ.get("RANK", "0") != "0":
         return first_lines
@@ -775,6 +793,20 @@ def baseline_configs(dev, steps=20):
     return out
 
 
+def dump_outputs(path, net, out):
+    """--dump-outputs: what the last timed step handed its caller (train_step's loss parts, arg-max map and confusion matrix) and the
+    state it left (parameters, momentum accumulators, batch-norm moving statistics), as float32 / float64 .npy files in `path`"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss_parts": out["loss_parts"].detach().cpu().numpy().astype(np.float64),
+              "pred": out["pred"].detach().cpu().numpy().astype(np.float32),          # class ids 0..5: exact in float32
+              "conf": out["conf"].detach().cpu().numpy().astype(np.float64),          # counts beyond 2^24: float64
+              "params": net.params.detach().cpu().numpy().astype(np.float32),
+              "momentum": net.mom.detach().cpu().numpy().astype(np.float32),
+              "bn": net.bn.detach().cpu().numpy().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -789,6 +821,12 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip BASELINE configs 2-5 beside the headline (N = 1 only, ~15 s)")
     ap.add_argument("--arith", choices=sorted(ARITH), default="f32",
                     help="arithmetic of the convolution kernels: exact fp32 MFMA (default) or split-bf16 (conv_split.hip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel timing and roofline, validation rate, per-rank size "
+                         "table, BASELINE configs 2-5, CPU baseline (N = 1), the second DRS_RCCL_BUCKETS=2 pass (N > 1); the --no-* "
+                         "options still drop single parts")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     ar = ARITH[args.arith]
     # ---- which process is this?  (decided before anything imports torch or touches the GPU)
@@ -797,7 +835,7 @@ def main():
     if not launched and args.gpus > 1:
         sys.exit(plain_parent(args, sys.argv[1:]))                # `python bench.py --gpus N`: start the launcher as a child
     if launched and not child and int(os.environ["WORLD_SIZE"]) > 1 and os.environ.get("DRS_BENCH_SUPERVISE", "1") != "0":
-        sys.exit(supervise(sys.argv[1:]))                         # a rank of the launcher: supervise a fresh measuring process
+        sys.exit(supervise(sys.argv[1:], args.full))              # a rank of the launcher: supervise a fresh measuring process
     if os.environ.get("DRS_BENCH_SELFTEST") == "1":
         sys.exit(selftest_worker(args))
     load_numerics()
@@ -916,10 +954,13 @@ def main():
     del t_local
     mark("timed region done")
     loss = net.loss_value(out["loss_parts"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, out)
+        mark("outputs written")
 
     # ---- per-kernel timing pass (outside the timed region): HIP events around every launch
     kernels, roofline = None, None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         net.timer = KernelTimer()
         for _ in range(3):
             one_step()
@@ -965,25 +1006,27 @@ def main():
 
     mark("kernel timing done")
     # ---- validation half of the metric: forward-only pixels/sec (eval-mode BN, arg-max, confusion), isprs:1569-1618
-    vb = 25             # B * 100 patches per validation pass; 25 batches of 128 bound the sample (0.4 s)
-    for _ in range(2):
-        P.crop_to_net(net, pool, inst[:GLOBAL_BATCH][sl], PATCH, mean, std)
-        net.forward(B_local, PATCH, want_logits=False, labels=True)
-    if comm:
-        comm.barrier()
-    torch.cuda.synchronize()
-    tv = time.perf_counter()
-    for i in range(vb):
-        P.crop_to_net(net, pool, inst[i * GLOBAL_BATCH:(i + 1) * GLOBAL_BATCH][sl], PATCH, mean, std)
-        net.forward(B_local, PATCH, want_logits=False, labels=True)
-    if comm:
-        comm.barrier()
-    torch.cuda.synchronize()
-    tv = time.perf_counter() - tv
-    if comm:
-        tv = comm.max_float(tv, dev)
-    val_pixels_per_s = vb * GLOBAL_BATCH * PATCH * PATCH / tv
-    mark("validation done")
+    val_pixels_per_s = None
+    if args.full:
+        vb = 25             # B * 100 patches per validation pass; 25 batches of 128 bound the sample (0.4 s)
+        for _ in range(2):
+            P.crop_to_net(net, pool, inst[:GLOBAL_BATCH][sl], PATCH, mean, std)
+            net.forward(B_local, PATCH, want_logits=False, labels=True)
+        if comm:
+            comm.barrier()
+        torch.cuda.synchronize()
+        tv = time.perf_counter()
+        for i in range(vb):
+            P.crop_to_net(net, pool, inst[i * GLOBAL_BATCH:(i + 1) * GLOBAL_BATCH][sl], PATCH, mean, std)
+            net.forward(B_local, PATCH, want_logits=False, labels=True)
+        if comm:
+            comm.barrier()
+        torch.cuda.synchronize()
+        tv = time.perf_counter() - tv
+        if comm:
+            tv = comm.max_float(tv, dev)
+        val_pixels_per_s = round(vb * GLOBAL_BATCH * PATCH * PATCH / tv, 1)
+        mark("validation done")
 
     # ---- the opt-in arithmetics beside the headline (N = 1 only; never `value`): the same step on the split-bf16 kernels (op-level path).
     # bf16x6 is the fp32-EQUIVALENT one (tests/test_gpu_split.py: its errors against the fp64 oracle are no larger than the fp32 MFMA
@@ -1016,16 +1059,16 @@ def main():
 
     mark("opt-in done")
     size_table = None
-    if world == 1 and args.arith == "f32" and not args.no_size_table and not forced:
+    if args.full and world == 1 and args.arith == "f32" and not args.no_size_table and not forced:
         size_table = per_rank_size_table(dev, pool, mean, std)
     mark("size table done")
     configs = None
-    if world == 1 and args.arith == "f32" and not args.no_configs and not forced:
+    if args.full and world == 1 and args.arith == "f32" and not args.no_configs and not forced:
         configs = baseline_configs(dev)
     mark("configs done")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -1050,7 +1093,7 @@ def main():
                        # the sum of one `1` per rank over the step's own communicator (engine.py: the known-answer check of a new
                        # RCCL communicator, or the same through the callback's): > 1 only if that many ranks really took part
                        "rccl_ranks_observed": getattr(net, "ranks_observed", 1) if comm else 1},
-            "val_pixels_per_sec": round(val_pixels_per_s, 1), "final_loss": round(loss, 5),
+            "val_pixels_per_sec": val_pixels_per_s, "final_loss": round(loss, 5),
             "workspace_gb_per_gpu": round(net.workspace_bytes() / 1e9, 2),
             "train_tflops": round(value * 3 * 2 * net.plan.mac_per_pixel() * PATCH * PATCH / 1e12, 2),
             "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "opt_in_arithmetic": opt_in,

@@ -27,30 +27,30 @@ def _run(cmd, tmp_path, **env):
 
 
 def test_plain_launch_starts_the_launcher_itself(tmp_path):
-    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1"], tmp_path)
+    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], tmp_path)
     assert rc == 0, err
     assert len(lines) == 1                                   # ONE JSON line on stdout, nothing else
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["config"]["ranks_observed"] == 2
     assert d["config"]["collectives"] == "selftest" and d["config"]["fallback_reason"] is None
     assert "stage=warm-up done" in err
-    # r05: a default run that worked is followed by ONE more fresh measuring process per rank with DRS_RCCL_BUCKETS=2; its line rides
-    # inside the first one and never replaces its value
+    # r05: with --full, a default run that worked is followed by ONE more fresh measuring process per rank with DRS_RCCL_BUCKETS=2; its
+    # line rides inside the first one and never replaces its value
     sp = d["extra"]["second_pass"]
     assert sp["config"]["env"]["DRS_RCCL_BUCKETS"] == "2" and sp["config"]["env"]["DRS_COMM"] == "rccl" and sp["config"]["ranks_observed"] == 2
     assert sp["value"] == 1.0 and d["config"]["env"]["DRS_RCCL_BUCKETS"] is None
 
 
 def test_a_second_pass_that_dies_or_hangs_leaves_the_first_line_standing(tmp_path):
-    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2"], tmp_path, DRS_BENCH_FAKE_CRASH="buckets")
+    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--full"], tmp_path, DRS_BENCH_FAKE_CRASH="buckets")
     assert rc == 0, err
     d = json.loads(lines[-1])
     assert len(lines) == 1 and d["value"] == 1.0 and "exit code 7" in d["extra"]["second_pass"]["error"]
-    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2"], tmp_path, DRS_BENCH_FAKE_HANG="buckets", DRS_BENCH_SECOND_PASS_LIMIT_S="4")
+    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--full"], tmp_path, DRS_BENCH_FAKE_HANG="buckets", DRS_BENCH_SECOND_PASS_LIMIT_S="4")
     assert rc == 0, err
     d = json.loads(lines[-1])
     assert len(lines) == 1 and d["value"] == 1.0 and "timeout" in d["extra"]["second_pass"]["error"]
-    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2"], tmp_path, DRS_BENCH_SECOND_PASS="0")
+    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--full"], tmp_path, DRS_BENCH_SECOND_PASS="0")
     assert rc == 0 and "extra" not in json.loads(lines[-1])
 
 
@@ -60,6 +60,7 @@ def test_under_the_launcher_every_rank_supervises_a_fresh_child(tmp_path):
                            "--master-port", str(port), BENCH, "--gpus", "2"], tmp_path)
     assert rc == 0, err
     assert len(lines) == 1 and json.loads(lines[0])["config"]["ranks_observed"] == 2
+    assert "extra" not in json.loads(lines[0])              # a plain run: no second pass (that is --full's)
 
 
 def test_a_hang_before_warm_up_falls_back_to_the_callback_path(tmp_path):
@@ -156,7 +157,7 @@ def test_a_teardown_during_the_second_pass_still_delivers_the_first_line(tmp_pat
         e.pop(k, None)
     e.update(DRS_BENCH_SELFTEST="1", DRS_BENCH_FAKE_HANG="buckets", DRS_BENCH_SECOND_PASS_LIMIT_S="600", DRS_BENCH_SECOND_PASS_WALL_S="600")
     port = 24000 + os.getpid() % 5000
-    cmd = [sys.executable, BENCH, "--gpus", "2"]
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--full"]
     if shape == "launcher":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                str(port)] + cmd[1:]
@@ -186,7 +187,7 @@ def test_a_teardown_during_the_second_pass_still_delivers_the_first_line(tmp_pat
 
 def test_the_second_pass_has_an_overall_wall_clock_cap(tmp_path):
     """markers keep coming but the pass never ends (here: the cap is shorter than the pass): cut by wall time, first line intact"""
-    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2"], tmp_path, DRS_BENCH_SECOND_PASS_WALL_S="0.5")
+    rc, lines, err = _run([sys.executable, BENCH, "--gpus", "2", "--full"], tmp_path, DRS_BENCH_SECOND_PASS_WALL_S="0.5")
     assert rc == 0, err
     d = json.loads(lines[-1])
     assert len(lines) == 1 and d["value"] == 1.0

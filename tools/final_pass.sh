@@ -5,8 +5,8 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; mkdir -p $O
 cd $R
 timeout -k 10 900 python -m pytest tests -q -m gpu -x > $O/final_gpu_tests.log 2>&1; echo "pytest rc=$?" >> $O/final_gpu_tests.log; tail -2 $O/final_gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
-DRS_FORCE_COLLECTIVES=1 python bench.py --steps 40 --no-cpu-baseline --no-opt-in --no-size-table > $O/bench_forced_rccl_world1.json 2> $O/bench_forced.err; echo "forced rc=$?"
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+DRS_FORCE_COLLECTIVES=1 python bench.py --full --steps 40 --no-cpu-baseline --no-opt-in --no-size-table > $O/bench_forced_rccl_world1.json 2> $O/bench_forced.err; echo "forced rc=$?"
 bash tools/profile_round.sh $1 > $O/profile_round.log 2>&1; echo "profile rc=$?"
 cd $R
 # (round 6: BASELINE configs 2-5 are in the bench line itself -- extra.configs; the launch-order / tail / priority A/Bs of rounds 4-5 live in
