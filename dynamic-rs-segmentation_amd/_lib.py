@@ -58,6 +58,7 @@ SIGNATURES = {
                                 _p, _i, _i, _p]),
     "drs_stitch_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drs_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "drs_tile_place": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "drs_softmax_accumulate": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
     # ---- step level (csrc/engine.hip)
@@ -70,6 +71,7 @@ SIGNATURES = {
     "drs_net_layout": (_i, [_p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_layer_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.c_char_p, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_info": (_i, [_p, C.c_char_p, _i, C.POINTER(_f), C.POINTER(_i), C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "drs_net_receptive_field": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_se_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_type_name": (_i, [_i, C.c_char_p, _i, C.POINTER(_i)]),
     "drs_net_num_variables": (_i, [_p]),

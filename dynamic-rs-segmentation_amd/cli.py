@@ -3,6 +3,8 @@
 isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     input_path output_path currentModelPath trainingInstances testing_instances learningRate weight_decay
     batch_size niter reference_crop_size reference_stride_crop net_type distribution_type probValues update_type process
+  + optionally, anywhere, `--dense-tile[=T]` (validate_test / generate_final_maps): overlap-tile inference instead of the
+    reference's sliding windows (loops.predict_tile_dense; T = tile side, default min(h, w, 512))
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -28,6 +30,30 @@ ISPRS_PARAMS = ["input_path", "output_path(for model, images, etc)", "currentMod
                 "net_type[dilated_icpr_original|dilated_grsl|dilated_icpr_rate6_densely|dilated_grsl_rate8|dilated8_grsl]",
                 "distribution_type[single_fixed|multi_fixed|uniform|multinomial]", "probValues", "update_type [acc|loss]",
                 "process [training|validate_test|generate_final_maps]"]
+
+
+DENSE_TILE_FLAG = "--dense-tile"
+
+
+def parse_dense_tile(argv):
+    """isprs flavour: the optional `--dense-tile[=T]` (anywhere in argv) that switches validate_test / generate_final_maps to
+    overlap-tile inference (loops.predict_tile_dense).  Returns (argv without the flag, T) -- T = 0 for the bare flag (the default
+    side), None without it, in which case argv comes back unchanged.  A malformed value, or the flag given twice, raises ValueError."""
+    rest, tile = [], None
+    for a in argv:
+        if a != DENSE_TILE_FLAG and not a.startswith(DENSE_TILE_FLAG + "="):
+            rest.append(a)
+            continue
+        if tile is not None:
+            raise ValueError(DENSE_TILE_FLAG + " given more than once")
+        if a == DENSE_TILE_FLAG:
+            tile = 0
+            continue
+        v = a[len(DENSE_TILE_FLAG) + 1:]
+        if not (v.isascii() and v.isdigit()) or int(v) < 1:
+            raise ValueError("%s=%s: the tile side must be a positive integer" % (DENSE_TILE_FLAG, v))
+        tile = int(v)
+    return (list(argv) if tile is None else rest), tile
 
 
 def print_params(list_params, argv):
@@ -83,8 +109,14 @@ def _placement(device, comm):
 def main(argv=None, device=None, comm=None):
     device, comm = _placement(device, comm)
     argv = list(sys.argv if argv is None else argv)
+    try:
+        argv, dense_tile = parse_dense_tile(argv)
+    except ValueError as e:
+        sys.exit(str(e))
     if len(argv) < len(ISPRS_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
+    if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(DENSE_TILE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if comm.rank == 0:
         print_params(ISPRS_PARAMS, argv)
     (input_path, output_path, former_model_path, tr, te, lr, wd, bs, niter, ref_crop, ref_stride, net_type,
@@ -147,10 +179,11 @@ def main(argv=None, device=None, comm=None):
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm)
+                                   step, output_path, comm, dense_tile=dense_tile)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
-                                         distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm)
+                                         distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
+                                         dense_tile=dense_tile)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

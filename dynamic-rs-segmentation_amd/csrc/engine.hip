@@ -824,6 +824,34 @@ int drs_net_info(const drs_net_t* n, char* net_type, int name_cap, float* alpha,
   return DRS_OK;
 }
 
+// receptive field of one output pixel p of the whole net: it depends on input pixels [p - before, p + after] along each axis.  Every
+// block is stride 1, so a block adds its conv's SAME pads, + 1 a side for the 3 x 3 max-pool, + the SAME pads of a k x k average pool;
+// the 1 x 1 classifier adds nothing.  A chain and the dense concat (isprs:921-948: its longest path runs through every block) sum their
+// blocks; a squeeze stage (isprs:726-742) adds its 1 x 1 squeeze block and the larger of its two expand blocks.  Squeeze-and-excitation
+// blocks (isprs:682-697) scale by a mean over the whole patch: no finite field, DRS_ERR_ARG.
+int drs_net_receptive_field(const drs_net_t* n, int* before, int* after) {
+  if (!n || !before || !after || !n->se.empty()) return DRS_ERR_ARG;
+  auto field = [](const Layer& L, int& b, int& a) {
+    b = L.pad_b; a = L.pad_a;
+    if (L.pool == 1) { b += 1; a += 1; }
+    if (L.pool == 2) { int pb, pa; same_pad(L.avg_k, 1, pb, pa); b += pb; a += pa; }
+  };
+  int sb = 0, sa = 0, b, a;
+  const std::vector<Layer>& Ls = n->layers;
+  if (n->table->topo == SQUEEZE) {             // blocks: conv1, then (s1, s2_1, s2_2) per stage (build_plan)
+    field(Ls[0], b, a); sb += b; sa += a;
+    for (size_t j = 1; j + 2 < Ls.size(); j += 3) {
+      int b1, a1, b2, a2;
+      field(Ls[j], b, a); field(Ls[j + 1], b1, a1); field(Ls[j + 2], b2, a2);
+      sb += b + std::max(b1, b2); sa += a + std::max(a1, a2);
+    }
+  } else {
+    for (const Layer& L : Ls) { field(L, b, a); sb += b; sa += a; }
+  }
+  *before = sb; *after = sa;
+  return DRS_OK;
+}
+
 // squeeze-and-excitation block `index` (isprs:682-697, 1042-1050): its scope ("se1": variables <scope>_fc1/weights, ...), the block
 // whose activation it scales, channels and the reduced width C / 4
 int drs_net_se_info(const drs_net_t* n, int index, char* scope, int scope_cap, int* layer, int* channels, int* reduced) {

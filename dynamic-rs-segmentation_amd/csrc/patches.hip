@@ -5,6 +5,7 @@
 //   normalize_images           :74-81    ((x - mean[c]) / std[c] for c = 0,1,2 ONLY)
 //   create_patches_per_map     :337-400  (same gather, window positions from the host)
 //   overlap-add of logits      :1261-1284 / :1925-1949, arg-max of the average
+//   (and, beside the reference's windows, the opt-in overlap-tile inference: exact cores of whole-net tiles, drs_tile_place)
 //
 // The crop writes straight into the zero-haloed, channel-padded input slab of conv1, so no separate pad/normalise
 // pass exists.  Arithmetic on pixel values is fp64 (the reference normalises float64 patches, then feeds float32),
@@ -192,6 +193,33 @@ __global__ void stitch_accumulate_kernel(const StitchArgs a) {
   }
 }
 
+// overlap-tile inference: the core box of tile i, (y0, x0, cy0, cy1, cx0, cx1) = origin and half-open core rows / columns in image
+// coordinates, is copied out of the tile's [T][T][K] logits into prob and counted in occur.  One thread per tile pixel; the box is
+// checked here (it is device data): a box outside the image or outside its tile places nothing, and the coverage count shows the gap.
+struct TilePlaceArgs {
+  float* prob;            // [h][w][K]
+  unsigned int* occur;    // [h][w]
+  const float* logits;    // [n][T][T][K]
+  const int* boxes;       // [n][6]
+  int h, w, K, T;
+};
+
+__global__ void tile_place_kernel(const TilePlaceArgs a) {
+  const int i = blockIdx.z, ty = blockIdx.y;
+  const int tx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tx >= a.T || ty >= a.T) return;
+  const int* b = a.boxes + 6 * (size_t)i;
+  const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
+  if (y0 < 0 || x0 < 0 || y0 > a.h - a.T || x0 > a.w - a.T) return;
+  if (cy0 < y0 || cy1 > y0 + a.T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + a.T || cx0 > cx1) return;
+  const int y = y0 + ty, x = x0 + tx;
+  if (y < cy0 || y >= cy1 || x < cx0 || x >= cx1) return;
+  const float* lg = a.logits + (((size_t)i * a.T + ty) * a.T + tx) * a.K;
+  float* pp = a.prob + ((size_t)y * a.w + x) * a.K;
+  for (int k = 0; k < a.K; ++k) pp[k] = lg[k];
+  atomicAdd(a.occur + (size_t)y * a.w + x, 1u);      // (a plan whose cores overlap counts 2 there, not a lost update)
+}
+
 // arg-max over classes of prob / max(occur, 1) (first maximum); the division is by a per-pixel positive constant
 __global__ void stitch_finalize_kernel(const float* __restrict__ prob, const unsigned int* __restrict__ occur, size_t npix, int K,
                                        unsigned char* __restrict__ out) {
@@ -260,6 +288,15 @@ int drs_stitch_accumulate(float* prob, unsigned int* occur, const float* logits,
   a.row0 = y0; a.nrows = y1 - y0;
   dim3 grid((w + 255) / 256, a.nrows);
   DRS_LAUNCH(stitch_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n, void* stream) {
+  if (!prob || !occur || !logits || !boxes || K < 1 || K > 8 || T < 1 || T > h || T > w || n < 1 || n > 65535 || T > 65535) return DRS_ERR_ARG;
+  TilePlaceArgs a;
+  a.prob = prob; a.occur = occur; a.logits = logits; a.boxes = boxes; a.h = h; a.w = w; a.K = K; a.T = T;
+  dim3 grid((T + 255) / 256, T, n);
+  DRS_LAUNCH(tile_place_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   return DRS_LAUNCH_CHECK();
 }
 

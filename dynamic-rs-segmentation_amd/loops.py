@@ -1,4 +1,4 @@
-"""Step loops: training, patch validation, whole-tile sliding-window inference.
+"""Step loops: training, patch validation, whole-tile sliding-window inference (and, opt-in, overlap-tile inference).
 
 Host mirror of /root/reference/isprs_dilated_random.py `train` :1621-1851, `validation` :1569-1618,
 `validate_test` :1241-1344 and `generate_final_maps` :1854-1957 (control flow, constants, log line formats and
@@ -464,6 +464,93 @@ def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_f
     return out.view(h, w)
 
 
+# ------------------------------------------------------------------------------------------------- whole tiles, overlap-tile
+DENSE_TILE = 512        # default tile side of predict_tile_dense (capped by the image's shorter side)
+DENSE_BATCH_MAX = 8     # tiles per forward of the inference twin
+
+
+def dense_batch(plan, T, cap=DENSE_BATCH_MAX):
+    """tiles of side T per forward: the largest B <= min(cap, 8) with B*T*T < 2^24 and every activation slab the net lists, and its
+    haloed output-gradient slab, below 2^30 floats (include/drs.h conventions; the dense net's 448-channel concat slab binds first)"""
+    hmax = max(L.halo for L in plan.layers)
+    cmax = max(L.cout for L in plan.layers)
+    for b in range(min(int(cap), DENSE_BATCH_MAX), 0, -1):
+        if (b * T * T < (1 << 24) and all(b * (T + 2 * P_) ** 2 * C_ < (1 << 30) for C_, P_ in plan.buffers.values())
+                and b * (T + 2 * hmax) ** 2 * cmax < (1 << 30)):
+            return b
+    raise ValueError("dense tile side %d is too large for one forward of %s" % (T, plan.net_type))
+
+
+def dense_twin(net, T, batch_size):
+    """The inference twin of `net` for tiles of side T: a DilatedNet of the same net_type / bands / classes sized (B_t, T), cached on
+    `net` (the trained net is sized for its largest training patch, usually far below a tile).  Its parameters and moving statistics
+    are copied from `net` device to device on EVERY call (same layout: the same table), so it never lags a net that is still training."""
+    B_t = dense_batch(net.plan, T, batch_size)
+    twin = getattr(net, "_dense_twin", None)
+    if twin is None or (twin.b_max, twin.s_max) != (B_t, T):
+        from .engine import EngineNet
+        net._dense_twin = None                      # (the old twin's buffers go before the new one's are allocated)
+        twin = DilatedNet(net.plan.net_type, net.plan.channels, net.plan.K, net.wd, b_max=B_t, s_max=T, device=net.dev,
+                          arith=net.arith, engine=isinstance(net, EngineNet))
+        net._dense_twin = twin
+    twin.params.copy_(net.params)
+    twin.bn.copy_(net.bn)
+    return twin
+
+
+def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False):
+    """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
+    size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
+    pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
+    margin from every tile edge that is not an image border, and the cores partition the map.  Each tile is cropped and normalised
+    (no augmentation), run through the inference twin (dense_twin; batch_size caps its tiles per forward), and its core's logits are
+    copied into the map (drs_tile_place); labels by drs_stitch_finalize (occur = 1).  Not the reference's map: no window averaging, no
+    window-border padding.  Returns (uint8 labels [h, w] on the device, tile count), or (prob, occur, tile count) with return_sums.
+    Data parallelism: rank r takes a contiguous run of tile rows, places its cores into a zeroed map, finalizes the rows its cores own
+    and the label maps are gathered by one sum all-reduce (the cores are disjoint); with return_sums prob / occur are summed instead."""
+    from . import _lib
+    comm = comm or NoComm()
+    if net.plan.receptive_field is None:
+        raise ValueError("%s has squeeze-and-excitation blocks (a mean over the whole patch): its output has no finite receptive field, "
+                         "so there is no exact whole-tile inference; use predict_tile" % net.plan.net_type)
+    before, after = net.plan.receptive_field
+    h, w = pool.h[map_index], pool.w[map_index]
+    K = net.plan.K
+    T = int(tile) if tile else min(h, w, DENSE_TILE)
+    oy, ys, ye = P.dense_axis(h, T, before, after)
+    boxes = P.dense_tiles(h, w, T, before, after)
+    n_w = len(boxes) // len(oy)
+    twin = dense_twin(net, T, batch_size)
+    W, r = comm.world, comm.rank
+    a = [q * len(oy) // W for q in range(W + 1)]          # tile rows per rank: contiguous, as even as possible
+    mine = np.arange(a[r] * n_w, a[r + 1] * n_w)
+    prob = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
+    occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
+    st = twin._stream()
+    boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
+    for c0 in range(0, len(mine), twin.b_max):
+        sel = mine[c0:c0 + twin.b_max]
+        inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
+        P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
+        _, logits = twin.forward(len(sel), T, want_logits=True)
+        _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
+                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+    if return_sums:
+        if W > 1:
+            comm.all_reduce_sum(prob)
+            comm.all_reduce_sum(occur)
+        return prob, occur, len(boxes)
+    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
+    own0 = ys[a[r]] if a[r] < len(oy) else h
+    own1 = ys[a[r + 1]] if a[r + 1] < len(oy) else h
+    if own1 > own0:
+        _lib.call("drs_stitch_finalize", prob.data_ptr() + own0 * w * K * 4, occur.data_ptr() + own0 * w * 4, own1 - own0, w, K,
+                  out.data_ptr() + own0 * w, st)
+    if W > 1:
+        comm.all_reduce_sum(out)    # every rank wrote only the rows its cores own: the sum is the gather of the label bands
+    return out.view(h, w), len(boxes)
+
+
 def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_type, num_scales):
     """The reference picks the best size, removes it from the candidates and repeats (isprs:1370-1420)."""
     values = np.asarray(values).copy()
@@ -481,9 +568,10 @@ def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_ty
 
 
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
-                  output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs"):
+                  output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
-    isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy)."""
+    isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
+    maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before."""
     from . import _lib
     comm = comm or NoComm()
     K = net.plan.K
@@ -493,8 +581,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     all_f1 = np.zeros(len(testing_data), dtype=np.float32)
     all_f1_per_class = np.zeros(K, dtype=np.float32)
     maps = []
+    if dense_tile is not None and crop_sizes:
+        raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
     for k in range(len(testing_data)):
-        if crop_sizes:      # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
+        if dense_tile is not None:
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile)
+        elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
             pred = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm)
         else:
             pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour)
@@ -536,17 +628,23 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
-                        distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None):
+                        distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
+                        dense_tile=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
-    (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`)."""
+    (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
+    default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before."""
     comm = comm or NoComm()
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
-    crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
-                 if sized else int(values[0]))
+    if dense_tile is None:
+        crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
+                     if sized else int(values[0]))
     pool = P.TilePool(testing_data, None, net.dev)
     maps = []
     for k in range(len(testing_data)):
-        pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
+        if dense_tile is not None:
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile)
+        else:
+            pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
         maps.append(pred.cpu().numpy())
         if comm.rank == 0 and output_path:
             # isprs:1950-1955: the colour map under the reference's file names (ISPRS palette, isprs:118-139), plus the class ids as .npy

@@ -132,6 +132,13 @@ class Plan(object):
         for j in range(n_se.value):
             _lib.call("drs_net_se_info", h, j, name, 96, C.byref(li), None, None)
             self.se[li.value] = name.value.decode()
+        # receptive field of the whole net (input pixels [p - before, p + after] feed output pixel p), or None for the nets with
+        # squeeze-and-excitation blocks: their mean over the whole patch has no finite field (overlap-tile inference, loops.predict_tile_dense)
+        b, a = C.c_int(), C.c_int()
+        rc = _lib.load().drs_net_receptive_field(h, C.byref(b), C.byref(a))
+        if rc != 0 and not self.se:
+            raise _lib.DrsError("drs_net_receptive_field -> %d for %s" % (rc, self.net_type))
+        self.receptive_field = (b.value, a.value) if rc == 0 else None
         if self.dense:      # kept for callers that want the slice table (isprs:921-948)
             self.concat_off = [L.dst_coff for L in self.layers]
             self.concat_halo = self.buffers["concat"][1]

@@ -3,7 +3,8 @@
 Host mirror of /root/reference/isprs_dilated_random.py: `select_batch` :46-58, the patch-size draw
 :1727-1737 with `define_multinomial_probs` :61-71, the per-patch augmentation draws inside
 `dynamically_create_patches` :288-318 and the sliding-window enumeration of `create_patches_per_map`
-:337-400.  Index work stays on the host (it is scalar work); every per-pixel operation -- crop,
+:337-400 (beside it, the tile plan of the opt-in overlap-tile inference: `dense_tiles`).  Index work
+stays on the host (it is scalar work); every per-pixel operation -- crop,
 rotation, noise, flip, normalisation of bands 0..2, zero halo and band padding for conv1 -- happens
 in one HIP kernel (drs_crop_normalize) that writes the conv1 input slab directly.
 
@@ -90,6 +91,43 @@ def window_positions(h, w, crop_size, stride, index, batch_size, flavour="isprs"
     x = np.minimum((f // n_w) * stride, h - crop_size)
     y = np.minimum((f % n_w) * stride, w - crop_size)
     return np.stack([x, y], axis=1).astype(np.int64)
+
+
+def dense_axis(length, T, before, after):
+    """One axis of the overlap-tile plan (loops.predict_tile_dense): (origins, core starts, core ends) of the tiles of side T along an
+    axis of `length` pixels, for a net whose output pixel p depends on input pixels [p - before, p + after].
+    Origins step by T - before - after; the last tile is moved back to end at the border, as windows are (isprs:366-375).  A core
+    starts `before` pixels into its tile and ends `after` pixels early, except at an image border, which it reaches; cores are then
+    clipped so that they partition [0, length): every pixel belongs to exactly one core, and every core edge that is not an image
+    border keeps the margin from its tile's edge.  T = length: one tile."""
+    length, T, before, after = int(length), int(T), int(before), int(after)
+    if length < 1 or T < 1 or before < 0 or after < 0:
+        raise ValueError("dense tiles: length %d, T %d, margins (%d, %d)" % (length, T, before, after))
+    if T > length:
+        raise ValueError("dense tile side %d exceeds the image side %d" % (T, length))
+    if T == length:
+        return [0], [0], [length]
+    step = T - before - after
+    if step < 1:
+        raise ValueError("dense tile side %d must exceed the receptive-field margins %d + %d" % (T, before, after))
+    n = -(-(length - T) // step) + 1
+    origins = [min(i * step, length - T) for i in range(n)]
+    starts, ends = [], []
+    for i, o in enumerate(origins):
+        starts.append(0 if i == 0 else ends[-1])
+        ends.append(length if i == n - 1 else o + T - after)
+    return origins, starts, ends
+
+
+def dense_tiles(h, w, T, before, after):
+    """The overlap-tile plan of an h x w image: int64 [n][6] rows (y0, x0, cy0, cy1, cx0, cx1) -- tile origin and half-open core box in
+    image coordinates -- in row-major tile order, the product of the two axis plans (dense_axis).  Tiles are square: T <= min(h, w)."""
+    if int(T) > min(int(h), int(w)):
+        raise ValueError("dense tile side %d exceeds min(h, w) = %d (tiles are square)" % (T, min(int(h), int(w))))
+    ry, rs, re = dense_axis(h, T, before, after)
+    cx, cs, ce = dense_axis(w, T, before, after)
+    return np.array([(ry[i], cx[j], rs[i], re[i], cs[j], ce[j]) for i in range(len(ry)) for j in range(len(cx))],
+                    dtype=np.int64).reshape(-1, 6)
 
 
 # ---------------------------------------------------------------------------------------- augmentation draws

@@ -1,6 +1,6 @@
 /*
  * drs.h -- C ABI of libdrs_hip.so: the MI355X (gfx950) kernels of the dilated-CNN multi-size patch
- * training / sliding-window inference path of keillernogueira/dynamic-rs-segmentation.
+ * training / sliding-window (and opt-in overlap-tile) inference path of keillernogueira/dynamic-rs-segmentation.
  *
  * The reference has no FFI of its own: its device boundary is three `sess.run` call shapes
  * (isprs_dilated_random.py:1750-1752 train, :1274-1275 infer, :1588 validate) behind which TensorFlow runs
@@ -249,6 +249,14 @@ int drs_stitch_accumulate(float* prob, unsigned int* occur, const float* logits,
                           int first_window, int n_windows, void* stream);
 int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int w, int K, unsigned char* out,
                         void* stream);
+/* overlap-tile inference (opt-in, beside the reference's windows): n tiles of side T, each with its core box, from the
+ * device array boxes [n][6] = (y0, x0, cy0, cy1, cx0, cx1) in image coordinates (tile origin, half-open core rows / columns).  For every
+ * core pixel (y, x) the K logits logits[i][y - y0][x - x0][:] (a [n][T][T][K] block, as drs_forward writes it) are COPIED into
+ * prob[y][x][:] and occur[y][x] += 1.  Labels: drs_stitch_finalize (occur = 1: an exact arg-max, first maximum).  K <= 8,
+ * T <= min(h, w); the boxes are device data, checked on the device: a box outside the image or outside its tile places nothing (the
+ * coverage count occur, 1 everywhere after a whole plan, shows the gap).  The tile plan itself is the host's. */
+int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
+                   void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);
@@ -306,6 +314,11 @@ int drs_net_layer_info(const drs_net_t* net, int index, char* name, int name_cap
  * isprs:726-742) and the number of squeeze-and-excitation blocks (isprs:1036-1061) */
 int drs_net_info(const drs_net_t* net, char* net_type, int name_cap, float* alpha, int* c_last, char* feat_slab, int slab_cap, int* topology,
                  int* n_se);
+/* receptive field of the whole net: output pixel p depends on input pixels [p - before, p + after] along each axis (conv SAME pads,
+ * + 1 a side per 3 x 3 max-pool, + the SAME pads of a k x k average pool; chain and dense concat sum their blocks, a squeeze stage adds
+ * its squeeze block and the larger expand block).  DRS_ERR_ARG for nets with squeeze-and-excitation blocks: their global average over
+ * the patch has no finite field. */
+int drs_net_receptive_field(const drs_net_t* net, int* before, int* after);
 /* squeeze-and-excitation block `index`: scope ("se1": variables <scope>_fc1/weights ...), the block whose activation it scales,
  * channels C and the reduced width C / 4 (isprs:682-697) */
 int drs_net_se_info(const drs_net_t* net, int index, char* scope, int scope_cap, int* layer, int* channels, int* reduced);

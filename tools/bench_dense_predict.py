@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""BASELINE config 5's workload in both inference modes, in one process: the reference's sliding windows (loops.predict_tile, 64 x 64
+windows at stride 32, batches of 256) and overlap-tile inference (loops.predict_tile_dense, tiles of 512).  The mosaic, its statistics
+and the net's moving statistics are built exactly as bench.py's baseline_configs builds config 5 (6000 x 6000 x 5 on the device,
+Dilated8Pooling, moving statistics from one train-mode pass over 256 spread windows).  Every shape is warmed up first; each mode then
+runs `reps` times, alternating, timed by a host clock around a device synchronize.  Prints one JSON line.
+    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3]
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from drs_amd.net import DilatedNet  # noqa: E402
+from drs_amd import loops, patches as P  # noqa: E402
+
+NET, CH, K, WD = "dilated_grsl_rate8", 5, 6, 0.005
+PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X fp32 MFMA rate (bench.py's figure)
+
+
+def checksum(pred):
+    idx = torch.arange(pred.numel(), device=pred.device, dtype=torch.int64)
+    return int(((pred.reshape(-1).long() + 1) * (idx % 65521 + 1)).sum().item() % (1 << 61))
+
+
+def main(mosaic=6000, tile=512, reps=3):
+    dev = "cuda:0"
+    n, S, Bw = int(mosaic), 64, 256
+    g0 = torch.Generator(device=dev).manual_seed(5)
+    m = torch.rand(5, n, n, device=dev, generator=g0)
+    m[:3] = torch.nn.functional.avg_pool2d(m[:3].unsqueeze(0), 9, stride=1, padding=4, count_include_pad=False)[0]
+    m[4] *= 0.2
+    mosaic_t = m.permute(1, 2, 0).contiguous().reshape(-1)
+    mean = m[:3].mean(dim=(1, 2)).tolist()
+    std = m[:3].std(dim=(1, 2)).tolist()
+    del m
+    pool = P.TilePool([np.zeros((S, S, CH), dtype=np.float32)], None, dev, dtype=np.float32)      # shell; the mosaic is on the device
+    pool.tiles, pool.labels = mosaic_t, torch.zeros(n * n, dtype=torch.uint8, device=dev)
+    pool.h, pool.w = [n], [n]
+    pool.tile_h = torch.tensor([n], dtype=torch.int32, device=dev)
+    pool.tile_w = torch.tensor([n], dtype=torch.int32, device=dev)
+    net = DilatedNet(NET, CH, K, WD, b_max=Bw, s_max=S, device=dev, seed=42)
+    nh, nw = P.window_counts(n, n, S, S // 2)
+    spread = np.linspace(0, nh * nw - 1, Bw).astype(np.int64)
+    allpos = np.stack([np.minimum((spread // nw) * (S // 2), n - S), np.minimum((spread % nw) * (S // 2), n - S)], axis=1)
+    P.crop_to_net(net, pool, np.concatenate([np.zeros((Bw, 1), dtype=np.int64), allpos], axis=1), S, mean, std)
+    net.train_step(Bw, S, 0.0, apply_update=False)
+    torch.cuda.synchronize()
+    for i, L in enumerate(net.plan.layers):
+        mr = net.mean_rstd[i].cpu().numpy().reshape(L.cout, 2).astype(np.float64)
+        net.set_variable(L.name + "/moving_mean", mr[:, 0])
+        net.set_variable(L.name + "/moving_variance", np.maximum(1.0 / mr[:, 1] ** 2 - 1e-3, 1e-6))
+
+    T = min(n, int(tile))
+    before, after = net.plan.receptive_field
+    boxes = P.dense_tiles(n, n, T, before, after)
+    B_t = loops.dense_batch(net.plan, T)
+    # warm-up: every shape each mode launches (full and last partial batch), code objects loaded outside the timing
+    rest_w = nh * nw % Bw
+    for b in sorted({Bw, rest_w} - {0}):
+        P.crop_to_net(net, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), allpos[:b]], axis=1), S, mean, std)
+        net.forward(b, S)
+    twin = loops.dense_twin(net, T, B_t)
+    for b in sorted({B_t, len(boxes) % B_t} - {0}):
+        P.crop_to_net(twin, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), boxes[:b, :2]], axis=1), T, mean, std)
+        twin.forward(b, T)
+    torch.cuda.synchronize()
+
+    runs = {"window": [], "dense": []}
+    maps = {}
+    for _ in range(int(reps)):
+        for mode in ("window", "dense"):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if mode == "window":
+                pred, _ = loops.predict_tile(net, pool, 0, S, Bw, mean, std)
+            else:
+                pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T)
+            torch.cuda.synchronize()
+            runs[mode].append(time.perf_counter() - t0)
+            maps[mode] = pred
+    mac = net.plan.mac_per_pixel()
+    pix = {"window": nh * nw * S * S, "dense": len(boxes) * T * T}
+    out = dict(workload="BASELINE config 5: dilated_grsl_rate8 inference of a %dx%dx5 synthetic mosaic on ONE GPU; sliding windows "
+                        "64x64 at stride 32 in batches of 256 (overlap-add, the reference's map) vs overlap-tile inference at T = %d "
+                        "(exact whole-tile forward, %d tiles per forward)" % (n, n, T, B_t),
+               receptive_field=[before, after], tiles=len(boxes), windows=nh * nw, reps=int(reps))
+    for mode in ("window", "dense"):
+        best = min(runs[mode])
+        flops = 2.0 * mac * pix[mode]
+        out[mode] = dict(seconds=[round(v, 3) for v in runs[mode]], best_s=round(best, 3), map_mpx_per_s=round(n * n / best / 1e6, 2),
+                         pixel_forwards=pix[mode], flop=flops, fp32_floor_s=round(flops / (PEAK_FP32_MFMA_TFLOPS * 1e12), 3),
+                         fp32_ceiling_frac=round(flops / best / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4))
+    out["speedup_best"] = round(out["window"]["best_s"] / out["dense"]["best_s"], 3)
+    out["pixel_forward_ratio"] = round(pix["window"] / pix["dense"], 3)
+    out["maps_agree_frac"] = round(float((maps["window"] == maps["dense"]).float().mean().item()), 5)     # for information only
+    out["dense_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense"])
+    out["window_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["window"])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main(**{k: int(v) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
