@@ -59,6 +59,8 @@ SIGNATURES = {
     "drs_stitch_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drs_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_tile_place": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
+    "drs_crop_dihedral": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "drs_tile_place_dihedral": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "drs_softmax_accumulate": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
     # ---- step level (csrc/engine.hip)

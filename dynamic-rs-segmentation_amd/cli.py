@@ -5,6 +5,8 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     batch_size niter reference_crop_size reference_stride_crop net_type distribution_type probValues update_type process
   + optionally, anywhere, `--dense-tile[=T]` (validate_test / generate_final_maps): overlap-tile inference instead of the
     reference's sliding windows (loops.predict_tile_dense; T = tile side, default min(h, w, 512))
+  + optionally, anywhere, with --dense-tile only, `--dense-tta=flip|d4`: its dihedral test-time augmentation (the mean of the class
+    probabilities over the flipped / rotated tiles; predict_tile_dense's tta)
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -54,6 +56,27 @@ def parse_dense_tile(argv):
             raise ValueError("%s=%s: the tile side must be a positive integer" % (DENSE_TILE_FLAG, v))
         tile = int(v)
     return (list(argv) if tile is None else rest), tile
+
+
+DENSE_TTA_FLAG = "--dense-tta"
+
+
+def parse_dense_tta(argv):
+    """isprs flavour: the optional `--dense-tta=flip|d4` (anywhere in argv; with --dense-tile only, which main checks).  Returns (argv
+    without the flag, "flip" / "d4"), or (argv unchanged, None) without it.  Any other value, a bare flag, or the flag given twice,
+    raises ValueError."""
+    rest, tta = [], None
+    for a in argv:
+        if a != DENSE_TTA_FLAG and not a.startswith(DENSE_TTA_FLAG + "="):
+            rest.append(a)
+            continue
+        if tta is not None:
+            raise ValueError(DENSE_TTA_FLAG + " given more than once")
+        v = a[len(DENSE_TTA_FLAG) + 1:]
+        if v not in P.TTA_GROUPS:
+            raise ValueError("%s: expected %s=%s" % (a, DENSE_TTA_FLAG, "|".join(P.TTA_GROUPS)))
+        tta = v
+    return (list(argv) if tta is None else rest), tta
 
 
 def print_params(list_params, argv):
@@ -111,8 +134,11 @@ def main(argv=None, device=None, comm=None):
     argv = list(sys.argv if argv is None else argv)
     try:
         argv, dense_tile = parse_dense_tile(argv)
+        argv, dense_tta = parse_dense_tta(argv)
     except ValueError as e:
         sys.exit(str(e))
+    if dense_tta is not None and dense_tile is None:
+        sys.exit(DENSE_TTA_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if len(argv) < len(ISPRS_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
@@ -179,11 +205,11 @@ def main(argv=None, device=None, comm=None):
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, dense_tile=dense_tile)
+                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         dense_tile=dense_tile)
+                                         dense_tile=dense_tile, dense_tta=dense_tta)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -5,7 +5,8 @@
 //   normalize_images           :74-81    ((x - mean[c]) / std[c] for c = 0,1,2 ONLY)
 //   create_patches_per_map     :337-400  (same gather, window positions from the host)
 //   overlap-add of logits      :1261-1284 / :1925-1949, arg-max of the average
-//   (and, beside the reference's windows, the opt-in overlap-tile inference: exact cores of whole-net tiles, drs_tile_place)
+//   (and, beside the reference's windows, the opt-in overlap-tile inference: exact cores of whole-net tiles, drs_tile_place;
+//    its dihedral test-time augmentation: drs_crop_dihedral, drs_tile_place_dihedral)
 //
 // The crop writes straight into the zero-haloed, channel-padded input slab of conv1, so no separate pad/normalise
 // pass exists.  Arithmetic on pixel values is fp64 (the reference normalises float64 patches, then feeds float32),
@@ -220,6 +221,99 @@ __global__ void tile_place_kernel(const TilePlaceArgs a) {
   atomicAdd(a.occur + (size_t)y * a.w + x, 1u);      // (a plan whose cores overlap counts 2 there, not a lost update)
 }
 
+// ------------------------------------------------------------------------------------------------ dihedral test-time augmentation
+// A code g in 0..7 is one symmetry of the square (include/drs.h): bit 0 fx (flip columns), bit 1 fy (flip rows), bit 2 t (transpose).
+// sigma_g(i, j): flip first, then transpose -- Y[i][j] = X[sigma_g(i, j)];  sigma_g^-1(a, b): transpose first, then flip.
+__device__ __forceinline__ void dihedral_fwd(int g, int T, int i, int j, int& si, int& sj) {
+  const int fi = (g & 2) ? T - 1 - i : i, fj = (g & 1) ? T - 1 - j : j;
+  if (g & 4) { si = fj; sj = fi; } else { si = fi; sj = fj; }
+}
+__device__ __forceinline__ void dihedral_inv(int g, int T, int a, int b, int& si, int& sj) {
+  const int ta = (g & 4) ? b : a, tb = (g & 4) ? a : b;
+  si = (g & 2) ? T - 1 - ta : ta;
+  sj = (g & 1) ? T - 1 - tb : tb;
+}
+
+// conv1's haloed slab of the g-transformed T x T tile at (row, col) of map `map`: the normalisation of crop_kernel without
+// augmentation (fp64 until the one rounding on the store, bands 0..2), the source pixel permuted by sigma_g.  One thread per slab
+// pixel, so the stores are coalesced; a transposed code reads its source with a row stride (absorbed by L2 / the Infinity Cache).
+// inst is device data: a tile outside its map, or a map index out of range, leaves that patch's slab all zeros.
+struct CropDihedralArgs {
+  const void* tiles;
+  const long long* tile_off;
+  const int* tile_h; const int* tile_w;
+  int n_maps, C;
+  const int* inst;              // [B][3]: map, row, col
+  int g;
+  double mean[3], stdv[3];
+  float* out; int T, P, ld;     // [B][T+2P][T+2P][ld]
+};
+
+template <typename Tp>
+__global__ void crop_dihedral_kernel(const CropDihedralArgs a) {
+  const int Tp2 = a.T + 2 * a.P;
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx >= Tp2) return;
+  const int b = blockIdx.y / Tp2, yy = blockIdx.y - b * Tp2;
+  float* dst = a.out + ((size_t)(b * Tp2 + yy) * Tp2 + xx) * a.ld;
+  const int i = yy - a.P, j = xx - a.P;
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i >= 0 && i < a.T && j >= 0 && j < a.T) {
+    const int map = a.inst[3 * b], row = a.inst[3 * b + 1], col = a.inst[3 * b + 2];
+    if (map >= 0 && map < a.n_maps && row >= 0 && col >= 0 && row <= a.tile_h[map] - a.T && col <= a.tile_w[map] - a.T) {
+      int si, sj;
+      dihedral_fwd(a.g, a.T, i, j, si, sj);
+      const Tp* src = reinterpret_cast<const Tp*>(a.tiles) + a.tile_off[map] + ((size_t)(row + si) * a.tile_w[map] + (col + sj)) * a.C;
+      for (int c = 0; c < a.C; ++c) {
+        double e = (double)src[c];
+        if (c < 3) e = (e - a.mean[c]) / a.stdv[c];
+        v[c] = (float)e;
+      }
+    }
+  }
+  for (int c4 = 0; c4 < a.ld; c4 += 4) {
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (c4 + k) < 8 ? v[(c4 + k) & 7] : 0.f;
+    *reinterpret_cast<f32x4*>(dst + c4) = o;
+  }
+}
+
+// the core of tile i (boxes as tile_place_kernel, checked the same way) gets the softmax of the logits the net computed for the
+// g-transformed tile, mapped back by sigma_g^-1, ADDED into acc; occur counts.  One thread per tile pixel in image order (coalesced
+// read-modify-write of acc); the cores of one plan are disjoint, so the plain read-modify-write is race-free and deterministic.
+struct TilePlaceDihedralArgs {
+  float* acc;             // [h][w][K]
+  unsigned int* occur;    // [h][w]
+  const float* logits;    // [n][T][T][K], on the transformed tile's grid
+  const int* boxes;       // [n][6]
+  int h, w, K, T, g;
+};
+
+__global__ void tile_place_dihedral_kernel(const TilePlaceDihedralArgs a) {
+  const int i = blockIdx.z, ty = blockIdx.y;
+  const int tx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tx >= a.T || ty >= a.T) return;
+  const int* b = a.boxes + 6 * (size_t)i;
+  const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
+  if (y0 < 0 || x0 < 0 || y0 > a.h - a.T || x0 > a.w - a.T) return;
+  if (cy0 < y0 || cy1 > y0 + a.T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + a.T || cx0 > cx1) return;
+  const int y = y0 + ty, x = x0 + tx;
+  if (y < cy0 || y >= cy1 || x < cx0 || x >= cx1) return;
+  int si, sj;
+  dihedral_inv(a.g, a.T, ty, tx, si, sj);
+  const float* lg = a.logits + (((size_t)i * a.T + si) * a.T + sj) * a.K;
+  float e[8], mx = lg[0], sum = 0.f;
+  for (int k = 1; k < a.K; ++k) mx = fmaxf(mx, lg[k]);
+  for (int k = 0; k < a.K; ++k) {
+    e[k] = expf(lg[k] - mx);            // max-subtracted: unlike the reference's softmax() (isprs:38-43), on purpose
+    sum += e[k];
+  }
+  float* pp = a.acc + ((size_t)y * a.w + x) * a.K;
+  for (int k = 0; k < a.K; ++k) pp[k] += e[k] / sum;
+  atomicAdd(a.occur + (size_t)y * a.w + x, 1u);
+}
+
 // arg-max over classes of prob / max(occur, 1) (first maximum); the division is by a per-pixel positive constant
 __global__ void stitch_finalize_kernel(const float* __restrict__ prob, const unsigned int* __restrict__ occur, size_t npix, int K,
                                        unsigned char* __restrict__ out) {
@@ -297,6 +391,34 @@ int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h,
   a.prob = prob; a.occur = occur; a.logits = logits; a.boxes = boxes; a.h = h; a.w = w; a.K = K; a.T = T;
   dim3 grid((T + 255) / 256, T, n);
   DRS_LAUNCH(tile_place_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_crop_dihedral(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
+                      int C, const int* inst, int g, const double* mean3, const double* std3, int B, int T, int P, int ld, float* out,
+                      void* stream) {
+  if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
+  const int Tp2 = T + 2 * P;
+  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
+  CropDihedralArgs a;
+  a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst; a.g = g;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+  a.out = out; a.T = T; a.P = P; a.ld = ld;
+  dim3 grid((Tp2 + 63) / 64, B * Tp2);
+  if (tiles_are_f64) DRS_LAUNCH(crop_dihedral_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  else DRS_LAUNCH(crop_dihedral_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
+                            int g, void* stream) {
+  if (!acc || !occur || !logits || !boxes || K < 1 || K > 8 || T < 1 || T > h || T > w || n < 1 || n > 65535 || T > 65535) return DRS_ERR_ARG;
+  if (g < 0 || g > 7) return DRS_ERR_ARG;
+  TilePlaceDihedralArgs a;
+  a.acc = acc; a.occur = occur; a.logits = logits; a.boxes = boxes; a.h = h; a.w = w; a.K = K; a.T = T; a.g = g;
+  dim3 grid((T + 255) / 256, T, n);
+  DRS_LAUNCH(tile_place_dihedral_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   return DRS_LAUNCH_CHECK();
 }
 

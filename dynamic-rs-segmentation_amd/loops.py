@@ -498,7 +498,7 @@ def dense_twin(net, T, batch_size):
     return twin
 
 
-def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False):
+def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None):
     """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
     size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
     pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
@@ -507,13 +507,21 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     copied into the map (drs_tile_place); labels by drs_stitch_finalize (occur = 1).  Not the reference's map: no window averaging, no
     window-border padding.  Returns (uint8 labels [h, w] on the device, tile count), or (prob, occur, tile count) with return_sums.
     Data parallelism: rank r takes a contiguous run of tile rows, places its cores into a zeroed map, finalizes the rows its cores own
-    and the label maps are gathered by one sum all-reduce (the cores are disjoint); with return_sums prob / occur are summed instead."""
+    and the label maps are gathered by one sum all-reduce (the cores are disjoint); with return_sums prob / occur are summed instead.
+    tta ("flip", "d4" or a tuple of codes 0..7; patches.tta_group): dihedral test-time augmentation.  Every tile is run
+    once per code g of the group, ascending: cropped transformed by g (drs_crop_dihedral), forwarded, and the softmax of its logits
+    mapped back by g^-1 is ADDED into the map (drs_tile_place_dihedral) -- per pixel, the sum over G of softmax(F(g.X)) put back on X's
+    grid, occur = |G|; labels the arg-max of that mean.  A flip swaps `before` and `after` on its axis and a transpose swaps the axes,
+    so with any g != 0 the plan keeps the symmetric margin max(before, after) on both sides."""
     from . import _lib
     comm = comm or NoComm()
     if net.plan.receptive_field is None:
         raise ValueError("%s has squeeze-and-excitation blocks (a mean over the whole patch): its output has no finite receptive field, "
                          "so there is no exact whole-tile inference; use predict_tile" % net.plan.net_type)
     before, after = net.plan.receptive_field
+    G = None if tta is None else P.tta_group(tta)
+    if G is not None and any(G):
+        before = after = max(before, after)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     T = int(tile) if tile else min(h, w, DENSE_TILE)
@@ -531,10 +539,17 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     for c0 in range(0, len(mine), twin.b_max):
         sel = mine[c0:c0 + twin.b_max]
         inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
-        P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
-        _, logits = twin.forward(len(sel), T, want_logits=True)
-        _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
-                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+        if G is None:
+            P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
+            _, logits = twin.forward(len(sel), T, want_logits=True)
+            _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
+                      boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+            continue
+        for g in G:         # ascending: the per-pixel order of the sum
+            P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, g)
+            _, logits = twin.forward(len(sel), T, want_logits=True)
+            _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
+                      boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
     if return_sums:
         if W > 1:
             comm.all_reduce_sum(prob)
@@ -567,13 +582,25 @@ def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_ty
     return chosen
 
 
+def _check_dense_tta(dense_tile, dense_tta):
+    if dense_tta is None:
+        return
+    if dense_tile is None:
+        raise ValueError("test-time augmentation needs overlap-tile inference (dense_tile): the sliding-window map depends on the "
+                         "patch size and has no exact dihedral form")
+    P.tta_group(dense_tta)
+
+
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
-                  output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None):
+                  output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
+                  dense_tta=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
-    maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before."""
+    maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
+    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta)."""
     from . import _lib
     comm = comm or NoComm()
+    _check_dense_tta(dense_tile, dense_tta)
     K = net.plan.K
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
@@ -585,7 +612,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile)
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta)
         elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
             pred = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm)
         else:
@@ -629,11 +656,13 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None):
+                        dense_tile=None, dense_tta=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
-    default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before."""
+    default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
+    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta)."""
     comm = comm or NoComm()
+    _check_dense_tta(dense_tile, dense_tta)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
         crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
@@ -642,7 +671,7 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     maps = []
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile)
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta)
         else:
             pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
         maps.append(pred.cpu().numpy())

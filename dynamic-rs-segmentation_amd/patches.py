@@ -6,7 +6,8 @@ Host mirror of /root/reference/isprs_dilated_random.py: `select_batch` :46-58, t
 :337-400 (beside it, the tile plan of the opt-in overlap-tile inference: `dense_tiles`).  Index work
 stays on the host (it is scalar work); every per-pixel operation -- crop,
 rotation, noise, flip, normalisation of bands 0..2, zero halo and band padding for conv1 -- happens
-in one HIP kernel (drs_crop_normalize) that writes the conv1 input slab directly.
+in one HIP kernel (drs_crop_normalize) that writes the conv1 input slab directly (and, for the test-time
+augmentation of overlap-tile inference, the dihedral symmetries of whole tiles: drs_crop_dihedral).
 
 RNG: like the reference, draws come from the global `random` / `numpy.random` streams in the
 reference's call order, so seeding both reproduces the reference's sequence.
@@ -130,6 +131,53 @@ def dense_tiles(h, w, T, before, after):
                     dtype=np.int64).reshape(-1, 6)
 
 
+# ------------------------------------------------------------------- dihedral test-time augmentation (D4)
+TTA_GROUPS = {"flip": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def dihedral_apply(x, g, inverse=False):
+    """The symmetry g (0..7: bit 0 fx = flip columns, bit 1 fy = flip rows, bit 2 t = transpose; include/drs.h) on the first two axes of
+    x, which need not be square: Y = Z[::-1 if fy, ::-1 if fx] with Z = x.swapaxes(0, 1) if t.  inverse=True applies g^-1 (undo the
+    flips, then transpose back), which puts a map computed on Y back on x's grid.  Returns a view."""
+    g = int(g)
+    if not 0 <= g <= 7:
+        raise ValueError("dihedral code %r: must be 0..7" % g)
+    x = np.asarray(x)
+    fy, fx = slice(None, None, -1 if g & 2 else 1), slice(None, None, -1 if g & 1 else 1)
+    if inverse:
+        x = x[fy, fx]
+        return x.swapaxes(0, 1) if g & 4 else x
+    z = x.swapaxes(0, 1) if g & 4 else x
+    return z[fy, fx]
+
+
+def dihedral_index(g, T):
+    """The numpy statement of sigma_g and sigma_g^-1 on a T x T tile: ((I, J), (Ii, Ji)), int64 [T][T] each, such that the transformed
+    tile is Y = X[I, J] (Y[i][j] = X[sigma_g(i, j)]: flip, then transpose) and logits L of Y land on X's grid as L[Ii, Ji]
+    (sigma_g^-1(a, b): transpose, then flip)."""
+    T = int(T)
+    ii, jj = np.meshgrid(np.arange(T), np.arange(T), indexing="ij")
+    grid = np.stack([ii, jj], axis=-1)
+    fwd = np.ascontiguousarray(dihedral_apply(grid, g))
+    inv = np.ascontiguousarray(dihedral_apply(grid, g, inverse=True))
+    return (fwd[..., 0], fwd[..., 1]), (inv[..., 0], inv[..., 1])
+
+
+def tta_group(tta):
+    """The codes of a test-time augmentation group, ascending: "flip" = (0, 1, 2, 3), "d4" = 0..7, or an explicit tuple / list of
+    distinct codes in 0..7 (e.g. (5,)).  Anything else raises ValueError."""
+    if isinstance(tta, str):
+        if tta not in TTA_GROUPS:
+            raise ValueError("test-time augmentation %r: expected one of %s or a tuple of codes 0..7" % (tta, "|".join(TTA_GROUPS)))
+        return TTA_GROUPS[tta]
+    if not isinstance(tta, (tuple, list)) or not tta:
+        raise ValueError("test-time augmentation %r: expected one of %s or a tuple of codes 0..7" % (tta, "|".join(TTA_GROUPS)))
+    if not all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) and 0 <= c <= 7 for c in tta) or len(set(tta)) != len(tta):
+        raise ValueError("test-time augmentation %r: codes must be distinct integers in 0..7" % (tta,))
+    codes = [int(c) for c in tta]
+    return tuple(sorted(codes))
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its
@@ -248,7 +296,7 @@ class _Staging(object):
             self.events[k].synchronize()              # the copy issued SLOTS steps ago has long finished
         B = len(inst)
         h = self.host[k].numpy()
-        h[self.o_inst:self.o_inst + 16 * B].view(np.int32)[:] = inst.reshape(-1)
+        h[self.o_inst:self.o_inst + 4 * inst.size].view(np.int32)[:] = inst.reshape(-1)      # [B][4], or [B][3] (crop_dihedral_to_net)
         if aug is not None:
             h[self.o_rot:self.o_rot + 48 * B].view(np.float64)[:] = aug.rot.reshape(-1)
             h[self.o_ron:self.o_ron + B] = aug.rot_on
@@ -295,6 +343,28 @@ def crop_to_net(net, pool, instances, S, mean, std, aug=None, void_label=-1, qua
               (2 if getattr(mean, "dtype", None) == np.float64 else 1) if quantize_f16 else 0, net._stream())
     net._keep = noise                                            # alive until the stream has consumed it
     return inst[:, 1:3]
+
+
+def crop_dihedral_to_net(net, pool, instances, T, mean, std, g):
+    """The test-time-augmentation crop beside crop_to_net (loops.predict_tile_dense with tta): fills net's conv1 slab with the T x T
+    tiles at `instances` rows (map, row, col), each transformed by the dihedral code g (dihedral_apply) and normalised as crop_to_net
+    normalises (drs_crop_dihedral; no augmentation, labels or mask).  No shift-back: a tile that does not lie inside its map is caught
+    on the device and leaves a zero slab."""
+    import ctypes as C
+    B = len(instances)
+    net._check(B, T)
+    inst = np.ascontiguousarray(np.asarray(instances, dtype=np.int64)[:, :3].astype(np.int32))
+    stg = getattr(net, "_staging", None)
+    if stg is None:
+        stg = net._staging = _Staging(net.dev, net.b_max)
+    p_inst = stg.upload(inst, None)[0]
+    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
+    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
+    m3c, s3c = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)       # HOST pointers: copied into the kernel arguments
+    slab, P, ld = net.input_slab()
+    _lib.call("drs_crop_dihedral", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(),
+              pool.tile_w.data_ptr(), len(pool.h), pool.C, p_inst, int(g), C.cast(m3c, C.c_void_p), C.cast(s3c, C.c_void_p), B, T, P,
+              ld, slab.data_ptr(), net._stream())
 
 
 def pack_feed(net, batch_x, batch_y, crop_size, mask=None, acc_mask=None):

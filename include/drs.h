@@ -257,6 +257,26 @@ int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int
  * coverage count occur, 1 everywhere after a whole plan, shows the gap).  The tile plan itself is the host's. */
 int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
                    void* stream);
+/* dihedral test-time augmentation of overlap-tile inference (opt-in).  A transform code g in 0..7 is one of the 8
+ * symmetries of the square (the group D4): bit 0 = fx (flip columns), bit 1 = fy (flip rows), bit 2 = t (transpose).  For a T x T
+ * tile X the transformed tile is Y[i][j] = X[sigma_g(i, j)] with
+ *     (i', j') = (fy ? T-1-i : i, fx ? T-1-j : j),   sigma_g(i, j) = t ? (j', i') : (i', j')      (flip, then transpose)
+ * and logits L of Y go back onto X's grid through sigma_g^-1(a, b): transpose first, then flip.  sigma_g != sigma_g^-1 exactly for
+ * g = 5 and g = 6 (the two quarter-turns).  drs_crop_normalize's flip codes are g = 2 (flip 1, flipud) and g = 1 (flip 2, fliplr).
+ *
+ * drs_crop_dihedral: conv1's input slab out [B][T+2P][T+2P][ld] of the g-transformed T x T tiles inst [B][3] = (map, row, col)
+ * (device data), normalised as drs_crop_normalize normalises (fp64 until one rounding to fp32 on the store, bands 0..2 only; mean3 /
+ * std3 are HOST pointers), with no augmentation, labels or mask; halo and channels C..ld-1 are zero.  A tile that does not lie
+ * inside its map, or a map index outside [0, n_maps), is caught on the device: that patch's slab is all zeros.  g = 0 is
+ * drs_crop_normalize with flip 0 and no augmentation, bit for bit.
+ * drs_tile_place_dihedral: boxes as drs_tile_place (same device-side checks); for every core pixel (y, x) at tile-local
+ * (a, b) = (y - y0, x - x0), softmax_k(logits[i][sigma_g^-1(a, b)][:]) (max-subtracted, fp32, classes summed in order) is ADDED
+ * into acc[y][x][:] and occur[y][x] += 1.  K <= 8.  The cores of one call must be disjoint (plain read-modify-write of acc). */
+int drs_crop_dihedral(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
+                      int C, const int* inst, int g, const double* mean3, const double* std3, int B, int T, int P, int ld, float* out,
+                      void* stream);
+int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
+                            int g, void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);

@@ -4,7 +4,9 @@ windows at stride 32, batches of 256) and overlap-tile inference (loops.predict_
 and the net's moving statistics are built exactly as bench.py's baseline_configs builds config 5 (6000 x 6000 x 5 on the device,
 Dilated8Pooling, moving statistics from one train-mode pass over 256 spread windows).  Every shape is warmed up first; each mode then
 runs `reps` times, alternating, timed by a host clock around a device synchronize.  Prints one JSON line.
-    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3]
+tta=flip|d4 adds a third mode: overlap-tile inference with that dihedral test-time augmentation (predict_tile_dense(..., tta=...)),
+on its own symmetric-margin plan.
+    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3] [tta=flip|d4]
 """
 import json
 import os
@@ -27,7 +29,7 @@ def checksum(pred):
     return int(((pred.reshape(-1).long() + 1) * (idx % 65521 + 1)).sum().item() % (1 << 61))
 
 
-def main(mosaic=6000, tile=512, reps=3):
+def main(mosaic=6000, tile=512, reps=3, tta=None):
     dev = "cuda:0"
     n, S, Bw = int(mosaic), 64, 256
     g0 = torch.Generator(device=dev).manual_seed(5)
@@ -68,28 +70,43 @@ def main(mosaic=6000, tile=512, reps=3):
     for b in sorted({B_t, len(boxes) % B_t} - {0}):
         P.crop_to_net(twin, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), boxes[:b, :2]], axis=1), T, mean, std)
         twin.forward(b, T)
+    modes = ("window", "dense")
+    if tta is not None:
+        G = P.tta_group(tta)
+        m = max(before, after)
+        boxes_tta = P.dense_tiles(n, n, T, m, m)
+        for b in sorted({B_t, len(boxes_tta) % B_t} - {0}):
+            for g in G:
+                P.crop_dihedral_to_net(twin, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), boxes_tta[:b, :2]], axis=1), T,
+                                       mean, std, g)
+                twin.forward(b, T)
+        modes = modes + ("dense_tta",)
     torch.cuda.synchronize()
 
-    runs = {"window": [], "dense": []}
+    runs = {mode: [] for mode in modes}
     maps = {}
     for _ in range(int(reps)):
-        for mode in ("window", "dense"):
+        for mode in modes:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             if mode == "window":
                 pred, _ = loops.predict_tile(net, pool, 0, S, Bw, mean, std)
-            else:
+            elif mode == "dense":
                 pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T)
+            else:
+                pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T, tta=tta)
             torch.cuda.synchronize()
             runs[mode].append(time.perf_counter() - t0)
             maps[mode] = pred
     mac = net.plan.mac_per_pixel()
     pix = {"window": nh * nw * S * S, "dense": len(boxes) * T * T}
+    if tta is not None:
+        pix["dense_tta"] = len(G) * len(boxes_tta) * T * T
     out = dict(workload="BASELINE config 5: dilated_grsl_rate8 inference of a %dx%dx5 synthetic mosaic on ONE GPU; sliding windows "
                         "64x64 at stride 32 in batches of 256 (overlap-add, the reference's map) vs overlap-tile inference at T = %d "
                         "(exact whole-tile forward, %d tiles per forward)" % (n, n, T, B_t),
                receptive_field=[before, after], tiles=len(boxes), windows=nh * nw, reps=int(reps))
-    for mode in ("window", "dense"):
+    for mode in modes:
         best = min(runs[mode])
         flops = 2.0 * mac * pix[mode]
         out[mode] = dict(seconds=[round(v, 3) for v in runs[mode]], best_s=round(best, 3), map_mpx_per_s=round(n * n / best / 1e6, 2),
@@ -98,10 +115,15 @@ def main(mosaic=6000, tile=512, reps=3):
     out["speedup_best"] = round(out["window"]["best_s"] / out["dense"]["best_s"], 3)
     out["pixel_forward_ratio"] = round(pix["window"] / pix["dense"], 3)
     out["maps_agree_frac"] = round(float((maps["window"] == maps["dense"]).float().mean().item()), 5)     # for information only
+    if tta is not None:
+        out["tta"] = dict(group=tta, codes=list(G), tiles=len(boxes_tta), symmetric_margin=m,
+                          cost_vs_dense=round(out["dense_tta"]["best_s"] / out["dense"]["best_s"], 3),
+                          maps_agree_with_dense_frac=round(float((maps["dense_tta"] == maps["dense"]).float().mean().item()), 5),
+                          map_checksum="sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense_tta"]))
     out["dense_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense"])
     out["window_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["window"])
     print(json.dumps(out))
 
 
 if __name__ == "__main__":
-    main(**{k: int(v) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
+    main(**{k: (v if k == "tta" else int(v)) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
