@@ -61,6 +61,8 @@ SIGNATURES = {
     "drs_tile_place": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "drs_crop_dihedral": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "drs_tile_place_dihedral": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
+    "drs_crop_resampled": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "drs_resample_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "drs_softmax_accumulate": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
     # ---- step level (csrc/engine.hip)

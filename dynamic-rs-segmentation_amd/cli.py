@@ -7,6 +7,9 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     reference's sliding windows (loops.predict_tile_dense; T = tile side, default min(h, w, 512))
   + optionally, anywhere, with --dense-tile only, `--dense-tta=flip|d4`: its dihedral test-time augmentation (the mean of the class
     probabilities over the flipped / rotated tiles; predict_tile_dense's tta)
+  + optionally, anywhere, with --dense-tile only, `--dense-scales=0.75,1,1.25`: its multi-scale test-time augmentation (the sum of
+    the class probabilities of the image resampled by each factor, resampled back; predict_tile_dense's scales), with or without
+    --dense-tta
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -79,6 +82,31 @@ def parse_dense_tta(argv):
     return (list(argv) if tta is None else rest), tta
 
 
+DENSE_SCALES_FLAG = "--dense-scales"
+
+
+def parse_dense_scales(argv):
+    """isprs flavour: the optional `--dense-scales=s1,s2,...` (anywhere in argv; with --dense-tile only, which main checks).  Returns
+    (argv without the flag, tuple of floats; patches.check_scales), or (argv unchanged, None) without it.  A bare flag, a malformed
+    or invalid list, or the flag given twice, raises ValueError."""
+    rest, scales = [], None
+    for a in argv:
+        if a != DENSE_SCALES_FLAG and not a.startswith(DENSE_SCALES_FLAG + "="):
+            rest.append(a)
+            continue
+        if scales is not None:
+            raise ValueError(DENSE_SCALES_FLAG + " given more than once")
+        v = a[len(DENSE_SCALES_FLAG) + 1:]
+        try:
+            vals = [float(t) for t in v.split(",")] if v and v == v.strip() and " " not in v else None
+        except ValueError:
+            vals = None
+        if vals is None:
+            raise ValueError("%s: expected %s=s1,s2,... (factors such as 0.75,1,1.25)" % (a, DENSE_SCALES_FLAG))
+        scales = P.check_scales(vals)
+    return (list(argv) if scales is None else rest), scales
+
+
 def print_params(list_params, argv):
     print("+" * 97)
     for i in range(1, len(argv)):
@@ -135,10 +163,13 @@ def main(argv=None, device=None, comm=None):
     try:
         argv, dense_tile = parse_dense_tile(argv)
         argv, dense_tta = parse_dense_tta(argv)
+        argv, dense_scales = parse_dense_scales(argv)
     except ValueError as e:
         sys.exit(str(e))
     if dense_tta is not None and dense_tile is None:
         sys.exit(DENSE_TTA_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
+    if dense_scales is not None and dense_tile is None:
+        sys.exit(DENSE_SCALES_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if len(argv) < len(ISPRS_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
@@ -205,11 +236,11 @@ def main(argv=None, device=None, comm=None):
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta)
+                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         dense_tile=dense_tile, dense_tta=dense_tta)
+                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

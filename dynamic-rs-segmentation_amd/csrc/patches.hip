@@ -6,7 +6,8 @@
 //   create_patches_per_map     :337-400  (same gather, window positions from the host)
 //   overlap-add of logits      :1261-1284 / :1925-1949, arg-max of the average
 //   (and, beside the reference's windows, the opt-in overlap-tile inference: exact cores of whole-net tiles, drs_tile_place;
-//    its dihedral test-time augmentation: drs_crop_dihedral, drs_tile_place_dihedral)
+//    its dihedral test-time augmentation: drs_crop_dihedral, drs_tile_place_dihedral; its multi-scale test-time augmentation:
+//    drs_crop_resampled, drs_resample_accumulate)
 //
 // The crop writes straight into the zero-haloed, channel-padded input slab of conv1, so no separate pad/normalise
 // pass exists.  Arithmetic on pixel values is fp64 (the reference normalises float64 patches, then feeds float32),
@@ -314,6 +315,111 @@ __global__ void tile_place_dihedral_kernel(const TilePlaceDihedralArgs a) {
   atomicAdd(a.occur + (size_t)y * a.w + x, 1u);
 }
 
+// ------------------------------------------------------------------------------------------- multi-scale test-time augmentation
+// One axis of the bilinear resampling D(n -> ns) with half-pixel centres (torch interpolate, bilinear, align_corners=False, no
+// antialias): output index d reads source i0, i1 with weight l on i1.  fp64; at ns == n: (d, d, 0) exactly.
+__device__ __forceinline__ void resample_axis(int d, int n, int ns, int& i0, int& i1, double& l) {
+  double src = ((double)d + 0.5) * ((double)n / (double)ns) - 0.5;
+  if (src < 0.0) src = 0.0;
+  i0 = (int)src;
+  if (i0 > n - 1) i0 = n - 1;
+  i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+  l = src - (double)i0;
+}
+
+// conv1's haloed slab of the g-transformed T x T tile at (row, col) of map `map` resampled to hs x ws: the slab pixel's source on the
+// scaled grid is sigma_g as in crop_dihedral_kernel, its value the bilinear mix of four source pixels in fp64, then the normalisation
+// of crop_kernel (bands 0..2) and one rounding.  One fused gather: no resized image exists.  One thread per slab pixel in store order.
+struct CropResampledArgs {
+  const void* tiles;
+  const long long* tile_off;
+  const int* tile_h; const int* tile_w;
+  int n_maps, C;
+  const int* inst;              // [B][3]: map, row, col on the hs x ws grid
+  int hs, ws, g;
+  double mean[3], stdv[3];
+  float* out; int T, P, ld;     // [B][T+2P][T+2P][ld]
+};
+
+template <typename Tp>
+__global__ void crop_resampled_kernel(const CropResampledArgs a) {
+  const int Tp2 = a.T + 2 * a.P;
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx >= Tp2) return;
+  const int b = blockIdx.y / Tp2, yy = blockIdx.y - b * Tp2;
+  float* dst = a.out + ((size_t)(b * Tp2 + yy) * Tp2 + xx) * a.ld;
+  const int i = yy - a.P, j = xx - a.P;
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i >= 0 && i < a.T && j >= 0 && j < a.T) {
+    const int map = a.inst[3 * b], row = a.inst[3 * b + 1], col = a.inst[3 * b + 2];
+    if (map >= 0 && map < a.n_maps && row >= 0 && col >= 0 && row <= a.hs - a.T && col <= a.ws - a.T) {
+      int si, sj;
+      dihedral_fwd(a.g, a.T, i, j, si, sj);
+      const int h = a.tile_h[map], w = a.tile_w[map];
+      int y0, y1, x0, x1;
+      double ly, lx;
+      resample_axis(row + si, h, a.hs, y0, y1, ly);
+      resample_axis(col + sj, w, a.ws, x0, x1, lx);
+      const Tp* base = reinterpret_cast<const Tp*>(a.tiles) + a.tile_off[map];
+      const Tp* s00 = base + ((size_t)y0 * w + x0) * a.C;
+      const Tp* s01 = base + ((size_t)y0 * w + x1) * a.C;
+      const Tp* s10 = base + ((size_t)y1 * w + x0) * a.C;
+      const Tp* s11 = base + ((size_t)y1 * w + x1) * a.C;
+      for (int c = 0; c < a.C; ++c) {
+        double e = (1.0 - ly) * ((1.0 - lx) * (double)s00[c] + lx * (double)s01[c]) +
+                   ly * ((1.0 - lx) * (double)s10[c] + lx * (double)s11[c]);
+        if (c < 3) e = (e - a.mean[c]) / a.stdv[c];
+        v[c] = (float)e;
+      }
+    }
+  }
+  for (int c4 = 0; c4 < a.ld; c4 += 4) {
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (c4 + k) < 8 ? v[(c4 + k) & 7] : 0.f;
+    *reinterpret_cast<f32x4*>(dst + c4) = o;
+  }
+}
+
+// the class-probability vector of pixel q of an hs x ws map: src / occur (a probability sum, src_is_prob) or the max-subtracted
+// softmax of src / occur (logits), written as in tile_place_dihedral_kernel; occur 0 counts as 1
+__device__ __forceinline__ void prob_vector(const float* src, const unsigned int* occur, size_t q, int K, int src_is_prob, float* p) {
+  const unsigned int o = occur[q];
+  const float oc = (float)(o ? o : 1u);
+  const float* s = src + q * K;
+  if (src_is_prob) {
+    for (int k = 0; k < K; ++k) p[k] = s[k] / oc;
+    return;
+  }
+  float mx = s[0] / oc, sum = 0.f;
+  for (int k = 1; k < K; ++k) mx = fmaxf(mx, s[k] / oc);
+  for (int k = 0; k < K; ++k) {
+    p[k] = expf(s[k] / oc - mx);
+    sum += p[k];
+  }
+  for (int k = 0; k < K; ++k) p[k] = p[k] / sum;
+}
+
+// acc[h][w][K] += U(hs x ws -> h x w) of the probability vectors: one thread per output pixel in image order (coalesced
+// read-modify-write of acc); weights in fp64, rounded once, the four vectors mixed in fp32 in the order of include/drs.h
+__global__ void resample_accumulate_kernel(const float* __restrict__ src, const unsigned int* __restrict__ occur, int hs, int ws, int K,
+                                           int src_is_prob, int h, int w, float* __restrict__ acc) {
+  const int y = blockIdx.y, x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= w || y >= h) return;
+  int y0, y1, x0, x1;
+  double ly, lx;
+  resample_axis(y, hs, h, y0, y1, ly);
+  resample_axis(x, ws, w, x0, x1, lx);
+  const float wy0 = (float)(1.0 - ly), wy1 = (float)ly, wx0 = (float)(1.0 - lx), wx1 = (float)lx;
+  float p00[8], p01[8], p10[8], p11[8];
+  prob_vector(src, occur, (size_t)y0 * ws + x0, K, src_is_prob, p00);
+  prob_vector(src, occur, (size_t)y0 * ws + x1, K, src_is_prob, p01);
+  prob_vector(src, occur, (size_t)y1 * ws + x0, K, src_is_prob, p10);
+  prob_vector(src, occur, (size_t)y1 * ws + x1, K, src_is_prob, p11);
+  float* pp = acc + ((size_t)y * w + x) * K;
+  for (int k = 0; k < K; ++k) pp[k] += wy0 * (wx0 * p00[k] + wx1 * p01[k]) + wy1 * (wx0 * p10[k] + wx1 * p11[k]);
+}
+
 // arg-max over classes of prob / max(occur, 1) (first maximum); the division is by a per-pixel positive constant
 __global__ void stitch_finalize_kernel(const float* __restrict__ prob, const unsigned int* __restrict__ occur, size_t npix, int K,
                                        unsigned char* __restrict__ out) {
@@ -419,6 +525,33 @@ int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits
   a.acc = acc; a.occur = occur; a.logits = logits; a.boxes = boxes; a.h = h; a.w = w; a.K = K; a.T = T; a.g = g;
   dim3 grid((T + 255) / 256, T, n);
   DRS_LAUNCH(tile_place_dihedral_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_crop_resampled(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
+                       int C, const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
+                       float* out, void* stream) {
+  if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
+  if (hs < 1 || ws < 1) return DRS_ERR_ARG;
+  const int Tp2 = T + 2 * P;
+  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
+  CropResampledArgs a;
+  a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst;
+  a.hs = hs; a.ws = ws; a.g = g;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+  a.out = out; a.T = T; a.P = P; a.ld = ld;
+  dim3 grid((Tp2 + 63) / 64, B * Tp2);
+  if (tiles_are_f64) DRS_LAUNCH(crop_resampled_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  else DRS_LAUNCH(crop_resampled_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs, int ws, int K, int src_is_prob, int h, int w, float* acc,
+                            void* stream) {
+  if (!src || !occur || !acc || K < 1 || K > 8 || hs < 1 || ws < 1 || h < 1 || w < 1 || h > 65535) return DRS_ERR_ARG;
+  dim3 grid((w + 255) / 256, h);
+  DRS_LAUNCH(resample_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, occur, hs, ws, K, src_is_prob, h, w, acc);
   return DRS_LAUNCH_CHECK();
 }
 

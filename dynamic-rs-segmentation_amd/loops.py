@@ -498,7 +498,8 @@ def dense_twin(net, T, batch_size):
     return twin
 
 
-def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None):
+def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None,
+                       scales=None):
     """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
     size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
     pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
@@ -512,7 +513,9 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     once per code g of the group, ascending: cropped transformed by g (drs_crop_dihedral), forwarded, and the softmax of its logits
     mapped back by g^-1 is ADDED into the map (drs_tile_place_dihedral) -- per pixel, the sum over G of softmax(F(g.X)) put back on X's
     grid, occur = |G|; labels the arg-max of that mean.  A flip swaps `before` and `after` on its axis and a transpose swaps the axes,
-    so with any g != 0 the plan keeps the symmetric margin max(before, after) on both sides."""
+    so with any g != 0 the plan keeps the symmetric margin max(before, after) on both sides.
+    scales (a list of distinct factors in [0.25, 4]; patches.check_scales): multi-scale test-time augmentation, with or
+    without tta -- see _predict_tile_dense_scales."""
     from . import _lib
     comm = comm or NoComm()
     if net.plan.receptive_field is None:
@@ -522,6 +525,9 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     G = None if tta is None else P.tta_group(tta)
     if G is not None and any(G):
         before = after = max(before, after)
+    if scales is not None:
+        return _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G,
+                                          P.check_scales(scales), before, after)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     T = int(tile) if tile else min(h, w, DENSE_TILE)
@@ -566,6 +572,66 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     return out.view(h, w), len(boxes)
 
 
+def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after):
+    """predict_tile_dense with scales.  For each scale s, in the order given: the map resampled to hs x ws
+    (patches.scaled_size; bilinear, half-pixel centres) is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) --
+    each tile cropped from the source map by one fused gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its
+    logits (drs_tile_place) or its per-g softmax (drs_tile_place_dihedral) summed into a zeroed hs x ws map; under data parallelism
+    that map is summed over the ranks (the same split of tile rows as one scale); then its class probabilities are resampled back onto
+    h x w and ADDED into acc (drs_resample_accumulate) on every rank, and the scale's buffers go.  Labels: drs_stitch_finalize(acc,
+    occur = len(scales)) on every rank.  Returns (labels, total tile count), or (acc, occur, total tile count) with return_sums.
+    One inference twin, sized once for max T_s, runs every scale's tiles."""
+    from . import _lib
+    h, w = pool.h[map_index], pool.w[map_index]
+    K = net.plan.K
+    plans = []
+    for s in scales:
+        hs, ws = P.scaled_size(h, s), P.scaled_size(w, s)
+        T = min(hs, ws, int(tile) if tile else DENSE_TILE)
+        if T < max(hs, ws) and T <= before + after:
+            raise ValueError("scale %g: the %d x %d map at this scale needs tiles of side %d, which cannot exceed the receptive-field "
+                             "margins %d + %d of %s" % (s, hs, ws, T, before, after, net.plan.net_type))
+        n_rows = len(P.dense_axis(hs, T, before, after)[0])
+        plans.append((hs, ws, T, n_rows, P.dense_tiles(hs, ws, T, before, after)))
+    twin = dense_twin(net, max(p[2] for p in plans), batch_size)
+    W, r = comm.world, comm.rank
+    st = twin._stream()
+    acc = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
+    n_tiles = 0
+    for hs, ws, T, n_rows, boxes in plans:
+        n_w = len(boxes) // n_rows
+        a = [q * n_rows // W for q in range(W + 1)]          # tile rows per rank, as with one scale
+        mine = np.arange(a[r] * n_w, a[r + 1] * n_w)
+        prob = torch.zeros(hs * ws * K, dtype=torch.float32, device=net.dev)
+        occur = torch.zeros(hs * ws, dtype=torch.int32, device=net.dev)
+        boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
+        for c0 in range(0, len(mine), twin.b_max):
+            sel = mine[c0:c0 + twin.b_max]
+            inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
+            for g in (0,) if G is None else G:        # ascending: the per-pixel order of the sum
+                P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, g)
+                _, logits = twin.forward(len(sel), T, want_logits=True)
+                if G is None:
+                    _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
+                              boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+                else:
+                    _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
+                              boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
+        if W > 1:
+            comm.all_reduce_sum(prob)
+            comm.all_reduce_sum(occur)
+        _lib.call("drs_resample_accumulate", prob.data_ptr(), occur.data_ptr(), hs, ws, K, 0 if G is None else 1, h, w, acc.data_ptr(),
+                  st)
+        del prob, occur, boxes_dev          # (stream-ordered: the next scale's buffers may reuse them)
+        n_tiles += len(boxes)
+    occur = torch.full((h * w,), len(scales), dtype=torch.int32, device=net.dev)
+    if return_sums:
+        return acc, occur, n_tiles
+    out = torch.empty(h * w, dtype=torch.uint8, device=net.dev)
+    _lib.call("drs_stitch_finalize", acc.data_ptr(), occur.data_ptr(), h, w, K, out.data_ptr(), st)
+    return out.view(h, w), n_tiles
+
+
 def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_type, num_scales):
     """The reference picks the best size, removes it from the candidates and repeats (isprs:1370-1420)."""
     values = np.asarray(values).copy()
@@ -591,16 +657,27 @@ def _check_dense_tta(dense_tile, dense_tta):
     P.tta_group(dense_tta)
 
 
+def _check_dense_scales(dense_tile, dense_scales):
+    if dense_scales is None:
+        return
+    if dense_tile is None:
+        raise ValueError("multi-scale test-time augmentation needs overlap-tile inference (dense_tile): the sliding windows take "
+                         "their scales from the patch size (crop_sizes)")
+    P.check_scales(dense_scales)
+
+
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None):
+                  dense_tta=None, dense_scales=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
-    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta)."""
+    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
+    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales)."""
     from . import _lib
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
+    _check_dense_scales(dense_tile, dense_scales)
     K = net.plan.K
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
@@ -612,7 +689,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta)
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
+                                         scales=dense_scales)
         elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
             pred = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm)
         else:
@@ -656,13 +734,15 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None, dense_tta=None):
+                        dense_tile=None, dense_tta=None, dense_scales=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
-    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta)."""
+    ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
+    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales)."""
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
+    _check_dense_scales(dense_tile, dense_scales)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
         crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
@@ -671,7 +751,8 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     maps = []
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta)
+            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
+                                         scales=dense_scales)
         else:
             pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
         maps.append(pred.cpu().numpy())

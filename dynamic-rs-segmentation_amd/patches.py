@@ -7,7 +7,8 @@ Host mirror of /root/reference/isprs_dilated_random.py: `select_batch` :46-58, t
 stays on the host (it is scalar work); every per-pixel operation -- crop,
 rotation, noise, flip, normalisation of bands 0..2, zero halo and band padding for conv1 -- happens
 in one HIP kernel (drs_crop_normalize) that writes the conv1 input slab directly (and, for the test-time
-augmentation of overlap-tile inference, the dihedral symmetries of whole tiles: drs_crop_dihedral).
+augmentation of overlap-tile inference, the dihedral symmetries of whole tiles: drs_crop_dihedral, and tiles of
+the bilinearly resampled image: drs_crop_resampled).
 
 RNG: like the reference, draws come from the global `random` / `numpy.random` streams in the
 reference's call order, so seeding both reproduces the reference's sequence.
@@ -176,6 +177,31 @@ def tta_group(tta):
         raise ValueError("test-time augmentation %r: codes must be distinct integers in 0..7" % (tta,))
     codes = [int(c) for c in tta]
     return tuple(sorted(codes))
+
+
+# ------------------------------------------------------------------- multi-scale test-time augmentation
+SCALE_MIN, SCALE_MAX = 0.25, 4.0
+
+
+def scaled_size(n, s):
+    """The side of an n-pixel axis resampled by the factor s: max(1, floor(n s + 0.5))."""
+    return max(1, int(math.floor(int(n) * float(s) + 0.5)))
+
+
+def check_scales(scales):
+    """The scale factors of multi-scale test-time augmentation as a tuple of floats, in the order given (the order of the per-pixel
+    sum).  A non-empty list / tuple of distinct finite numbers in [SCALE_MIN, SCALE_MAX]; anything else raises ValueError."""
+    if not isinstance(scales, (tuple, list)) or not scales:
+        raise ValueError("scales %r: expected a non-empty list of factors in [%g, %g]" % (scales, SCALE_MIN, SCALE_MAX))
+    if not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in scales):
+        raise ValueError("scales %r: the factors must be numbers" % (scales,))
+    out = tuple(float(v) for v in scales)
+    for v in out:
+        if not math.isfinite(v) or not SCALE_MIN <= v <= SCALE_MAX:
+            raise ValueError("scale %r: must be finite and in [%g, %g]" % (v, SCALE_MIN, SCALE_MAX))
+    if len(set(out)) != len(out):
+        raise ValueError("scales %r: a factor is given twice" % (scales,))
+    return out
 
 
 # ---------------------------------------------------------------------------------------- augmentation draws
@@ -365,6 +391,28 @@ def crop_dihedral_to_net(net, pool, instances, T, mean, std, g):
     _lib.call("drs_crop_dihedral", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(),
               pool.tile_w.data_ptr(), len(pool.h), pool.C, p_inst, int(g), C.cast(m3c, C.c_void_p), C.cast(s3c, C.c_void_p), B, T, P,
               ld, slab.data_ptr(), net._stream())
+
+
+def crop_resampled_to_net(net, pool, instances, T, hs, ws, mean, std, g):
+    """The multi-scale crop beside crop_dihedral_to_net (loops.predict_tile_dense with scales): fills net's conv1 slab with the T x T
+    tiles at `instances` rows (map, row, col) of the map bilinearly resampled to hs x ws (row / col on that grid), each transformed by
+    the dihedral code g and normalised as crop_to_net normalises (drs_crop_resampled; no resized image is made).  A tile that does not
+    lie inside the hs x ws grid is caught on the device and leaves a zero slab."""
+    import ctypes as C
+    B = len(instances)
+    net._check(B, T)
+    inst = np.ascontiguousarray(np.asarray(instances, dtype=np.int64)[:, :3].astype(np.int32))
+    stg = getattr(net, "_staging", None)
+    if stg is None:
+        stg = net._staging = _Staging(net.dev, net.b_max)
+    p_inst = stg.upload(inst, None)[0]
+    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
+    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
+    m3c, s3c = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)       # HOST pointers: copied into the kernel arguments
+    slab, P, ld = net.input_slab()
+    _lib.call("drs_crop_resampled", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(),
+              pool.tile_w.data_ptr(), len(pool.h), pool.C, p_inst, int(hs), int(ws), int(g), C.cast(m3c, C.c_void_p),
+              C.cast(s3c, C.c_void_p), B, T, P, ld, slab.data_ptr(), net._stream())
 
 
 def pack_feed(net, batch_x, batch_y, crop_size, mask=None, acc_mask=None):

@@ -277,6 +277,27 @@ int drs_crop_dihedral(const void* tiles, int tiles_are_f64, const long long* til
                       void* stream);
 int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
                             int g, void* stream);
+/* multi-scale test-time augmentation of overlap-tile inference (opt-in).  For a map X of h x w and a scale s the
+ * scaled side is hs = max(1, floor(h s + 0.5)) (ws alike).  D(n -> ns) is bilinear with half-pixel centres (torch interpolate,
+ * mode bilinear, align_corners=False, no antialias): per axis, output index d reads
+ *     src = max((d + 0.5) (n / ns) - 0.5, 0),  i0 = floor(src),  i1 = min(i0 + 1, n - 1),  l = src - i0
+ * and the value is (1-ly)((1-lx) v00 + lx v01) + ly((1-lx) v10 + lx v11).  At ns == n the weights are exactly (1, 0).
+ *
+ * drs_crop_resampled: conv1's input slab out [B][T+2P][T+2P][ld] of the T x T tiles inst [B][3] = (map, row, col) (device data) of
+ * Xs = D(X) -- row / col on the hs x ws grid, every map resampled to hs x ws -- each transformed by the dihedral code g as
+ * drs_crop_dihedral transforms it; D in fp64 on every channel, then normalised as drs_crop_normalize normalises (bands 0..2, one
+ * rounding to fp32; mean3 / std3 are HOST pointers).  One fused gather: no resized image is made.  Halo and channels C..ld-1 are
+ * zero; a tile outside [0, hs-T] x [0, ws-T], or a map index outside [0, n_maps), leaves a zero slab.  At hs == h and ws == w it
+ * is drs_crop_dihedral bit for bit (values other than -0.0).
+ * drs_resample_accumulate: acc[h][w][K] += U(hs x ws -> h x w) of the class-probability map of src [hs][ws][K]: the vector of a
+ * source pixel q is src[q] / occur[q] when src_is_prob (a sum of probabilities), else the max-subtracted fp32 softmax of
+ * src[q] / occur[q] as drs_tile_place_dihedral forms it (logits); occur 0 counts as 1.  Coordinates and weights in fp64, the four
+ * vectors mixed in fp32 in the order of D above.  K <= 8, h <= 65535.  At hs == h and ws == w it is acc += vector, bit for bit. */
+int drs_crop_resampled(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
+                       int C, const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
+                       float* out, void* stream);
+int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs, int ws, int K, int src_is_prob, int h, int w, float* acc,
+                            void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);

@@ -5,8 +5,9 @@ and the net's moving statistics are built exactly as bench.py's baseline_configs
 Dilated8Pooling, moving statistics from one train-mode pass over 256 spread windows).  Every shape is warmed up first; each mode then
 runs `reps` times, alternating, timed by a host clock around a device synchronize.  Prints one JSON line.
 tta=flip|d4 adds a third mode: overlap-tile inference with that dihedral test-time augmentation (predict_tile_dense(..., tta=...)),
-on its own symmetric-margin plan.
-    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3] [tta=flip|d4]
+on its own symmetric-margin plan.  scales=0.75,1,1.25 adds the multi-scale test-time augmentation mode (predict_tile_dense(...,
+scales=...); with tta= as well, both at once), every scale's tile shapes warmed up too.
+    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3] [tta=flip|d4] [scales=0.75,1,1.25]
 """
 import json
 import os
@@ -18,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from drs_amd.net import DilatedNet  # noqa: E402
-from drs_amd import loops, patches as P  # noqa: E402
+from drs_amd import _lib, loops, patches as P  # noqa: E402
 
 NET, CH, K, WD = "dilated_grsl_rate8", 5, 6, 0.005
 PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X fp32 MFMA rate (bench.py's figure)
@@ -29,7 +30,7 @@ def checksum(pred):
     return int(((pred.reshape(-1).long() + 1) * (idx % 65521 + 1)).sum().item() % (1 << 61))
 
 
-def main(mosaic=6000, tile=512, reps=3, tta=None):
+def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None):
     dev = "cuda:0"
     n, S, Bw = int(mosaic), 64, 256
     g0 = torch.Generator(device=dev).manual_seed(5)
@@ -81,6 +82,25 @@ def main(mosaic=6000, tile=512, reps=3, tta=None):
                                        mean, std, g)
                 twin.forward(b, T)
         modes = modes + ("dense_tta",)
+    if scales is not None:
+        scales = P.check_scales([float(v) for v in str(scales).split(",")])
+        Gs = (0,) if tta is None else P.tta_group(tta)
+        ms = (max(before, after),) * 2 if any(Gs) else (before, after)
+        plans = []
+        for s in scales:
+            ns = P.scaled_size(n, s)
+            Ts = min(ns, T)
+            plans.append((s, ns, Ts, P.dense_tiles(ns, ns, Ts, *ms)))
+            for b in sorted({B_t, len(plans[-1][3]) % B_t} - {0}):
+                for g in Gs:
+                    P.crop_resampled_to_net(twin, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), plans[-1][3][:b, :2]], axis=1),
+                                            Ts, ns, ns, mean, std, g)
+                    twin.forward(b, Ts)
+        one = torch.ones(K, dtype=torch.float32, device=dev)
+        occ1 = torch.ones(1, dtype=torch.int32, device=dev)
+        for is_prob in (0, 1):
+            _lib.call("drs_resample_accumulate", one.data_ptr(), occ1.data_ptr(), 1, 1, K, is_prob, 1, 1, one.data_ptr(), twin._stream())
+        modes = modes + ("dense_scales",)
     torch.cuda.synchronize()
 
     runs = {mode: [] for mode in modes}
@@ -93,8 +113,10 @@ def main(mosaic=6000, tile=512, reps=3, tta=None):
                 pred, _ = loops.predict_tile(net, pool, 0, S, Bw, mean, std)
             elif mode == "dense":
                 pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T)
-            else:
+            elif mode == "dense_tta":
                 pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T, tta=tta)
+            else:
+                pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T, tta=tta, scales=scales)
             torch.cuda.synchronize()
             runs[mode].append(time.perf_counter() - t0)
             maps[mode] = pred
@@ -102,6 +124,8 @@ def main(mosaic=6000, tile=512, reps=3, tta=None):
     pix = {"window": nh * nw * S * S, "dense": len(boxes) * T * T}
     if tta is not None:
         pix["dense_tta"] = len(G) * len(boxes_tta) * T * T
+    if scales is not None:
+        pix["dense_scales"] = len(Gs) * sum(len(bx) * Ts * Ts for _, _, Ts, bx in plans)
     out = dict(workload="BASELINE config 5: dilated_grsl_rate8 inference of a %dx%dx5 synthetic mosaic on ONE GPU; sliding windows "
                         "64x64 at stride 32 in batches of 256 (overlap-add, the reference's map) vs overlap-tile inference at T = %d "
                         "(exact whole-tile forward, %d tiles per forward)" % (n, n, T, B_t),
@@ -120,10 +144,18 @@ def main(mosaic=6000, tile=512, reps=3, tta=None):
                           cost_vs_dense=round(out["dense_tta"]["best_s"] / out["dense"]["best_s"], 3),
                           maps_agree_with_dense_frac=round(float((maps["dense_tta"] == maps["dense"]).float().mean().item()), 5),
                           map_checksum="sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense_tta"]))
+    if scales is not None:
+        tiles_one = len(P.dense_tiles(n, n, T, *ms))
+        out["scales"] = dict(factors=list(scales), tta=tta, sides=[ns for _, ns, _, _ in plans], tile_sides=[Ts for _, _, Ts, _ in plans],
+                             tiles=[len(bx) for _, _, _, bx in plans],
+                             predicted_cost_vs_one_scale=round(sum(len(bx) for _, _, _, bx in plans) / tiles_one, 3),
+                             cost_vs_dense=round(out["dense_scales"]["best_s"] / out["dense"]["best_s"], 3),
+                             maps_agree_with_dense_frac=round(float((maps["dense_scales"] == maps["dense"]).float().mean().item()), 5),
+                             map_checksum="sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense_scales"]))
     out["dense_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense"])
     out["window_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["window"])
     print(json.dumps(out))
 
 
 if __name__ == "__main__":
-    main(**{k: (v if k == "tta" else int(v)) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
+    main(**{k: (v if k in ("tta", "scales") else int(v)) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
