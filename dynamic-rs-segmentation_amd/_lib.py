@@ -46,6 +46,10 @@ SIGNATURES = {
     "drs_avg_pool_backward": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "drs_se_forward": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "drs_se_backward": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "drs_se_core_sums_scratch_doubles": (_i, [_i]),
+    "drs_se_core_sums": (_i, [_p, _i, _i, _p, _i, _p, _p, _p]),
+    "drs_se_gate": (_i, [_p, _d, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "drs_se_scale_const": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p]),
     "drs_classifier_rows": (_i, [_i, _i]),
     "drs_classifier_loss": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _p, _p, _p,
                                  _p, _p]),
@@ -76,6 +80,7 @@ SIGNATURES = {
     "drs_net_layer_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.c_char_p, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_info": (_i, [_p, C.c_char_p, _i, C.POINTER(_f), C.POINTER(_i), C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_receptive_field": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
+    "drs_net_receptive_field_gated": (_i, [_p, C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_se_info": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "drs_net_type_name": (_i, [_i, C.c_char_p, _i, C.POINTER(_i)]),
     "drs_net_num_variables": (_i, [_p]),
@@ -97,6 +102,8 @@ SIGNATURES = {
     "drs_train_step": (_i, [_p, _i, _i, _f, _i, _d, _p]),
     "drs_forward": (_i, [_p, _i, _i, _i, _i, _p]),
     "drs_apply_update": (_i, [_p, _f, _p]),
+    "drs_forward_staged": (_i, [_p, _i, _i, _i, _p, _i, _i, _p]),
+    "drs_net_se_gate_finish": (_i, [_p, _i, _d, _p]),
     "drs_net_set_two_streams": (_i, [_p, _i]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),

@@ -10,6 +10,8 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
   + optionally, anywhere, with --dense-tile only, `--dense-scales=0.75,1,1.25`: its multi-scale test-time augmentation (the sum of
     the class probabilities of the image resampled by each factor, resampled back; predict_tile_dense's scales), with or without
     --dense-tta
+  + optionally, anywhere, with --dense-tile only, `--dense-se=global` (nets with squeeze-and-excitation blocks, which --dense-tile
+    refuses without it): the blocks are gated by the mean over the whole image, computed exactly in tiles (predict_tile_dense's se)
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -107,6 +109,27 @@ def parse_dense_scales(argv):
     return (list(argv) if scales is None else rest), scales
 
 
+DENSE_SE_FLAG = "--dense-se"
+
+
+def parse_dense_se(argv):
+    """isprs flavour: the optional `--dense-se=global` (anywhere in argv; with --dense-tile only, which main checks).  Returns (argv
+    without the flag, "global"), or (argv unchanged, None) without it.  Any other value, a bare flag, or the flag given twice, raises
+    ValueError."""
+    rest, se = [], None
+    for a in argv:
+        if a != DENSE_SE_FLAG and not a.startswith(DENSE_SE_FLAG + "="):
+            rest.append(a)
+            continue
+        if se is not None:
+            raise ValueError(DENSE_SE_FLAG + " given more than once")
+        v = a[len(DENSE_SE_FLAG) + 1:]
+        if v not in loops.DENSE_SE_MODES:
+            raise ValueError("%s: expected %s=%s" % (a, DENSE_SE_FLAG, "|".join(loops.DENSE_SE_MODES)))
+        se = v
+    return (list(argv) if se is None else rest), se
+
+
 def print_params(list_params, argv):
     print("+" * 97)
     for i in range(1, len(argv)):
@@ -164,12 +187,15 @@ def main(argv=None, device=None, comm=None):
         argv, dense_tile = parse_dense_tile(argv)
         argv, dense_tta = parse_dense_tta(argv)
         argv, dense_scales = parse_dense_scales(argv)
+        argv, dense_se = parse_dense_se(argv)
     except ValueError as e:
         sys.exit(str(e))
     if dense_tta is not None and dense_tile is None:
         sys.exit(DENSE_TTA_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if dense_scales is not None and dense_tile is None:
         sys.exit(DENSE_SCALES_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
+    if dense_se is not None and dense_tile is None:
+        sys.exit(DENSE_SE_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if len(argv) < len(ISPRS_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
@@ -236,11 +262,11 @@ def main(argv=None, device=None, comm=None):
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales)
+                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales)
+                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -137,6 +137,7 @@ struct LayerPtrs {
   const float* w;                                                 // the filter the forward pass multiplies by (conv1: the padded copy)
   float* act_in; float* act_out; float* gact_in; float* gact_out; // slabs this block reads / writes and their gradients
   float *se_act, *se_s, *se_e1, *se_e2;                           // squeeze-and-excitation state of the block (or null)
+  double* se_sum; float* se_gate;                                 // ... and its whole-image sums / gate (drs_forward_staged)
 };
 struct Ptrs {
   bool ok = false;
@@ -406,6 +407,13 @@ void list_buffers(drs_net* n) {
     n->add_buf("se_e2" + id, B * s.C, F32);
   }
   if (!n->se.empty()) n->add_buf("se_scratch", B * (3 * (size_t)cmax + cmax / 4), F32);
+  // overlap-tile inference with whole-image gates (drs_forward_staged): per SE block the fp64 per-channel sums of a sweep (the host
+  // zeroes them when a sweep begins and all-reduces them under data parallelism) and the gate drs_net_se_gate_finish makes of them
+  for (size_t j = 0; j < n->se.size(); ++j) {
+    n->add_buf("se_sum" + std::to_string(j), (size_t)n->se[j].C, F64);
+    n->add_buf("se_gate" + std::to_string(j), (size_t)n->se[j].C, F32);
+  }
+  if (!n->se.empty()) n->add_buf("se_sum_scratch", (size_t)drs_se_core_sums_scratch_doubles(cmax), F64);
   const size_t crow = drs_classifier_rows(n->b_max, n->s_max);
   n->add_buf("dw_partial", crow * n->c_last * n->K, F32);
   n->add_buf("db_partial", crow * n->K, F32);
@@ -576,21 +584,26 @@ bool resolve(drs_net* n) {
     q.act_in = n->p<float>("act:" + n->slabs[L.src].name); q.act_out = n->p<float>("act:" + n->slabs[L.dst].name);
     q.gact_in = L.src != 0 ? n->p<float>("gact:" + n->slabs[L.src].name) : nullptr;
     q.gact_out = n->p<float>("gact:" + n->slabs[L.dst].name);
-    q.se_act = q.se_s = q.se_e1 = q.se_e2 = nullptr;
+    q.se_act = q.se_s = q.se_e1 = q.se_e2 = nullptr; q.se_sum = nullptr; q.se_gate = nullptr;
 #ifdef DRS_DEV
     if (n->layer_slabs) { q.gzL = n->p<float>("gzL" + id); q.slabL = n->p<float>("slabL" + id); }
 #endif
     if (L.se >= 0) {
       const std::string sid = std::to_string(L.se);
       q.se_act = n->p<float>("se_act" + sid); q.se_s = n->p<float>("se_s" + sid); q.se_e1 = n->p<float>("se_e1" + sid); q.se_e2 = n->p<float>("se_e2" + sid);
+      q.se_sum = n->p<double>("se_sum" + sid); q.se_gate = n->p<float>("se_gate" + sid);
     }
   }
   P.ok = true;
   return true;
 }
 
+// drs_forward_staged: SE blocks [0, stage) scale by their stored whole-image gate ("se_gate<j>") instead of the patch mean; SE block
+// `stage` (if there is one) adds the per-channel sums of its activated input over the tiles' cores into "se_sum<stage>" and ends the pass
+struct Staged { int stage; const int* boxes; int n_boxes; };
+
 // conv -> (+bias) -> batch norm -> activation -> pool / SE, for every block (net.py _forward_layers, exact-fp32 arithmetic)
-int forward_layers(drs_net* n, int B, int S, bool training, double count, hipStream_t st) {
+int forward_layers(drs_net* n, int B, int S, bool training, double count, hipStream_t st, const Staged* sg = nullptr) {
   const long long M = (long long)B * S * S;
   const Ptrs& P = n->ptrs;
   float* params = P.params;
@@ -633,8 +646,13 @@ int forward_layers(drs_net* n, int B, int S, bool training, double count, hipStr
       float* act = q.se_act;
       { Timed t(n, st, K_BN_FWD, M * L.cout * 8.0);
         DRS_TRY(drs_bn_act_pool_forward(z, B, S, L.cout, mr, n->alpha, 0, act, 0, L.cout, 0, nullptr, st)); }
-      Timed t(n, st, K_SE_FWD, M * L.cout * 12.0);
-      DRS_TRY(drs_se_forward(act, B, S, L.cout, s.R, params + s.w1, params + s.b1, params + s.w2, params + s.b2, q.se_s, q.se_e1, q.se_e2, outp,
+      if (sg && L.se == sg->stage) {
+        Timed t(n, st, K_SE_FWD, M * L.cout * 4.0);
+        return drs_se_core_sums(act, L.cout, S, sg->boxes, sg->n_boxes, q.se_sum, n->p<double>("se_sum_scratch"), st);
+      }
+      Timed t(n, st, K_SE_FWD, M * L.cout * (sg ? 8.0 : 12.0));
+      if (sg) DRS_TRY(drs_se_scale_const(act, B, S, L.cout, q.se_gate, outp, out.P, out.C, L.dst_coff, st));
+      else DRS_TRY(drs_se_forward(act, B, S, L.cout, s.R, params + s.w1, params + s.b1, params + s.w2, params + s.b2, q.se_s, q.se_e1, q.se_e2, outp,
                              out.P, out.C, L.dst_coff, st));
       n->halo_ok[L.dst] = -1;
     } else if (L.pool == 2) {   // activation into a plain [M][C] buffer, then the k x k average into the next layer's slab
@@ -829,8 +847,7 @@ int drs_net_info(const drs_net_t* n, char* net_type, int name_cap, float* alpha,
 // the 1 x 1 classifier adds nothing.  A chain and the dense concat (isprs:921-948: its longest path runs through every block) sum their
 // blocks; a squeeze stage (isprs:726-742) adds its 1 x 1 squeeze block and the larger of its two expand blocks.  Squeeze-and-excitation
 // blocks (isprs:682-697) scale by a mean over the whole patch: no finite field, DRS_ERR_ARG.
-int drs_net_receptive_field(const drs_net_t* n, int* before, int* after) {
-  if (!n || !before || !after || !n->se.empty()) return DRS_ERR_ARG;
+static int net_field(const drs_net_t* n, int* before, int* after) {
   auto field = [](const Layer& L, int& b, int& a) {
     b = L.pad_b; a = L.pad_a;
     if (L.pool == 1) { b += 1; a += 1; }
@@ -850,6 +867,19 @@ int drs_net_receptive_field(const drs_net_t* n, int* before, int* after) {
   }
   *before = sb; *after = sa;
   return DRS_OK;
+}
+
+int drs_net_receptive_field(const drs_net_t* n, int* before, int* after) {
+  if (!n || !before || !after || !n->se.empty()) return DRS_ERR_ARG;
+  return net_field(n, before, after);
+}
+
+// the same count with every squeeze-and-excitation layer taken as a per-channel constant (a 1 x 1 step): the field of the chains
+// between the gates, which is what overlap-tile inference with whole-image gates needs (drs_forward_staged).  Equal to
+// drs_net_receptive_field for a net without such layers.
+int drs_net_receptive_field_gated(const drs_net_t* n, int* before, int* after) {
+  if (!n || !before || !after) return DRS_ERR_ARG;
+  return net_field(n, before, after);
 }
 
 // squeeze-and-excitation block `index` (isprs:682-697, 1042-1050): its scope ("se1": variables <scope>_fc1/weights, ...), the block
@@ -1061,6 +1091,35 @@ static int forward_impl(drs_net_t* n, int B, int S, int flags, int ignore_label,
   if (flags & DRS_WITH_LABELS)
     DRS_TRY(drs_confusion(P.labels, P.pred, (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (size_t)M, n->K, ignore_label, P.conf, st));
   return DRS_OK;
+}
+
+// overlap-tile inference of a net with squeeze-and-excitation blocks, gated by whole-IMAGE means.  stage < n_se: the
+// eval-mode pass over the B tiles in "act:x0" up to the block SE `stage` follows, SE blocks [0, stage) scaling by their stored gates;
+// the per-channel sums of that block's activated output over the tiles' core boxes are ADDED into "se_sum<stage>".  stage == n_se:
+// the whole pass with every stored gate, to logits / pred as drs_forward writes them.
+static int forward_staged_impl(drs_net_t* n, int B, int S, int stage, const int* boxes, int n_boxes, int flags, void* stream) {
+  if (!n || !check_bs(n, B, S) || !resolve(n) || n->se.empty() || stage < 0 || stage > (int)n->se.size()) return DRS_ERR_ARG;
+  const bool last = stage == (int)n->se.size();
+  if (!last && (!boxes || n_boxes != B)) return DRS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const long long M = (long long)B * S * S;
+  const Ptrs& P = n->ptrs;
+  const Staged sg{stage, boxes, n_boxes};
+  DRS_TRY(forward_layers(n, B, S, false, (double)M, st, &sg));
+  if (!last) return DRS_OK;
+  const Slab& f = n->slabs[n->feat];
+  float* params = P.params;
+  return drs_classifier_loss(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b, nullptr,
+                             nullptr, nullptr, 0.f, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr, P.pred,
+                             nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, st);
+}
+
+int drs_net_se_gate_finish(drs_net_t* n, int index, double count, void* stream) {
+  if (!n || !resolve(n) || index < 0 || index >= (int)n->se.size() || !(count > 0.0)) return DRS_ERR_ARG;
+  const SeBlock& s = n->se[index];
+  const LayerPtrs& q = n->ptrs.L[s.layer];
+  float* params = n->ptrs.params;
+  return drs_se_gate(q.se_sum, count, s.C, s.R, params + s.w1, params + s.b1, params + s.w2, params + s.b2, q.se_s, q.se_e1, q.se_gate, stream);
 }
 
 float drs_net_learning_rate(const drs_net_t* n, float lr0) {
@@ -1425,6 +1484,10 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
 // the entry points whose host side allocates (strings, vectors): an allocation failure is a status, nothing throws across the ABI
 int drs_forward(drs_net_t* n, int B, int S, int flags, int ignore_label, void* stream) {
   try { return forward_impl(n, B, S, flags, ignore_label, stream); } catch (...) { return DRS_ERR_HIP; }
+}
+
+int drs_forward_staged(drs_net_t* n, int B, int S, int stage, const int* boxes, int n_boxes, int flags, void* stream) {
+  try { return forward_staged_impl(n, B, S, stage, boxes, n_boxes, flags, stream); } catch (...) { return DRS_ERR_HIP; }
 }
 
 int drs_train_step(drs_net_t* n, int B, int S, float lr0, int flags, double global_pixels, void* stream) {

@@ -671,8 +671,9 @@ __global__ void se_excite_kernel(const float* __restrict__ s, const float* __res
 }
 
 // y = x * e2 into the interior of a view (FWD), or gx = gy * e2 + gs (BWD, plain [M][C] output)
+// ld_e: floats between two images' rows of e2 (C: one gate vector per image; 0: one for the whole batch, drs_se_scale_const)
 template <bool BWD>
-__global__ void se_scale_kernel(const float* __restrict__ x, int ld_x, int coff_x, const float* __restrict__ e2,
+__global__ void se_scale_kernel(const float* __restrict__ x, int ld_x, int coff_x, const float* __restrict__ e2, int ld_e,
                                 const float* __restrict__ gs, int B, int S, int C, ActView out) {
   const int CQ = C >> 2;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -681,7 +682,7 @@ __global__ void se_scale_kernel(const float* __restrict__ x, int ld_x, int coff_
   const int b = blockIdx.y / S, y = blockIdx.y - b * S;
   const size_t p = ((size_t)b * S + y) * S + xx;
   const f32x4 v = *reinterpret_cast<const f32x4*>(x + p * ld_x + coff_x + cq * 4);
-  const f32x4 sc = *reinterpret_cast<const f32x4*>(e2 + (size_t)b * C + cq * 4);
+  const f32x4 sc = *reinterpret_cast<const f32x4*>(e2 + (size_t)b * ld_e + cq * 4);
   f32x4 o;
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = v[j] * sc[j];
@@ -692,6 +693,59 @@ __global__ void se_scale_kernel(const float* __restrict__ x, int ld_x, int coff_
   }
   const int Sp = S + 2 * out.P;
   *reinterpret_cast<f32x4*>(out.base + ((size_t)(b * Sp + y + out.P) * Sp + xx + out.P) * out.ld + out.coff + cq * 4) = o;
+}
+
+// ---- squeeze-and-excitation gates of a whole image, computed in tiles (overlap-tile inference)
+// Per-channel sums of the activated block output over the CORE boxes of n tiles: act [n][T][T][C], boxes [n][6] as tile_place_kernel
+// reads them (y0, x0, cy0, cy1, cx0, cx1; device data, checked here: a core that does not lie inside its tile adds nothing).
+// Level 1: workgroup (channel group of 64, band) walks the tile rows band, band + SE_SUM_BANDS, ... and, inside a row, only the core
+// columns; 64 lanes across channels (one 256-byte run per pixel), 4 pixel lanes, fp32 loads accumulated in fp64, the 4 lanes added in
+// order -> scratch[band][C].  Level 2: one thread per channel adds the bands in order and ADDS the total into sums[c] (plain
+// read-modify-write: launches on one stream accumulate in stream order).  No atomics: the same launches give the same bits.
+constexpr int SE_SUM_BANDS = 512;
+
+__global__ __launch_bounds__(256) void se_core_sums_l1_kernel(const float* __restrict__ a, int C, int T, const int* __restrict__ boxes, int n,
+                                                              double* __restrict__ scratch) {
+  __shared__ double sh[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx;
+  double acc = 0.0;
+  if (c < C) {
+    const int nrows = n * T;
+    for (int r = blockIdx.y; r < nrows; r += SE_SUM_BANDS) {
+      const int i = r / T, yy = r - i * T;
+      const int* b = boxes + 6 * (size_t)i;
+      const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
+      if (cy0 < y0 || cy1 > y0 + T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + T || cx0 > cx1) continue;
+      const int y = y0 + yy;
+      if (y < cy0 || y >= cy1) continue;
+      const float* row = a + ((size_t)i * T + yy) * T * C + c;
+      const int xe = cx1 - x0;            // tile-local core columns [cx0 - x0, xe), inside [0, T) by the check above
+      int x = cx0 - x0 + ty;
+      for (; x + 12 < xe; x += 16) {      // four independent loads in flight per lane
+        const float v0 = row[(size_t)x * C], v1 = row[(size_t)(x + 4) * C], v2 = row[(size_t)(x + 8) * C], v3 = row[(size_t)(x + 12) * C];
+        acc += (double)v0; acc += (double)v1; acc += (double)v2; acc += (double)v3;
+      }
+      for (; x < xe; x += 4) acc += (double)row[(size_t)x * C];
+    }
+  }
+  sh[ty][tx] = acc;
+  __syncthreads();
+  if (ty == 0 && c < C) scratch[(size_t)blockIdx.y * C + c] = ((sh[0][tx] + sh[1][tx]) + sh[2][tx]) + sh[3][tx];
+}
+
+__global__ void se_core_sums_l2_kernel(const double* __restrict__ scratch, int C, int nbands, double* __restrict__ sums) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double s = 0.0;
+  for (int b = 0; b < nbands; ++b) s += scratch[(size_t)b * C + c];
+  sums[c] += s;
+}
+
+// s[c] = (float)(sums[c] / count): the whole-image mean, divided in fp64 and rounded once (the excite arithmetic then runs on it)
+__global__ void se_mean_kernel(const double* __restrict__ sums, double count, int C, float* __restrict__ s) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) s[c] = (float)(sums[c] / count);
 }
 
 // per image: back through sigmoid, FC2, ReLU, FC1; gs already carries the 1/(S*S) of the spatial mean
@@ -1845,7 +1899,7 @@ int drs_se_forward(const float* act, int B, int S, int C, int R, const float* w1
     const int Sp = S + 2 * P_out;
     DRS_LAUNCH(zero_halo_kernel, dim3((Sp * (C / 4) + 255) / 256, B * Sp), dim3(256), 0, st, v, B, C);
   }
-  DRS_LAUNCH(se_scale_kernel<false>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, st, act, C, 0, e2, nullptr, B, S, C, v);
+  DRS_LAUNCH(se_scale_kernel<false>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, st, act, C, 0, e2, C, nullptr, B, S, C, v);
   return DRS_LAUNCH_CHECK();
 }
 
@@ -1865,8 +1919,44 @@ int drs_se_backward(const float* gy, int ld_g, int coff_g, const float* act, con
              gpre1, gs);
   DRS_LAUNCH(se_fc_wgrad_kernel, dim3(((R + 1) * C + 255) / 256), dim3(256), 0, st, e1, gpre2, B, R, C, dw2, db2);
   DRS_LAUNCH(se_fc_wgrad_kernel, dim3(((C + 1) * R + 255) / 256), dim3(256), 0, st, s, gpre1, B, C, R, dw1, db1);
-  DRS_LAUNCH(se_scale_kernel<true>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, st, gy, ld_g, coff_g, e2, gs, B, S, C,
+  DRS_LAUNCH(se_scale_kernel<true>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, st, gy, ld_g, coff_g, e2, C, gs, B, S, C,
              mkview(gact, S, 0, C, 0));
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_se_core_sums_scratch_doubles(int C) { return C > 0 ? SE_SUM_BANDS * C : 0; }
+
+// act [n*T*T][C], boxes [n][6] (device) -> sums[C] += per-channel sum over every tile's core; scratch: drs_se_core_sums_scratch_doubles(C)
+int drs_se_core_sums(const float* act, int C, int T, const int* boxes, int n, double* sums, double* scratch, void* stream) {
+  if (!act || !boxes || !sums || !scratch || C < 1 || T < 1 || T > 65535 || n < 1 || n > 65535 || (long long)n * T * T >= (1ll << 31)) return DRS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int nbands = n * T < SE_SUM_BANDS ? n * T : SE_SUM_BANDS;
+  DRS_LAUNCH(se_core_sums_l1_kernel, dim3((C + 63) / 64, nbands), dim3(256), 0, st, act, C, T, boxes, n, scratch);
+  DRS_LAUNCH(se_core_sums_l2_kernel, dim3((C + 63) / 64), dim3(64), 0, st, scratch, C, nbands, sums);
+  return DRS_LAUNCH_CHECK();
+}
+
+// sums[C] over `count` pixels -> s = mean (one rounding to fp32), e1 = relu(s w1 + b1) [R], e2 = sigmoid(e1 w2 + b2) [C]: the excite
+// arithmetic of drs_se_forward for one "image"
+int drs_se_gate(const double* sums, double count, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
+                float* s, float* e1, float* e2, void* stream) {
+  if (!sums || !w1 || !b1 || !w2 || !b2 || !s || !e1 || !e2 || C < 1 || R < 1 || !(count > 0.0)) return DRS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  DRS_LAUNCH(se_mean_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, count, C, s);
+  DRS_LAUNCH(se_excite_kernel, dim3(1), dim3(256), (C + R) * sizeof(float), st, s, w1, b1, w2, b2, C, R, e1, e2);
+  return DRS_LAUNCH_CHECK();
+}
+
+// out view = act * e2[c] with ONE gate vector for the whole batch (halo zeroed): drs_se_forward's last step with a given gate
+int drs_se_scale_const(const float* act, int B, int S, int C, const float* e2, float* out, int P_out, int ld_out, int coff_out, void* stream) {
+  if (!act || !e2 || !out || B < 1 || S < 1 || C < 4 || C % 4 || (long long)B * (S + 2 * P_out) > 65535) return DRS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  ActView v = mkview(out, S, P_out, ld_out, coff_out);
+  if (P_out > 0) {
+    const int Sp = S + 2 * P_out;
+    DRS_LAUNCH(zero_halo_kernel, dim3((Sp * (C / 4) + 255) / 256, B * Sp), dim3(256), 0, st, v, B, C);
+  }
+  DRS_LAUNCH(se_scale_kernel<false>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, st, act, C, 0, e2, 0, nullptr, B, S, C, v);
   return DRS_LAUNCH_CHECK();
 }
 

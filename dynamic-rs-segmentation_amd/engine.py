@@ -110,6 +110,9 @@ class EngineNet(DilatedNet):
             setattr(self, n, b[n])
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
+        # whole-image gates of overlap-tile inference (forward_staged): per SE block the fp64 sums of a sweep and the gate made of them
+        self.se_sum = [b["se_sum%d" % j] for j in range(len(p.se))]
+        self.se_gate = [b["se_gate%d" % j] for j in range(len(p.se))]
 
     def workspace_bytes(self):
         return sum(t.numel() * t.element_size() for t in self._bufs.values())
@@ -319,6 +322,22 @@ class EngineNet(DilatedNet):
         _lib.call("drs_forward", self.h, B, S, flags, int(ignore_label), self._stream())
         M, K = B * S * S, self.plan.K
         return self.pred[:M].view(B, S, S), (self.logits[:M * K].view(B, S, S, K) if want_logits else None)
+
+    def forward_staged(self, B, S, stage, boxes=None, want_logits=True):
+        """One sweep's pass over the B tiles in the input slab (overlap-tile inference with whole-image SE gates, DESIGN.md 8a.3;
+        drs_forward_staged).  stage < number of SE blocks: up to the block SE `stage` follows, with the gates before it, its
+        activated output summed over the tiles' cores (boxes: device pointer to their [B][6] int32 rows) into se_sum[stage];
+        returns None.  stage == number of SE blocks: the whole pass with every gate; returns (pred, logits) as forward does."""
+        self._check(B, S)
+        _lib.call("drs_forward_staged", self.h, B, S, int(stage), boxes, B, _lib.WANT_LOGITS if want_logits else 0, self._stream())
+        if stage < len(self.se_sum):
+            return None
+        M, K = B * S * S, self.plan.K
+        return self.pred[:M].view(B, S, S), (self.logits[:M * K].view(B, S, S, K) if want_logits else None)
+
+    def se_gate_finish(self, j, count):
+        """se_sum[j] (summed over the ranks by the caller) over `count` pixels -> se_gate[j] (drs_net_se_gate_finish)"""
+        _lib.call("drs_net_se_gate_finish", self.h, int(j), float(count), self._stream())
 
     def train_step(self, B, S, lr0, use_loss_mask=False, use_acc_mask=True, global_pixels=None, apply_update=True, want_logits=False):
         self._check(B, S)

@@ -498,8 +498,30 @@ def dense_twin(net, T, batch_size):
     return twin
 
 
+DENSE_SE_MODES = ("global",)
+
+
+def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g=0):
+    """The gate sweeps of predict_tile_dense(se="global") for the image transformed by the dihedral code g: for SE
+    block j = 0, 1, ... every tile of this rank (`mine`, indices into the plan `boxes`) is cropped transformed by g (crop(inst)) and
+    forwarded up to the block SE j follows with the gates before it (forward_staged), its activated output summed per channel over the
+    tile's core -- as it lies in the transformed tile, patches.dihedral_core_boxes -- into the twin's fp64 se_sum[j], which is zeroed
+    on the stream when the sweep begins and summed over the ranks when it ends; se_gate[j] is made of the mean over `count` pixels."""
+    local = torch.from_numpy(P.dihedral_core_boxes(boxes, T, g).astype(np.int32)).to(twin.dev)
+    for j in range(len(twin.plan.se)):
+        twin.se_sum[j].zero_()
+        for c0 in range(0, len(mine), twin.b_max):
+            sel = mine[c0:c0 + twin.b_max]
+            crop(np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1))
+            twin.forward_staged(len(sel), T, j, local.data_ptr() + int(sel[0]) * 6 * 4)
+        if comm.world > 1:
+            comm.all_reduce_sum(twin.se_sum[j])
+        twin.se_gate_finish(j, count)
+    twin._keep_boxes = local             # alive until the stream has consumed it
+
+
 def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None,
-                       scales=None):
+                       scales=None, se=None):
     """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
     size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
     pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
@@ -515,19 +537,33 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     grid, occur = |G|; labels the arg-max of that mean.  A flip swaps `before` and `after` on its axis and a transpose swaps the axes,
     so with any g != 0 the plan keeps the symmetric margin max(before, after) on both sides.
     scales (a list of distinct factors in [0.25, 4]; patches.check_scales): multi-scale test-time augmentation, with or
-    without tta -- see _predict_tile_dense_scales."""
+    without tta -- see _predict_tile_dense_scales.
+    se ("global"; nets with squeeze-and-excitation blocks only, which raise without it): every SE block scales by the
+    sigmoid gate of the mean over ALL h x w pixels of the image -- the function the net computes when the whole image is one patch --
+    instead of a patch's own mean (what the window path does, and what training saw: a different function, hence opt-in).  With n
+    SE blocks the plan is swept n + 1 times: sweep j forwards every tile up to the block SE j follows with the gates before it and
+    sums its activated output over the cores in fp64 (_se_global_gates); the last sweep is the full forward with every gate.  The
+    margin is the field with the SE layers as constants (Plan.gated_receptive_field).  The net is not equivariant (asymmetric SAME
+    pads, unsymmetric filters), so the activation means of a flipped or rotated image are not those of the image: with tta every
+    code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale."""
     from . import _lib
     comm = comm or NoComm()
-    if net.plan.receptive_field is None:
+    if se is not None and se not in DENSE_SE_MODES:
+        raise ValueError("se must be None or one of %s, not %r" % (list(DENSE_SE_MODES), se))
+    if se is not None and not net.plan.se:
+        raise ValueError("se=%r asks for whole-image squeeze-and-excitation gates, and %s has no squeeze-and-excitation blocks"
+                         % (se, net.plan.net_type))
+    if se is None and net.plan.receptive_field is None:
         raise ValueError("%s has squeeze-and-excitation blocks (a mean over the whole patch): its output has no finite receptive field, "
-                         "so there is no exact whole-tile inference; use predict_tile" % net.plan.net_type)
-    before, after = net.plan.receptive_field
+                         "so there is no single-pass exact whole-tile inference; use predict_tile, or se=\"global\" for gates from the "
+                         "whole image's mean" % net.plan.net_type)
+    before, after = net.plan.receptive_field if se is None else net.plan.gated_receptive_field
     G = None if tta is None else P.tta_group(tta)
     if G is not None and any(G):
         before = after = max(before, after)
     if scales is not None:
         return _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G,
-                                          P.check_scales(scales), before, after)
+                                          P.check_scales(scales), before, after, se)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     T = int(tile) if tile else min(h, w, DENSE_TILE)
@@ -542,20 +578,31 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
     st = twin._stream()
     boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
-    for c0 in range(0, len(mine), twin.b_max):
-        sel = mine[c0:c0 + twin.b_max]
-        inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
-        if G is None:
-            P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
-            _, logits = twin.forward(len(sel), T, want_logits=True)
-            _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
-                      boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
-            continue
-        for g in G:         # ascending: the per-pixel order of the sum
-            P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, g)
-            _, logits = twin.forward(len(sel), T, want_logits=True)
-            _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
-                      boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
+    forward = twin.forward
+    if se is not None:
+        forward = lambda nb, T_, want_logits: twin.forward_staged(nb, T_, len(twin.plan.se), want_logits=want_logits)   # noqa: E731
+    # one pass over the tiles runs every code of its group per batch; with se every code is a pass of its own, after its gate sweeps
+    for Gp in ([G] if se is None or G is None else [(g,) for g in G]):
+        if se is not None and Gp is None:
+            _se_global_gates(twin, lambda inst: P.crop_to_net(twin, pool, inst, T, mean_full, std_full), T, boxes, mine, map_index,
+                             h * w, comm)
+        elif se is not None:
+            _se_global_gates(twin, lambda inst: P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, Gp[0]), T, boxes, mine,
+                             map_index, h * w, comm, Gp[0])
+        for c0 in range(0, len(mine), twin.b_max):
+            sel = mine[c0:c0 + twin.b_max]
+            inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
+            if Gp is None:
+                P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
+                _, logits = forward(len(sel), T, want_logits=True)
+                _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
+                          boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+                continue
+            for g in Gp:        # ascending: the per-pixel order of the sum
+                P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, g)
+                _, logits = forward(len(sel), T, want_logits=True)
+                _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
+                          boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
     if return_sums:
         if W > 1:
             comm.all_reduce_sum(prob)
@@ -572,7 +619,8 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     return out.view(h, w), len(boxes)
 
 
-def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after):
+def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after,
+                               se=None):
     """predict_tile_dense with scales.  For each scale s, in the order given: the map resampled to hs x ws
     (patches.scaled_size; bilinear, half-pixel centres) is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) --
     each tile cropped from the source map by one fused gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its
@@ -580,7 +628,9 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
     that map is summed over the ranks (the same split of tile rows as one scale); then its class probabilities are resampled back onto
     h x w and ADDED into acc (drs_resample_accumulate) on every rank, and the scale's buffers go.  Labels: drs_stitch_finalize(acc,
     occur = len(scales)) on every rank.  Returns (labels, total tile count), or (acc, occur, total tile count) with return_sums.
-    One inference twin, sized once for max T_s, runs every scale's tiles."""
+    One inference twin, sized once for max T_s, runs every scale's tiles.  With se (predict_tile_dense's) every scale is
+    an image of its own, and so is every code of tta: gates from sweeps over the scale's hs x ws grid (tiles transformed by the code),
+    before that code's full forwards."""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
@@ -605,18 +655,27 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
         prob = torch.zeros(hs * ws * K, dtype=torch.float32, device=net.dev)
         occur = torch.zeros(hs * ws, dtype=torch.int32, device=net.dev)
         boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
-        for c0 in range(0, len(mine), twin.b_max):
-            sel = mine[c0:c0 + twin.b_max]
-            inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
-            for g in (0,) if G is None else G:        # ascending: the per-pixel order of the sum
-                P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, g)
-                _, logits = twin.forward(len(sel), T, want_logits=True)
-                if G is None:
-                    _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
-                              boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
-                else:
-                    _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
-                              boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
+        forward = twin.forward
+        if se is not None:
+            forward = lambda nb, T_, want_logits: twin.forward_staged(nb, T_, len(twin.plan.se), want_logits=want_logits)   # noqa: E731
+        codes = (0,) if G is None else G
+        # one pass runs every code per batch of tiles; with se every code is a pass of its own, after its gate sweeps
+        for Gp in ([codes] if se is None else [(g,) for g in codes]):
+            if se is not None:
+                _se_global_gates(twin, lambda inst: P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, Gp[0]), T,
+                                 boxes, mine, map_index, hs * ws, comm, Gp[0])
+            for c0 in range(0, len(mine), twin.b_max):
+                sel = mine[c0:c0 + twin.b_max]
+                inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
+                for g in Gp:        # ascending: the per-pixel order of the sum
+                    P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, g)
+                    _, logits = forward(len(sel), T, want_logits=True)
+                    if G is None:
+                        _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
+                                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
+                    else:
+                        _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
+                                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
         if W > 1:
             comm.all_reduce_sum(prob)
             comm.all_reduce_sum(occur)
@@ -666,18 +725,30 @@ def _check_dense_scales(dense_tile, dense_scales):
     P.check_scales(dense_scales)
 
 
+def _check_dense_se(dense_tile, dense_se):
+    if dense_se is None:
+        return
+    if dense_tile is None:
+        raise ValueError("whole-image squeeze-and-excitation gates need overlap-tile inference (dense_tile): a sliding window is "
+                         "gated by its own mean")
+    if dense_se not in DENSE_SE_MODES:
+        raise ValueError("dense_se must be one of %s, not %r" % (list(DENSE_SE_MODES), dense_se))
+
+
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None, dense_scales=None):
+                  dense_tta=None, dense_scales=None, dense_se=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
     ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
-    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales)."""
+    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales).
+    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se)."""
     from . import _lib
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
+    _check_dense_se(dense_tile, dense_se)
     K = net.plan.K
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
@@ -690,7 +761,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     for k in range(len(testing_data)):
         if dense_tile is not None:
             pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                         scales=dense_scales)
+                                         scales=dense_scales, se=dense_se)
         elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
             pred = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm)
         else:
@@ -734,15 +805,17 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None, dense_tta=None, dense_scales=None):
+                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
     ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
-    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales)."""
+    dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales).
+    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se)."""
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
+    _check_dense_se(dense_tile, dense_se)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
         crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
@@ -752,7 +825,7 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     for k in range(len(testing_data)):
         if dense_tile is not None:
             pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                         scales=dense_scales)
+                                         scales=dense_scales, se=dense_se)
         else:
             pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
         maps.append(pred.cpu().numpy())

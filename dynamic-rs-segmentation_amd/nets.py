@@ -139,6 +139,10 @@ class Plan(object):
         if rc != 0 and not self.se:
             raise _lib.DrsError("drs_net_receptive_field -> %d for %s" % (rc, self.net_type))
         self.receptive_field = (b.value, a.value) if rc == 0 else None
+        # the same count with the squeeze-and-excitation layers taken as per-channel constants (overlap-tile inference with
+        # whole-image gates, loops.predict_tile_dense(se="global")); equal to receptive_field for a net without them
+        _lib.call("drs_net_receptive_field_gated", h, C.byref(b), C.byref(a))
+        self.gated_receptive_field = (b.value, a.value)
         if self.dense:      # kept for callers that want the slice table (isprs:921-948)
             self.concat_off = [L.dst_coff for L in self.layers]
             self.concat_halo = self.buffers["concat"][1]

@@ -54,6 +54,10 @@ class OpLevelNet(DilatedNet):
                 self.se_state[i] = dict(act=torch.zeros(M * C, **f32), s=torch.zeros(B * C, **f32),
                                         e1=torch.zeros(B * (C // 4), **f32), e2=torch.zeros(B * C, **f32))
             self.se_scratch = torch.zeros(B * (3 * cmax + cmax // 4), **f32)
+            # whole-image gates of overlap-tile inference (forward_staged): per SE block the fp64 sums of a sweep and the gate
+            self.se_sum = [torch.zeros(p.layers[i].cout, **f64) for i in sorted(p.se)]
+            self.se_gate = [torch.zeros(p.layers[i].cout, **f32) for i in sorted(p.se)]
+            self.se_sum_scratch = torch.zeros(_lib.query("drs_se_core_sums_scratch_doubles", cmax), **f64)
         if p.se or any(q is not None and q[0] == "avg" for q in p.pools):
             self.act = torch.zeros(M * cmax, **f32)        # activated, not yet averaged output of a layer
             self.gpool = torch.zeros(M * cmax, **f32)      # gradient wrt it
@@ -184,7 +188,9 @@ class OpLevelNet(DilatedNet):
         off, _ = self.plan.offsets[name + "/biases"]
         return self.params[off:].data_ptr()
 
-    def _forward_layers(self, B, S, training, count):
+    def _forward_layers(self, B, S, training, count, staged=None):
+        """staged = (stage, boxes) (forward_staged): SE blocks before `stage` scale by their stored whole-image gate, SE block
+        `stage` adds its core sums into se_sum[stage] and ends the pass"""
         p, st = self.plan, self._stream()
         M = B * S * S
         self._prepare_weights(st, training)
@@ -221,6 +227,16 @@ class OpLevelNet(DilatedNet):
                 stt, sc = self.se_state[i], p.se[i]
                 self._k("bn_act_pool_fwd", M * L.cout * 8.0, "drs_bn_act_pool_forward", _ptr(self.z[i]), B, S, L.cout,
                         _ptr(self.mean_rstd[i]), p.alpha, 0, _ptr(stt["act"]), 0, L.cout, 0, None, st)
+                if staged is not None:
+                    j = sorted(p.se).index(i)
+                    if j == staged[0]:
+                        self._k("se_fwd", M * L.cout * 4.0, "drs_se_core_sums", _ptr(stt["act"]), L.cout, S, staged[1], B,
+                                _ptr(self.se_sum[j]), _ptr(self.se_sum_scratch), st)
+                        return
+                    self._k("se_fwd", M * L.cout * 8.0, "drs_se_scale_const", _ptr(stt["act"]), B, S, L.cout, _ptr(self.se_gate[j]),
+                            _ptr(out), Pout, ldout, coff, st)
+                    self._touch_f32(L.dst)
+                    continue
                 self._k("se_fwd", M * L.cout * 12.0, "drs_se_forward", _ptr(stt["act"]), B, S, L.cout, L.cout // 4,
                         self._pptr(sc + "_fc1/weights"), self._pptr(sc + "_fc1/biases"), self._pptr(sc + "_fc2/weights"),
                         self._pptr(sc + "_fc2/biases"), _ptr(stt["s"]), _ptr(stt["e1"]), _ptr(stt["e2"]), _ptr(out), Pout, ldout, coff, st)
@@ -252,13 +268,29 @@ class OpLevelNet(DilatedNet):
                         coff, _ptr(self.idx[i]) if (training and mx) else None, st)
                 self._touch_f32(L.dst)
 
-    def forward(self, B, S, want_logits=True, labels=False, acc_mask=False, ignore_label=-1):
+    def forward_staged(self, B, S, stage, boxes=None, want_logits=True):
+        """the op-level statement of drs_forward_staged (engine.EngineNet.forward_staged): the same launches in the same order"""
+        if not self.plan.se or not 0 <= stage <= len(self.plan.se) or (stage < len(self.plan.se) and not boxes):
+            raise ValueError("forward_staged: stage %r / boxes %r do not fit %s" % (stage, boxes, self.plan.net_type))
+        return self.forward(B, S, want_logits=want_logits, _staged=(int(stage), boxes))
+
+    def se_gate_finish(self, j, count):
+        p = self.plan
+        i = sorted(p.se)[j]
+        stt, sc, C = self.se_state[i], p.se[i], p.layers[i].cout
+        _lib.call("drs_se_gate", _ptr(self.se_sum[j]), float(count), C, C // 4, self._pptr(sc + "_fc1/weights"),
+                  self._pptr(sc + "_fc1/biases"), self._pptr(sc + "_fc2/weights"), self._pptr(sc + "_fc2/biases"), _ptr(stt["s"]),
+                  _ptr(stt["e1"]), _ptr(self.se_gate[j]), self._stream())
+
+    def forward(self, B, S, want_logits=True, labels=False, acc_mask=False, ignore_label=-1, _staged=None):
         """is_training=False pass over the slab filled by crop/feed: returns (pred uint8 [B,S,S] device,
         logits float32 [B,S,S,K] device or None).  With labels=True the confusion matrix of (self.labels,
         pred) is added into self.conf (validation, isprs:1599)."""
         self._check(B, S)
         p, st = self.plan, self._stream()
-        self._forward_layers(B, S, False, B * S * S)
+        self._forward_layers(B, S, False, B * S * S, _staged)
+        if _staged is not None and _staged[0] < len(p.se):
+            return None
         feat, Pf, ldf, cf = self._feat_view()
         off, _ = p.offsets["conv_classifier/weights"]
         _lib.call("drs_classifier_loss", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K, self.params[off:].data_ptr(),

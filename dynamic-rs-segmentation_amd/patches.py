@@ -152,6 +152,22 @@ def dihedral_apply(x, g, inverse=False):
     return z[fy, fx]
 
 
+def dihedral_core_boxes(boxes, T, g):
+    """The core boxes of a dense plan (dense_tiles rows (y0, x0, cy0, cy1, cx0, cx1)) as they lie in the g-TRANSFORMED T x T tiles
+    (dihedral_apply): rows (0, 0, i0, i1, j0, j1), tile-local and half-open -- position (i, j) of the transformed tile is inside iff
+    the tile pixel sigma_g(i, j) it shows is a core pixel.  (A flip mirrors the interval on its axis, the transpose swaps the axes.)"""
+    b = np.asarray(boxes, dtype=np.int64)
+    r0, r1, c0, c1 = b[:, 2] - b[:, 0], b[:, 3] - b[:, 0], b[:, 4] - b[:, 1], b[:, 5] - b[:, 1]
+    if int(g) & 4:
+        r0, r1, c0, c1 = c0, c1, r0, r1
+    if int(g) & 2:
+        r0, r1 = T - r1, T - r0
+    if int(g) & 1:
+        c0, c1 = T - c1, T - c0
+    z = np.zeros_like(r0)
+    return np.stack([z, z, r0, r1, c0, c1], axis=1)
+
+
 def dihedral_index(g, T):
     """The numpy statement of sigma_g and sigma_g^-1 on a T x T tile: ((I, J), (Ii, Ji)), int64 [T][T] each, such that the transformed
     tile is Y = X[I, J] (Y[i][j] = X[sigma_g(i, j)]: flip, then transpose) and logits L of Y land on X's grid as L[Ii, Ji]

@@ -188,6 +188,22 @@ int drs_se_forward(const float* act, int B, int S, int C, int R, const float* w1
 int drs_se_backward(const float* gy, int ld_g, int coff_g, const float* act, const float* s, const float* e1, const float* e2,
                     const float* w1, const float* w2, int B, int S, int C, int R, float* gact, float* dw1, float* db1, float* dw2,
                     float* db2, float* scratch, void* stream);
+/* the same layer gated by the mean over a whole IMAGE that is forwarded in tiles (overlap-tile inference with se="global", DESIGN.md
+ * 8a.3): the gate is then one constant vector per image, made in three steps.
+ * drs_se_core_sums : act [n*T*T][C] (the activated block output of n tiles of side T) and boxes [n][6] = (y0, x0, cy0, cy1, cx0, cx1)
+ *           (device data, drs_tile_place's layout): sums[c] += sum of act over every tile's core box (cores partition the image, so
+ *           a whole plan counts every pixel once).  fp32 loads accumulated in fp64 in a fixed order, no atomics; launches on one
+ *           stream accumulate in stream order.  A core that does not lie inside its tile adds nothing.  The caller zeroes sums when
+ *           a sweep begins.  scratch: drs_se_core_sums_scratch_doubles(C) doubles.  n * T * T < 2^31.
+ * drs_se_gate      : sums [C] over `count` pixels -> s = (float)(sums / count) (fp64 division, one rounding), e1 [R], e2 [C] by
+ *           drs_se_forward's excite arithmetic for one image.
+ * drs_se_scale_const: out view = act * e2[c] with ONE gate vector e2 [C] for the whole batch (halo zeroed). */
+int drs_se_core_sums_scratch_doubles(int C);
+int drs_se_core_sums(const float* act, int C, int T, const int* boxes, int n, double* sums, double* scratch, void* stream);
+int drs_se_gate(const double* sums, double count, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
+                float* s, float* e1, float* e2, void* stream);
+int drs_se_scale_const(const float* act, int B, int S, int C, const float* e2, float* out, int P_out, int ld_out, int coff_out,
+                       void* stream);
 
 /* ---- 1x1 classifier + sparse softmax cross-entropy + tf.argmax (+ their gradients) ----------------------
  * (isprs:1024-1031, 1089-1099, 1690; masked loss: contest_dilated_random.py:881-901; confusion matrix:
@@ -360,6 +376,10 @@ int drs_net_info(const drs_net_t* net, char* net_type, int name_cap, float* alph
  * its squeeze block and the larger expand block).  DRS_ERR_ARG for nets with squeeze-and-excitation blocks: their global average over
  * the patch has no finite field. */
 int drs_net_receptive_field(const drs_net_t* net, int* before, int* after);
+/* the same count with every squeeze-and-excitation layer taken as a per-channel constant (1 x 1): the field of the chains between the
+ * gates, which overlap-tile inference with whole-image gates relies on (drs_forward_staged).  Equal to drs_net_receptive_field for a
+ * net without such layers; dilated_icpr_rate6_SE: (27, 28). */
+int drs_net_receptive_field_gated(const drs_net_t* net, int* before, int* after);
 /* squeeze-and-excitation block `index`: scope ("se1": variables <scope>_fc1/weights ...), the block whose activation it scales,
  * channels C and the reduced width C / 4 (isprs:682-697) */
 int drs_net_se_info(const drs_net_t* net, int index, char* scope, int scope_cap, int* layer, int* channels, int* reduced);
@@ -419,6 +439,18 @@ int drs_net_set_rccl(drs_net_t* net, int world, int rank, void* comm_small, void
 int drs_train_step(drs_net_t* net, int B, int S, float lr0, int flags, double global_pixels, void* stream);
 int drs_forward(drs_net_t* net, int B, int S, int flags, int ignore_label, void* stream);
 int drs_apply_update(drs_net_t* net, float lr0, void* stream);        /* the update alone (after DRS_NO_UPDATE) */
+/* overlap-tile inference of a net with n_se squeeze-and-excitation blocks, gated by the mean over the whole IMAGE instead of the patch
+ * (opt-in): n_se + 1 sweeps over the tile plan.  Buffers "se_sum<j>" (double [C_j]) and "se_gate<j>" (float [C_j]).
+ *   sweep j < n_se : zero "se_sum<j>" on the stream; for every batch of B tiles in "act:x0" drs_forward_staged(stage = j, boxes = the
+ *                    B tiles' [B][6] device boxes as drs_tile_place reads them, n_boxes = B): the eval-mode pass up to the block SE j
+ *                    follows, SE blocks [0, j) scaling by "se_gate<..>", the block's activated output summed per channel over the
+ *                    cores into "se_sum<j>" (drs_se_core_sums).  Then, under data parallelism, one fp64 sum all-reduce of
+ *                    "se_sum<j>" by the host, and drs_net_se_gate_finish(j, count = h * w) -> "se_gate<j>" (drs_se_gate).
+ *   sweep n_se     : drs_forward_staged(stage = n_se; boxes unused): the whole pass with every gate, "pred" / "logits"
+ *                    (DRS_WANT_LOGITS) as drs_forward writes them.
+ * DRS_ERR_ARG for a net without squeeze-and-excitation blocks.  drs_forward is not affected. */
+int drs_forward_staged(drs_net_t* net, int B, int S, int stage, const int* boxes, int n_boxes, int flags, void* stream);
+int drs_net_se_gate_finish(drs_net_t* net, int index, double count, void* stream);
 /* the backward pass of drs_train_step on two streams (the filter gradients on a stream of the library's beside the batch-norm-backward /
  * input-gradient chain on `stream`): mode -1 = by the library's rule (steps of fewer than 2^18 pixels; the default), 0 = never (a
  * host that must see every launch of the step on ITS stream), 1 = always.  Bitwise the same step in every mode. */

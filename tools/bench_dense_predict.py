@@ -7,7 +7,10 @@ runs `reps` times, alternating, timed by a host clock around a device synchroniz
 tta=flip|d4 adds a third mode: overlap-tile inference with that dihedral test-time augmentation (predict_tile_dense(..., tta=...)),
 on its own symmetric-margin plan.  scales=0.75,1,1.25 adds the multi-scale test-time augmentation mode (predict_tile_dense(...,
 scales=...); with tta= as well, both at once), every scale's tile shapes warmed up too.
-    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3] [tta=flip|d4] [scales=0.75,1,1.25]
+se=global is a mode of its own: the squeeze-and-excitation net (dilated_icpr_rate6_SE), its sliding-window map at S = 64 against its
+overlap-tile map with whole-image gates (predict_tile_dense(..., se="global")) -- the plain dense mode does not exist
+for that net.
+    python tools/bench_dense_predict.py [mosaic=6000] [tile=512] [reps=3] [tta=flip|d4] [scales=0.75,1,1.25] [se=global]
 """
 import json
 import os
@@ -30,7 +33,9 @@ def checksum(pred):
     return int(((pred.reshape(-1).long() + 1) * (idx % 65521 + 1)).sum().item() % (1 << 61))
 
 
-def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None):
+def setup(net_type, mosaic):
+    """config 5's mosaic on the device, its statistics, and `net_type` with moving statistics from one train-mode pass over 256 spread
+    windows"""
     dev = "cuda:0"
     n, S, Bw = int(mosaic), 64, 256
     g0 = torch.Generator(device=dev).manual_seed(5)
@@ -46,7 +51,7 @@ def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None):
     pool.h, pool.w = [n], [n]
     pool.tile_h = torch.tensor([n], dtype=torch.int32, device=dev)
     pool.tile_w = torch.tensor([n], dtype=torch.int32, device=dev)
-    net = DilatedNet(NET, CH, K, WD, b_max=Bw, s_max=S, device=dev, seed=42)
+    net = DilatedNet(net_type, CH, K, WD, b_max=Bw, s_max=S, device=dev, seed=42)
     nh, nw = P.window_counts(n, n, S, S // 2)
     spread = np.linspace(0, nh * nw - 1, Bw).astype(np.int64)
     allpos = np.stack([np.minimum((spread // nw) * (S // 2), n - S), np.minimum((spread % nw) * (S // 2), n - S)], axis=1)
@@ -57,6 +62,77 @@ def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None):
         mr = net.mean_rstd[i].cpu().numpy().reshape(L.cout, 2).astype(np.float64)
         net.set_variable(L.name + "/moving_mean", mr[:, 0])
         net.set_variable(L.name + "/moving_variance", np.maximum(1.0 / mr[:, 1] ** 2 - 1e-3, 1e-6))
+    return dev, n, S, Bw, pool, net, mean, std, nh, nw, allpos
+
+
+def main_se(mosaic=6000, tile=512, reps=3):
+    """se=global: the SE net's window map against its overlap-tile map with whole-image gates"""
+    net_type = "dilated_icpr_rate6_SE"
+    dev, n, S, Bw, pool, net, mean, std, nh, nw, allpos = setup(net_type, mosaic)
+    # (the initialiser's fully connected SE weights, stddev 0.005, leave every gate at sigmoid(0.1): give the gates something to do)
+    g1 = torch.Generator(device="cpu").manual_seed(7)
+    for name in net.variable_names():
+        if "_fc" in name and name.endswith("/weights"):
+            net.set_variable(name, (torch.randn(net.get_variable(name).shape, generator=g1) * 0.3).numpy())
+    T = min(n, int(tile))
+    before, after = net.plan.gated_receptive_field
+    boxes = P.dense_tiles(n, n, T, before, after)
+    B_t = loops.dense_batch(net.plan, T)
+    for b in sorted({Bw, nh * nw % Bw} - {0}):
+        P.crop_to_net(net, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), allpos[:b]], axis=1), S, mean, std)
+        net.forward(b, S)
+    twin = loops.dense_twin(net, T, B_t)
+    n_se = len(net.plan.se)
+    boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(dev)
+    for b in sorted({B_t, len(boxes) % B_t} - {0}):          # every shape of every sweep, code objects loaded outside the timing
+        P.crop_to_net(twin, pool, np.concatenate([np.zeros((b, 1), dtype=np.int64), boxes[:b, :2]], axis=1), T, mean, std)
+        for j in range(n_se):
+            twin.forward_staged(b, T, j, boxes_dev.data_ptr())
+            twin.se_gate_finish(j, float(n) * n)
+        twin.forward_staged(b, T, n_se)
+    torch.cuda.synchronize()
+    modes = ("window", "dense_se")
+    runs, maps = {m: [] for m in modes}, {}
+    for _ in range(int(reps)):
+        for mode in modes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if mode == "window":
+                pred, _ = loops.predict_tile(net, pool, 0, S, Bw, mean, std)
+            else:
+                pred, _ = loops.predict_tile_dense(net, pool, 0, B_t, mean, std, tile=T, se="global")
+            torch.cuda.synchronize()
+            runs[mode].append(time.perf_counter() - t0)
+            maps[mode] = pred
+    # MACs per pixel of a sweep: the blocks up to the one SE j follows; the last sweep is the whole net
+    per_block = [L.k * L.k * L.cin * L.cout for L in net.plan.layers]
+    sweeps = [sum(per_block[:li + 1]) for li in sorted(net.plan.se)] + [net.plan.mac_per_pixel()]
+    mac = {"window": net.plan.mac_per_pixel() * nh * nw * S * S, "dense_se": sum(sweeps) * len(boxes) * T * T}
+    out = dict(workload="BASELINE config 5's mosaic (%dx%dx5) with %s on ONE GPU: sliding windows 64x64 at stride 32 in batches of 256 "
+                        "(every window gated by its own mean) vs overlap-tile inference with whole-image gates at T = %d (%d sweeps "
+                        "over %d tiles, %d tiles per forward)" % (n, n, net_type, T, n_se + 1, len(boxes), B_t),
+               gated_receptive_field=[before, after], tiles=len(boxes), windows=nh * nw, reps=int(reps),
+               sweep_mac_per_pixel=sweeps, sweeps_vs_one_pass=round(sum(sweeps) / sweeps[-1], 3))
+    for mode in modes:
+        best = min(runs[mode])
+        flops = 2.0 * mac[mode]
+        out[mode] = dict(seconds=[round(v, 3) for v in runs[mode]], best_s=round(best, 3), map_mpx_per_s=round(n * n / best / 1e6, 2),
+                         flop=flops, fp32_floor_s=round(flops / (PEAK_FP32_MFMA_TFLOPS * 1e12), 3),
+                         fp32_ceiling_frac=round(flops / best / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4))
+    out["dense_se_vs_window_time"] = round(out["dense_se"]["best_s"] / out["window"]["best_s"], 3)
+    out["dense_se_vs_window_flop_predicted"] = round(mac["dense_se"] / mac["window"], 3)
+    out["maps_agree_frac"] = round(float((maps["window"] == maps["dense_se"]).float().mean().item()), 5)     # for information only
+    out["dense_se_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["dense_se"])
+    out["window_map_checksum"] = "sum((label+1) * (flat_index %% 65521 + 1)) mod 2^61 = %d" % checksum(maps["window"])
+    print(json.dumps(out))
+
+
+def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None, se=None):
+    if se is not None:
+        if se != "global" or tta is not None or scales is not None:
+            sys.exit("se=global is a mode of its own (no tta= / scales= beside it)")
+        return main_se(mosaic, tile, reps)
+    dev, n, S, Bw, pool, net, mean, std, nh, nw, allpos = setup(NET, mosaic)
 
     T = min(n, int(tile))
     before, after = net.plan.receptive_field
@@ -158,4 +234,4 @@ def main(mosaic=6000, tile=512, reps=3, tta=None, scales=None):
 
 
 if __name__ == "__main__":
-    main(**{k: (v if k in ("tta", "scales") else int(v)) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
+    main(**{k: (v if k in ("tta", "scales", "se") else int(v)) for k, v in (a.split("=", 1) for a in sys.argv[1:])})
