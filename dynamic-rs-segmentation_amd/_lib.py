@@ -53,6 +53,9 @@ SIGNATURES = {
     "drs_classifier_rows": (_i, [_i, _i]),
     "drs_classifier_loss": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _p, _p, _p,
                                  _p, _p]),
+    "drs_classifier_loss_weighted": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _i, _p, _p,
+                                          _p, _p, _p]),
+    "drs_label_histogram": (_i, [_p, _sz, _i, _i, _p, _p]),
     "drs_rows_reduce_f32": (_i, [_p, _i, _i, _p, _p, _p]),
     "drs_sum_f64": (_i, [_p, _i, _p, _p]),
     "drs_l2_loss": (_i, [_p, _sz, _p, _p, _p]),
@@ -105,6 +108,8 @@ SIGNATURES = {
     "drs_forward_staged": (_i, [_p, _i, _i, _i, _p, _i, _i, _p]),
     "drs_net_se_gate_finish": (_i, [_p, _i, _d, _p]),
     "drs_net_set_two_streams": (_i, [_p, _i]),
+    "drs_net_set_class_weights": (_i, [_p, _p, _i]),
+    "drs_net_get_class_weights": (_i, [_p, _p, _i, C.POINTER(_i)]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),
     "drs_net_timing_summary": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),

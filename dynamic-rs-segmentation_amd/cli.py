@@ -12,6 +12,8 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     --dense-tta
   + optionally, anywhere, with --dense-tile only, `--dense-se=global` (nets with squeeze-and-excitation blocks, which --dense-tile
     refuses without it): the blocks are gated by the mean over the whole image, computed exactly in tiles (predict_tile_dense's se)
+  + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
+    cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -130,6 +132,31 @@ def parse_dense_se(argv):
     return (list(argv) if se is None else rest), se
 
 
+CLASS_WEIGHTS_FLAG = "--class-weights"
+
+
+def parse_class_weights(argv, num_classes=None):
+    """all flavours: the optional `--class-weights=balanced|median|w0,w1,...` (anywhere in argv; training).  Returns (argv without the
+    flag, "balanced" / "median" / tuple of floats), or (argv unchanged, None) without it.  A bare flag, a malformed list, a negative
+    or non-finite weight, a list whose length is not num_classes (when given), or the flag given twice, raises ValueError."""
+    rest, cw = [], None
+    for a in argv:
+        if a != CLASS_WEIGHTS_FLAG and not a.startswith(CLASS_WEIGHTS_FLAG + "="):
+            rest.append(a)
+            continue
+        if cw is not None:
+            raise ValueError(CLASS_WEIGHTS_FLAG + " given more than once")
+        form = "%s=%s|w0,w1,... (%s finite weights >= 0)" % (CLASS_WEIGHTS_FLAG, "|".join(P.CLASS_WEIGHT_RECIPES),
+                                                             "one per class:" if num_classes is None else str(num_classes))
+        try:
+            cw = P.parse_class_weights(a[len(CLASS_WEIGHTS_FLAG) + 1:])
+        except ValueError:
+            raise ValueError("%s: expected %s" % (a, form)) from None
+        if not isinstance(cw, str) and num_classes is not None and len(cw) != num_classes:
+            raise ValueError("%s: %d weights given, expected %s" % (a, len(cw), form))
+    return (list(argv) if cw is None else rest), cw
+
+
 def print_params(list_params, argv):
     print("+" * 97)
     for i in range(1, len(argv)):
@@ -188,6 +215,7 @@ def main(argv=None, device=None, comm=None):
         argv, dense_tta = parse_dense_tta(argv)
         argv, dense_scales = parse_dense_scales(argv)
         argv, dense_se = parse_dense_se(argv)
+        argv, class_weights = parse_class_weights(argv, 6)
     except ValueError as e:
         sys.exit(str(e))
     if dense_tta is not None and dense_tile is None:
@@ -200,6 +228,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(DENSE_TILE_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if class_weights is not None and argv[16] != "training":
+        sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if comm.rank == 0:
         print_params(ISPRS_PARAMS, argv)
     (input_path, output_path, former_model_path, tr, te, lr, wd, bs, niter, ref_crop, ref_stride, net_type,
@@ -248,7 +278,8 @@ def main(argv=None, device=None, comm=None):
         return loops.train(training_data, training_labels, train_dist, rot, testing_data, testing_labels, test_dist,
                            testing_instances, lr_initial, batch_size, niter, weight_decay, mean_full, std_full, update_type,
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
-                           output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm)
+                           output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
+                           class_weights=class_weights)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -294,6 +325,10 @@ def main_coffee(argv=None, device=None, comm=None):
     from . import loops_indexed as LI
     device, comm = _placement(device, comm)
     argv = list(sys.argv if argv is None else argv)
+    try:
+        argv, class_weights = parse_class_weights(argv, 2)
+    except ValueError as e:
+        sys.exit(str(e))
     if len(argv) < len(COFFEE_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(COFFEE_PARAMS))
     if comm.rank == 0:
@@ -309,7 +344,7 @@ def main_coffee(argv=None, device=None, comm=None):
     return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
-                    quantize_f16=True)                      # coffee:293: training patches pass through float16
+                    quantize_f16=True, class_weights=class_weights)     # coffee:293: training patches pass through float16
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -317,6 +352,10 @@ def main_contest(argv=None, device=None, comm=None):
     from . import datasets, loops_indexed as LI
     device, comm = _placement(device, comm)
     argv = list(sys.argv if argv is None else argv)
+    try:
+        argv, class_weights = parse_class_weights(argv, 7)
+    except ValueError as e:
+        sys.exit(str(e))
     if len(argv) < len(CONTEST_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(CONTEST_PARAMS))
     if comm.rank == 0:
@@ -338,7 +377,9 @@ def main_contest(argv=None, device=None, comm=None):
     if operation == "train":
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
-                        void_label=7, device=device, comm=comm, flavour="contest")
+                        void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights)
+    if class_weights is not None:
+        sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":
         from .net import DilatedNet
         step = loops.step_from_model_path(current_model)

@@ -189,6 +189,8 @@ struct drs_net {
   hipEvent_t ev_gz[2], ev_wg[2];
   hipEvent_t ev_cls = nullptr;              // two-stream pass: compute stream -> filter-gradient stream (the step has begun; the classifier launch is done)
   hipEvent_t ev_prep = nullptr;             // ... and back: the step's preparation launch (filter flips, zero fills) is done
+  bool has_wc = false;                      // class weights of the training loss (drs_net_set_class_weights); none: the unweighted kernels
+  float wc[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -1045,6 +1047,32 @@ int drs_net_set_two_streams(drs_net_t* n, int mode) {
   return DRS_OK;
 }
 
+// Class weights of the training loss (drs_train_step only: the forward passes have no loss): host_w = K finite, non-negative floats
+// (HOST pointer; K = the net's class count), copied into the handle; NULL clears them.  The step hands them to the classifier launch
+// by value (drs_classifier_loss_weighted): no device buffer.
+int drs_net_set_class_weights(drs_net_t* n, const float* host_w, int K) {
+  if (!n) return DRS_ERR_ARG;
+  if (!host_w) {
+    n->has_wc = false;
+    for (int k = 0; k < 8; ++k) n->wc[k] = 1.f;
+    return DRS_OK;
+  }
+  if (K != n->K) return DRS_ERR_ARG;
+  for (int k = 0; k < K; ++k)
+    if (!std::isfinite(host_w[k]) || host_w[k] < 0.f) return DRS_ERR_ARG;
+  for (int k = 0; k < 8; ++k) n->wc[k] = k < K ? host_w[k] : 1.f;
+  n->has_wc = true;
+  return DRS_OK;
+}
+
+// host_w (K_cap >= the net's K floats, HOST) <- the weights in use (ones when none are set); *is_set = 1 if weights are set
+int drs_net_get_class_weights(const drs_net_t* n, float* host_w, int K_cap, int* is_set) {
+  if (!n || !host_w || K_cap < n->K) return DRS_ERR_ARG;
+  for (int k = 0; k < n->K; ++k) host_w[k] = n->wc[k];
+  if (is_set) *is_set = n->has_wc ? 1 : 0;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1255,11 +1283,11 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   double* scratch = P.colsum_scratch;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
-    DRS_TRY(drs_classifier_loss(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
-                                P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
-                                (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                (flags & DRS_WANT_LOGITS) ? P.logits : nullptr, P.pred, gfeat, f.C, 0,
-                                P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    DRS_TRY(drs_classifier_loss_weighted(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+                                         P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                         (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
+                                         n->has_wc ? n->wc : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr, P.pred, gfeat,
+                                         f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
   }
   // the classifier's slab reductions (its kernel / bias gradients, the cross-entropy sum) and the L2 term: seven launches of ~5 us that
   // nothing needs before the end of the step -- in the two-stream backward pass they go to the filter-gradient stream (below), off

@@ -10,6 +10,7 @@
 // so a step is bitwise reproducible.  Everything is channels-last; a thread owns 4 consecutive channels (16-B
 // accesses), consecutive lanes own consecutive channel quads, so every wave access is a run of full cache lines.
 #include "drs_common.hpp"
+#include <cmath>
 
 namespace {
 
@@ -891,11 +892,23 @@ struct ClsArgs {
   int rows_per_block;
   int dma_span, nrows;       // classifier_dma_kernel: slab rows' worth of pixels per workgroup; slab rows in all
   float rcpS, rcpSS;
+  float wc[8];               // class weights of the weighted forms (WT), by value: scalar registers, no buffer and no load
 };
 
+// The weight of a pixel's label: a register select over the eight by-value weights (a label outside [0, K) never enters the loss:
+// whatever comes out for it is multiplied into nothing)
+template <int KN = 8>
+__device__ __forceinline__ float cls_weight(const ClsArgs& a, int y) {
+  float w = a.wc[0];
+#pragma unroll
+  for (int k = 1; k < KN; ++k) w = y == k ? a.wc[k] : w;
+  return w;
+}
+
 // CI = C / 64; KM = class slots carried per lane: the exact class count for the reference's 2 / 6 / 7 classes (no masked
-// slots, no wasted multiplies), 8 otherwise
-template <int CI, int KM>
+// slots, no wasted multiplies), 8 otherwise.  WT (all three forms): class-weighted loss, L = inv_n * sum wc[y] CE -- the pixel's
+// weight scales the logit gradients (through inv_n) and its loss term; without WT the code is what it was, no multiply by one
+template <int CI, int KM, bool WT>
 __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
   __shared__ float red[4][CI * 64 * KM];
   __shared__ float redb[4][KM];
@@ -991,13 +1004,15 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
     const float inv = 1.0f / se;
     float ly = 0.f;
     float dl[KM];
+    const float wy = WT ? cls_weight<KM>(a, y) : 1.f;
+    const float sc = WT ? a.inv_n * wy : a.inv_n;
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
       const float pk = ex[k] * inv;
-      dl[k] = in_loss && k < K ? (pk - (k == y ? 1.f : 0.f)) * a.inv_n : 0.f;
+      dl[k] = in_loss && k < K ? (pk - (k == y ? 1.f : 0.f)) * sc : 0.f;
       if (k == y) ly = lg[k];
     }
-    if (in_loss) lsum += (double)(__logf(se) + mx - ly);
+    if (in_loss) lsum += WT ? (double)wy * (double)(__logf(se) + mx - ly) : (double)(__logf(se) + mx - ly);
     if (a.gfeat) {
 #pragma unroll
       for (int gi = 0; gi < CI / V; ++gi) {
@@ -1079,7 +1094,7 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
 // instruction for the first (k = channel on l >> 4), 4 pixels x 256 B for the third (k = pixel on l >> 4) -- the second time
 // out of L2.  One workgroup = 4 waves, each walking its own 16-pixel tiles of the workgroup's pixel range; the filter sits in
 // LDS in the two operand arrangements.  Sums over pixels (dW, db, the loss) stay per workgroup and are added in wave order.
-template <int CQ, bool TRAIN>
+template <int CQ, bool TRAIN, bool WT>
 __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
   constexpr int C = CQ * 64, NJ = C / 16, KP = 16;
   __shared__ __attribute__((aligned(16))) float W1[C * KP];      // [c / 16][(c % 16) / 4][row i <-> class (i >> 2) + 4 (i & 3)][c % 4]: A operand of the first product
@@ -1179,10 +1194,12 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     se += __shfl_xor(se, 16);                       // (a + b == b + a bit for bit: every lane of the pixel gets the same sum)
     se += __shfl_xor(se, 32);
     const float inv = 1.0f / se;
-    const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * a.inv_n : 0.f;
-    const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * a.inv_n : 0.f;
-    if (in_loss && cls0 == y) lsum += (double)(__logf(se) + mx - lg0);
-    if (in_loss && cls1 == y) lsum += (double)(__logf(se) + mx - lg1);
+    const float wy = WT ? cls_weight(a, y) : 1.f;
+    const float sc = WT ? a.inv_n * wy : a.inv_n;
+    const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
+    const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
+    if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
+    if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
     db0 += dl0;
     db1 += dl1;
     if (!a.gfeat) continue;
@@ -1273,7 +1290,7 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
 // hidden behind a whole tile of arithmetic.  Every vector-memory operation inside the loop is counted by hand: the label / mask
 // bytes are inline-asm loads waited for with vmcnt(#DMA instructions), the DMA itself with vmcnt(#feature-gradient stores).
 // Products, orientations, class permutation and every sum are those of classifier_mfma_kernel: results are bitwise the same.
-template <int CQ, bool TRAIN>
+template <int CQ, bool TRAIN, bool WT>
 __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int C = CQ * 64, NJ = C / 16, KP = 16, NI = 4 * CQ;      // NI: 1-KiB DMA instructions per tile
@@ -1399,10 +1416,14 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       se += __shfl_xor(se, 16);
       se += __shfl_xor(se, 32);
       const float inv = 1.0f / se;
-      const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * a.inv_n : 0.f;
-      const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * a.inv_n : 0.f;
-      if (in_loss && cls0 == y) lsum += (double)(__logf(se) + mx - lg0);
-      if (in_loss && cls1 == y) lsum += (double)(__logf(se) + mx - lg1);
+      // (the weight select: vector-ALU work of the softmax section, after the logits' MFMAs have been issued and before the filter
+      // gradient's -- no MFMA waits for it)
+      const float wy = WT ? cls_weight(a, y) : 1.f;
+      const float sc = WT ? a.inv_n * wy : a.inv_n;
+      const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
+      const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
+      if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
+      if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
       db0 += dl0;
       db1 += dl1;
       if (a.gfeat) {
@@ -1556,6 +1577,28 @@ __global__ void confusion_kernel(const unsigned char* __restrict__ labels, const
     const int r = threadIdx.x / K, c = threadIdx.x - r * K;
     const unsigned v = sh[r * 8 + c];
     if (v) atomicAdd(&conf[threadIdx.x], v);
+  }
+}
+
+// Per-class pixel counts of a label map (the class weights' recipes, patches.class_weights): labels equal to void_label or outside
+// [0, K) are left out.  Per-workgroup 32-bit counters in LDS, added to the 64-bit totals by integer atomics: order-independent,
+// exact.  The 32-bit counters hold because a workgroup sees fewer than 2^32 labels: drs_label_histogram launches 1024 workgroups
+// from 2^18 labels on and refuses n >= 2^40, at most 2^30 labels each -- its grid cap and its bound on n go together.  The
+// workgroup has at least 8 threads (they zero and flush the counters); the one launch site uses 256.
+__global__ void label_histogram_kernel(const unsigned char* __restrict__ labels, size_t n, int K, int void_label,
+                                       unsigned long long* __restrict__ counts) {
+  __shared__ unsigned int sh[8];
+  if (threadIdx.x < 8) sh[threadIdx.x] = 0u;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int y = labels[i];
+    if (y == void_label || y >= K) continue;
+    atomicAdd(&sh[y], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < K) {
+    const unsigned v = sh[threadIdx.x];
+    if (v) atomicAdd(&counts[threadIdx.x], (unsigned long long)v);
   }
 }
 
@@ -1770,12 +1813,21 @@ int drs_debug_slide_minrows(int v) { const int old = g_slide_minrows; if (v >= 1
 int drs_debug_cls_variant(int v) { const int old = g_cls_variant; if (v >= 0) g_cls_variant = v; return old; }
 #endif
 
-int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
-                        const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
-                        const unsigned char* acc_mask, float inv_n, float* logits, unsigned char* pred, float* gfeat,
-                        int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial,
-                        unsigned int* conf, void* stream) {
+// class_weights: HOST pointer to K floats or NULL.  NULL, all weights exactly 1, or no labels (inference): the unweighted kernels,
+// which do not multiply at all (bit for bit drs_classifier_loss); otherwise the WT instantiations with the weights by value.
+int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                                 const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                                 const unsigned char* acc_mask, float inv_n, const float* class_weights, float* logits,
+                                 unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
+                                 double* loss_partial, unsigned int* conf, void* stream) {
   if (!feat || !w || !bias || K < 1 || K > 8 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
+  bool wt = false;
+  if (class_weights)
+    for (int k = 0; k < K; ++k) {
+      if (!std::isfinite(class_weights[k]) || class_weights[k] < 0.f) return DRS_ERR_ARG;
+      wt = wt || class_weights[k] != 1.0f;
+    }
+  wt = wt && labels;
   const long long M = (long long)B * S * S;
   if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
   if (labels && !loss_partial) return DRS_ERR_ARG;
@@ -1787,6 +1839,7 @@ int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff
   a.gfeat = gfeat; a.ld_g = ld_g; a.coff_g = coff_g; a.dw_partial = dw_partial; a.db_partial = db_partial;
   a.loss_partial = loss_partial; a.conf = conf;
   a.rcpS = 1.0f / (float)S; a.rcpSS = 1.0f / (float)(S * S);
+  for (int k = 0; k < 8; ++k) a.wc[k] = wt && k < K ? class_weights[k] : 1.f;
   const int nblk = drs_classifier_rows(B, S);
   a.rows_per_block = (int)(((M + nblk - 1) / nblk + 63) / 64 * 64);      // whole 16-pixel tiles per wave; trailing workgroups may be empty
   hipStream_t st = (hipStream_t)stream;
@@ -1800,26 +1853,49 @@ int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff
   if (mfma && C / 64 <= 4 && g_cls_variant != 2 && (g_cls_variant == 3 || M >= (1 << 18))) {
     a.dma_span = (nblk + 255) / 256;
     const int ndma = (nblk + a.dma_span - 1) / a.dma_span;
-#define DRS_CLS_D(cq) do { if (labels) DRS_LAUNCH((classifier_dma_kernel<cq, true>), dim3(ndma), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_dma_kernel<cq, false>), dim3(ndma), dim3(256), 0, st, a); } while (0)
+#define DRS_CLS_D(cq) do { if (wt) DRS_LAUNCH((classifier_dma_kernel<cq, true, true>), dim3(ndma), dim3(256), 0, st, a); \
+                           else if (labels) DRS_LAUNCH((classifier_dma_kernel<cq, true, false>), dim3(ndma), dim3(256), 0, st, a); \
+                           else DRS_LAUNCH((classifier_dma_kernel<cq, false, false>), dim3(ndma), dim3(256), 0, st, a); } while (0)
     switch (C / 64) { case 1: DRS_CLS_D(1); break; case 2: DRS_CLS_D(2); break; case 3: DRS_CLS_D(3); break; default: DRS_CLS_D(4); break; }
 #undef DRS_CLS_D
     return DRS_LAUNCH_CHECK();
   }
   if (mfma) {
-#define DRS_CLS_M(cq) do { if (labels) DRS_LAUNCH((classifier_mfma_kernel<cq, true>), dim3(nblk), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_mfma_kernel<cq, false>), dim3(nblk), dim3(256), 0, st, a); } while (0)
+#define DRS_CLS_M(cq) do { if (wt) DRS_LAUNCH((classifier_mfma_kernel<cq, true, true>), dim3(nblk), dim3(256), 0, st, a); \
+                           else if (labels) DRS_LAUNCH((classifier_mfma_kernel<cq, true, false>), dim3(nblk), dim3(256), 0, st, a); \
+                           else DRS_LAUNCH((classifier_mfma_kernel<cq, false, false>), dim3(nblk), dim3(256), 0, st, a); } while (0)
     switch (C / 64) { case 1: DRS_CLS_M(1); break; case 2: DRS_CLS_M(2); break; case 3: DRS_CLS_M(3); break; case 4: DRS_CLS_M(4); break;
                       case 5: DRS_CLS_M(5); break; case 6: DRS_CLS_M(6); break; default: DRS_CLS_M(7); break; }
 #undef DRS_CLS_M
     return DRS_LAUNCH_CHECK();
   }
-#define DRS_CLS_CASE(ci, km) DRS_LAUNCH((classifier_loss_kernel<ci, km>), dim3(nblk), dim3(256), 0, st, a)
+#define DRS_CLS_CASE(ci, km) do { if (wt) DRS_LAUNCH((classifier_loss_kernel<ci, km, true>), dim3(nblk), dim3(256), 0, st, a); \
+                                  else DRS_LAUNCH((classifier_loss_kernel<ci, km, false>), dim3(nblk), dim3(256), 0, st, a); } while (0)
 #define DRS_CLS_KM(km) switch (C / 64) { case 1: DRS_CLS_CASE(1, km); break; case 2: DRS_CLS_CASE(2, km); break; case 3: DRS_CLS_CASE(3, km); break; \
     case 4: DRS_CLS_CASE(4, km); break; case 5: DRS_CLS_CASE(5, km); break; case 6: DRS_CLS_CASE(6, km); break; default: DRS_CLS_CASE(7, km); break; }
   if (K == 2) DRS_CLS_KM(2) else if (K == 6) DRS_CLS_KM(6) else if (K == 7) DRS_CLS_KM(7) else DRS_CLS_KM(8)
 #undef DRS_CLS_KM
 #undef DRS_CLS_CASE
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                        const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                        const unsigned char* acc_mask, float inv_n, float* logits, unsigned char* pred, float* gfeat,
+                        int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial,
+                        unsigned int* conf, void* stream) {
+  return drs_classifier_loss_weighted(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, nullptr, logits, pred,
+                                      gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
+}
+
+// counts[k] += number of labels equal to k, k < K, other than void_label (-1: none); counts: K 64-bit counters (device), ADDED to
+int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_label, unsigned long long* counts, void* stream) {
+  if (!labels || !counts || K < 1 || K > 8 || n < 1 || n >= ((size_t)1 << 40)) return DRS_ERR_ARG;
+  // (grid cap 1024 and n < 2^40 together keep a workgroup below 2^32 labels, what label_histogram_kernel's 32-bit LDS counters
+  // can hold: a smaller grid or a larger n needs wider counters there)
+  const size_t nb = (n + 255) / 256;
+  DRS_LAUNCH(label_histogram_kernel, dim3(nb < 1024 ? (unsigned)nb : 1024u), dim3(256), 0, (hipStream_t)stream, labels, n, K, void_label,
+             counts);
   return DRS_LAUNCH_CHECK();
 }
 

@@ -285,6 +285,23 @@ class EngineNet(DilatedNet):
         self._cb = (_lib.ALLREDUCE_FN(allreduce), _lib.WAIT_FN(wait))       # kept alive with the net
         _lib.call("drs_net_set_comm", self.h, self.comm.world, self.comm.rank, C.cast(self._cb[0], C.c_void_p), C.cast(self._cb[1], C.c_void_p), None)
 
+    def _class_weights_changed(self):
+        """hand the weights to the library's net (drs_net_set_class_weights copies them: the step passes them to its classifier launch
+        by value)"""
+        w = self._class_weights
+        if w is None:
+            _lib.call("drs_net_set_class_weights", self.h, None, 0)
+        else:
+            _lib.call("drs_net_set_class_weights", self.h, w.ctypes.data_as(C.c_void_p), int(w.size))
+
+    @property
+    def class_weights(self):
+        """the weights the library's net holds (float32 [K]), or None when none are set (drs_net_get_class_weights)"""
+        import numpy as np
+        w, is_set = np.ones(self.plan.K, dtype=np.float32), C.c_int()
+        _lib.call("drs_net_get_class_weights", self.h, w.ctypes.data_as(C.c_void_p), int(w.size), C.byref(is_set))
+        return w if is_set.value else None
+
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always
         (drs_net_set_two_streams; bitwise the same step in every mode)"""

@@ -63,9 +63,38 @@ def _cm_str(cm):
     return np.array_str(np.asarray(cm)).replace("\n", "")
 
 
+CLASS_WEIGHTS_SIDE = "class_weights_step_"
+
+
+def _weights_str(w):
+    return str(["{:.6g}".format(float(v)) for v in w])
+
+
+def save_class_weights(net, output_path, step):
+    """the class weights of the training loss, when set, as the side file `class_weights_step_<step>.npy` beside the size scores (they
+    are state of the run, not of the model: the .npz keeps the TensorFlow variable set)"""
+    w = getattr(net, "class_weights", None)
+    if w is not None:
+        np.save(output_path + CLASS_WEIGHTS_SIDE + str(step) + ".npy", np.asarray(w, dtype=np.float32))
+
+
+def load_class_weights(net, former_model_path):
+    """set the weights that save_class_weights left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep:
+        return
+    path = head + CLASS_WEIGHTS_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        net.set_class_weights(np.load(path))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Class weights (restored from " + path + "): weights " + _weights_str(net.class_weights))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
-    """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802)."""
+    """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights
+    of the loss when set (save_class_weights)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
+    save_class_weights(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -84,6 +113,7 @@ def load_checkpoint(net, former_model_path):
     path = former_model_path if former_model_path.endswith(".npz") else former_model_path + ".npz"
     with np.load(path) as d:
         net.load_state_dict({k: d[k] for k in d.files})
+    load_class_weights(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -133,6 +163,22 @@ def check_training_labels(pool, num_classes, void_label=None):
         bad &= pool.labels != void_label
     if bool(bad.any()):
         raise ValueError("training labels hold class ids outside [0, %d): %s" % (num_classes, torch.unique(pool.labels[bad]).tolist()[:8]))
+
+
+def setup_class_weights(net, pool, num_classes, class_weights, comm, say, void_label=None):
+    """The class weights of a training run (train's `class_weights`): "balanced" / "median" from the per-class pixel counts of the
+    pool's label maps, counted on the device (TilePool.label_counts; the void label left out), or K numbers as given
+    (patches.class_weights).  Every rank holds the same pool and so computes the same weights: asserted once over the ranks, bit
+    patterns and counts.  One log line says what is in use."""
+    counts = pool.label_counts(num_classes, void_label)
+    wc = P.check_class_weights(list(P.class_weights(counts, class_weights)), num_classes)
+    comm.agree([int(c) for c in counts] + [int(b) for b in wc.view(np.uint32)], "class counts / class weights")
+    restored = net.class_weights
+    net.set_class_weights(wc)
+    say("Class weights (" + (class_weights if isinstance(class_weights, str) else "given") + "): pixel counts " + str([int(c) for c in counts]) +
+        " weights " + _weights_str(wc) +
+        ("" if restored is None or restored.tobytes() == wc.tobytes() else " -- replacing the weights restored from the checkpoint, " + _weights_str(restored)))
+    return wc
 
 
 # ------------------------------------------------------------------------------------------------- data parallelism
@@ -206,8 +252,12 @@ def train(training_data, training_labels, training_class_distribution, training_
           mean_full, std_full, update_type, distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values,
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
-          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None):
-    """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet."""
+          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None):
+    """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
+    class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
+    cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
+    update_type="loss", is then the WEIGHTED one (inv_n * sum wc[y] CE + the L2 term); accuracies, confusion matrices and validation
+    are not weighted.  Given here, it replaces weights restored from a checkpoint's side file; None keeps those."""
     comm = comm or NoComm()
     say = (lambda *a: print(*a)) if comm.rank == 0 else (lambda *a: None)
     say(BatchColors.OKGREEN + "TRAINING" + BatchColors.ENDC)
@@ -246,6 +296,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         load_checkpoint(net, former_model_path)
     else:
         say("Model totally initialized!")
+    if class_weights is not None:
+        setup_class_weights(net, train_pool, num_classes, class_weights, comm, say)
 
     it = 0
     epoch_mean = 0.0

@@ -151,6 +151,7 @@ class DilatedNet(object):
         self.bessel = 1 if bessel_moving_var else 0
         self.lr_decay_factor = lr_decay_factor      # 0.5 isprs:1686; 0.1 coffee:1228, contest:1021
         self.global_step = 0
+        self._class_weights = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -217,6 +218,26 @@ class DilatedNet(object):
             if n + "/Momentum" in d:
                 self.set_variable(n, d[n + "/Momentum"], "Momentum")
         self.global_step = int(d.get("main_global_step", 0))
+
+    # ------------------------------------------------------------------ class weights of the training loss
+    def set_class_weights(self, w):
+        """Class weights of the training loss (opt-in): w = K finite, non-negative numbers wc, or None to clear them.
+        train_step's data term becomes inv_n * sum over the pixels in the loss of wc[y] * CE (inv_n unchanged: 1 / the number of pixels
+        the loss averages over, NOT 1 / sum wc[y]); logits, pred, the confusion matrix, the L2 term and every forward pass are not
+        weighted.  None, the default, is the unweighted step bit for bit -- and so are all-ones weights.  State of the training run,
+        not of the model: loops.save_checkpoint keeps it in the side file, the TensorFlow checkpoint does not hold it, and an inference
+        twin does not copy it."""
+        from .patches import check_class_weights
+        self._class_weights = None if w is None else check_class_weights(w, self.plan.K)
+        self._class_weights_changed()
+
+    def _class_weights_changed(self):
+        pass
+
+    @property
+    def class_weights(self):
+        """the weights in use (float32 [K], a copy), or None"""
+        return None if self._class_weights is None else self._class_weights.copy()
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

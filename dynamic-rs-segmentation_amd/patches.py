@@ -220,6 +220,73 @@ def check_scales(scales):
     return out
 
 
+# ------------------------------------------------------------------- class weights of the training loss
+CLASS_WEIGHT_RECIPES = ("balanced", "median")
+MAX_CLASSES = 8          # the classifier kernels carry at most eight classes (include/drs.h)
+
+
+def check_class_weights(w, K):
+    """K class weights as the kernels take them: a float32 array [K] of finite, non-negative numbers (a list, tuple or array of exactly
+    K numbers; K <= 8).  Anything else raises ValueError."""
+    K = int(K)
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError("class weights: %d classes, the kernels carry 1..%d" % (K, MAX_CLASSES))
+    if isinstance(w, (str, bytes)) or not isinstance(w, (list, tuple, np.ndarray)):
+        raise ValueError("class weights %r: expected %d numbers" % (w, K))
+    if not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in np.asarray(w, dtype=object).reshape(-1)):
+        raise ValueError("class weights %r: the weights must be numbers" % (w,))
+    a = np.asarray(w, dtype=np.float64).reshape(-1)
+    if a.size != K:
+        raise ValueError("class weights %r: %d given, the net has %d classes" % (list(a), a.size, K))
+    if not np.all(np.isfinite(a)) or np.any(a < 0) or np.any(a > float(np.finfo(np.float32).max)):
+        raise ValueError("class weights %r: every weight must be finite and >= 0" % (list(a),))
+    return np.ascontiguousarray(a.astype(np.float32))
+
+
+def class_weights(counts, recipe):
+    """The class weights wc [K] (float64) of the weighted training loss from the per-class pixel counts n_k of the training labels
+    (TilePool.label_counts).  With N = sum n_k and Kp = the number of classes that occur:
+      "balanced": wc_k = N / (Kp n_k), so that sum_k (n_k / N) wc_k = 1: the expected scale of the weighted loss (normalised by the
+                  pixel count, DESIGN.md 3a) is that of the unweighted one;
+      "median":   wc_k = median(f) / f_k with f_k = n_k / N, the median over the classes that occur (median-frequency balancing);
+      a list / tuple / array of K numbers: taken as given (check_class_weights).
+    A class that never occurs gets weight 1: it never enters the sum."""
+    n = np.asarray(counts)
+    if n.ndim != 1 or not 1 <= n.size <= MAX_CLASSES or not np.issubdtype(n.dtype, np.integer) or np.any(n < 0):
+        raise ValueError("class counts %r: expected 1..%d non-negative integers" % (counts, MAX_CLASSES))
+    if not isinstance(recipe, str):
+        return check_class_weights(recipe, n.size).astype(np.float64)
+    if recipe not in CLASS_WEIGHT_RECIPES:
+        raise ValueError("class weights %r: expected one of %s or %d numbers" % (recipe, "|".join(CLASS_WEIGHT_RECIPES), n.size))
+    w = np.ones(n.size, dtype=np.float64)
+    occ = n > 0
+    if not occ.any():
+        return w
+    nk = n[occ].astype(np.float64)
+    N = float(nk.sum())
+    if recipe == "balanced":
+        w[occ] = N / (float(occ.sum()) * nk)
+    else:
+        f = nk / N
+        w[occ] = float(np.median(f)) / f
+    return w
+
+
+def parse_class_weights(text):
+    """The value of the command lines' --class-weights option: a recipe name as it stands, or "w0,w1,..." as a tuple of floats (finite,
+    >= 0; their count is checked against the net's classes where the net is known).  Anything else raises ValueError."""
+    if text in CLASS_WEIGHT_RECIPES:
+        return text
+    try:
+        vals = [float(t) for t in text.split(",")] if text and text == text.strip() and " " not in text else None
+    except ValueError:
+        vals = None
+    if not vals or len(vals) > MAX_CLASSES or not all(math.isfinite(v) and v >= 0 for v in vals):
+        raise ValueError("class weights %r: expected %s or up to %d finite weights >= 0 (w0,w1,...)"
+                         % (text, "|".join(CLASS_WEIGHT_RECIPES), MAX_CLASSES))
+    return tuple(vals)
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its
@@ -301,6 +368,19 @@ class TilePool(object):
         self.lab_off = torch.from_numpy(loff).to(self.dev)
         self.tile_h = torch.tensor(self.h, dtype=torch.int32, device=self.dev)
         self.tile_w = torch.tensor(self.w, dtype=torch.int32, device=self.dev)
+
+    def label_counts(self, K, void_label=None):
+        """Per-class pixel counts n_k, k < K, over every label map of the pool (int64 [K]), counted on the device where the maps are
+        resident (drs_label_histogram: integer atomics, exact); pixels equal to void_label (None / negative: none) or >= K are left
+        out.  Synchronises."""
+        K = int(K)
+        if not 1 <= K <= MAX_CLASSES:
+            raise ValueError("label counts: %d classes, the kernel carries 1..%d" % (K, MAX_CLASSES))
+        void = -1 if void_label is None or int(void_label) < 0 else int(void_label)
+        counts = torch.zeros(K, dtype=torch.int64, device=self.dev)
+        _lib.call("drs_label_histogram", self.labels.data_ptr(), int(self.labels.numel()), K, void, counts.data_ptr(),
+                  torch.cuda.current_stream(self.dev).cuda_stream)
+        return counts.cpu().numpy()
 
 
 def _shift_inside(inst_xy, pool, S):

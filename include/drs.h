@@ -218,6 +218,25 @@ int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff
                         const unsigned char* acc_mask, float inv_n, float* logits, unsigned char* pred, float* gfeat,
                         int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial,
                         unsigned int* conf, void* stream);
+/* The same with per-class weights (opt-in).  class_weights: HOST pointer to K finite, non-negative floats wc (copied
+ * into the kernel arguments: no device buffer, no extra load), or NULL.  With weights the data term of the loss is
+ *     L = inv_n * sum over the pixels p in the loss of wc[y_p] * CE_p
+ * ("in the loss" as above: loss_mask set when given, y_p < K) and the logit gradient is wc[y_p] * (softmax_k - [k == y_p]) * inv_n:
+ * gfeat, dw_partial, db_partial and loss_partial (sum of wc[y] * CE, fp64) follow from it; logits, pred and conf are not weighted.
+ * The normaliser stays inv_n -- NOT 1 / sum wc[y_p], PyTorch's `weight=` convention: inv_n is known before the launch, so there is
+ * no data-dependent pre-pass and no extra collective under data parallelism, and with "balanced" weights (sum_k f_k wc_k = 1 over
+ * the class frequencies f) the expected scale of L is that of the unweighted loss.
+ * NULL, or all K weights exactly 1.0f, or labels == NULL: the kernels of drs_classifier_loss, which do not multiply at all -- every
+ * output bit for bit.  A negative or non-finite weight: DRS_ERR_ARG (K <= 8 as above). */
+int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                                 const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                                 const unsigned char* acc_mask, float inv_n, const float* class_weights, float* logits,
+                                 unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
+                                 double* loss_partial, unsigned int* conf, void* stream);
+/* per-class pixel counts of n label bytes (the class-weight recipes): counts[k] += #{i : labels[i] == k}, k < K <= 8, leaving out
+ * labels equal to void_label (-1: none) or >= K; counts = K 64-bit counters on the device, ADDED to (integer atomics: exact and
+ * order-independent), so the maps of a pool accumulate over several calls.  n < 2^40. */
+int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_label, unsigned long long* counts, void* stream);
 
 /* fixed-order column sums (scratch: drs_colsum_scratch_doubles(ncols) doubles) / scalar sums used on the slabs above */
 int drs_rows_reduce_f32(const float* in, int nrows, int ncols, float* out, double* scratch, void* stream);
@@ -455,6 +474,12 @@ int drs_net_se_gate_finish(drs_net_t* net, int index, double count, void* stream
  * input-gradient chain on `stream`): mode -1 = by the library's rule (steps of fewer than 2^18 pixels; the default), 0 = never (a
  * host that must see every launch of the step on ITS stream), 1 = always.  Bitwise the same step in every mode. */
 int drs_net_set_two_streams(drs_net_t* net, int mode);
+/* class weights of drs_train_step's loss (drs_classifier_loss_weighted; the "scalars"[0] it leaves is then the weighted mean):
+ * host_w = HOST pointer to K = the net's class count finite, non-negative floats, copied into the handle; NULL clears them (the
+ * default: the unweighted step, bit for bit).  drs_forward and drs_forward_staged have no loss and ignore them.
+ * drs_net_get_class_weights: host_w (K_cap >= K floats) <- the weights in use, ones when none are set; *is_set (may be NULL) says which. */
+int drs_net_set_class_weights(drs_net_t* net, const float* host_w, int K);
+int drs_net_get_class_weights(const drs_net_t* net, float* host_w, int K_cap, int* is_set);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
