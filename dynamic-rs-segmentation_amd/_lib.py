@@ -55,6 +55,8 @@ SIGNATURES = {
                                  _p, _p]),
     "drs_classifier_loss_weighted": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _i, _p, _p,
                                           _p, _p, _p]),
+    "drs_classifier_loss_focal": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _i, _i, _p, _p,
+                                       _p, _p, _p]),
     "drs_label_histogram": (_i, [_p, _sz, _i, _i, _p, _p]),
     "drs_rows_reduce_f32": (_i, [_p, _i, _i, _p, _p, _p]),
     "drs_sum_f64": (_i, [_p, _i, _p, _p]),
@@ -110,6 +112,8 @@ SIGNATURES = {
     "drs_net_set_two_streams": (_i, [_p, _i]),
     "drs_net_set_class_weights": (_i, [_p, _p, _i]),
     "drs_net_get_class_weights": (_i, [_p, _p, _i, C.POINTER(_i)]),
+    "drs_net_set_focal_gamma": (_i, [_p, _f]),
+    "drs_net_get_focal_gamma": (_i, [_p, C.POINTER(_f)]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),
     "drs_net_timing_summary": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),

@@ -14,6 +14,8 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     refuses without it): the blocks are gated by the mean over the whole image, computed exactly in tiles (predict_tile_dense's se)
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
+  + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
+    of the focal loss, 0 or in (0, 8] (loops.train's focal_gamma)
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -157,6 +159,27 @@ def parse_class_weights(argv, num_classes=None):
     return (list(argv) if cw is None else rest), cw
 
 
+FOCAL_GAMMA_FLAG = "--focal-gamma"
+
+
+def parse_focal_gamma(argv):
+    """all flavours: the optional `--focal-gamma=G` (anywhere in argv; training).  Returns (argv without the flag, G as a float), or
+    (argv unchanged, None) without it.  A bare flag, a value that is not one number, 0 or finite in (0, 8], or the flag given twice,
+    raises ValueError."""
+    rest, g = [], None
+    for a in argv:
+        if a != FOCAL_GAMMA_FLAG and not a.startswith(FOCAL_GAMMA_FLAG + "="):
+            rest.append(a)
+            continue
+        if g is not None:
+            raise ValueError(FOCAL_GAMMA_FLAG + " given more than once")
+        try:
+            g = P.parse_focal_gamma(a[len(FOCAL_GAMMA_FLAG) + 1:])
+        except ValueError:
+            raise ValueError("%s: expected %s=G (one number, 0 or finite in (0, %g])" % (a, FOCAL_GAMMA_FLAG, P.MAX_FOCAL_GAMMA)) from None
+    return (list(argv) if g is None else rest), g
+
+
 def print_params(list_params, argv):
     print("+" * 97)
     for i in range(1, len(argv)):
@@ -216,6 +239,7 @@ def main(argv=None, device=None, comm=None):
         argv, dense_scales = parse_dense_scales(argv)
         argv, dense_se = parse_dense_se(argv)
         argv, class_weights = parse_class_weights(argv, 6)
+        argv, focal_gamma = parse_focal_gamma(argv)
     except ValueError as e:
         sys.exit(str(e))
     if dense_tta is not None and dense_tile is None:
@@ -230,6 +254,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(DENSE_TILE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
+    if focal_gamma is not None and argv[16] != "training":
+        sys.exit(FOCAL_GAMMA_FLAG + " applies to the training process only")
     if comm.rank == 0:
         print_params(ISPRS_PARAMS, argv)
     (input_path, output_path, former_model_path, tr, te, lr, wd, bs, niter, ref_crop, ref_stride, net_type,
@@ -279,7 +305,7 @@ def main(argv=None, device=None, comm=None):
                            testing_instances, lr_initial, batch_size, niter, weight_decay, mean_full, std_full, update_type,
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
-                           class_weights=class_weights)
+                           class_weights=class_weights, focal_gamma=focal_gamma)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -327,6 +353,7 @@ def main_coffee(argv=None, device=None, comm=None):
     argv = list(sys.argv if argv is None else argv)
     try:
         argv, class_weights = parse_class_weights(argv, 2)
+        argv, focal_gamma = parse_focal_gamma(argv)
     except ValueError as e:
         sys.exit(str(e))
     if len(argv) < len(COFFEE_PARAMS) + 1:
@@ -344,7 +371,7 @@ def main_coffee(argv=None, device=None, comm=None):
     return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
-                    quantize_f16=True, class_weights=class_weights)     # coffee:293: training patches pass through float16
+                    quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma)     # coffee:293: training patches pass through float16
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -354,6 +381,7 @@ def main_contest(argv=None, device=None, comm=None):
     argv = list(sys.argv if argv is None else argv)
     try:
         argv, class_weights = parse_class_weights(argv, 7)
+        argv, focal_gamma = parse_focal_gamma(argv)
     except ValueError as e:
         sys.exit(str(e))
     if len(argv) < len(CONTEST_PARAMS) + 1:
@@ -361,6 +389,8 @@ def main_contest(argv=None, device=None, comm=None):
     if comm.rank == 0:
         print_params(CONTEST_PARAMS, argv)
     path, output_path, current_model, lr, wd, bs, niter, crop, stride, net_type, dist, pv, update_type, operation = argv[1:15]
+    if focal_gamma is not None and operation != "train":
+        sys.exit(FOCAL_GAMMA_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
     resolve(net_type)
     acc, occ, chosen, probs = init_size_scores(dist, values, occur_init=1)            # contest:1275
@@ -377,7 +407,8 @@ def main_contest(argv=None, device=None, comm=None):
     if operation == "train":
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
-                        void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights)
+                        void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
+                        focal_gamma=focal_gamma)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

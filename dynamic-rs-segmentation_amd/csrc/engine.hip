@@ -191,6 +191,7 @@ struct drs_net {
   hipEvent_t ev_prep = nullptr;             // ... and back: the step's preparation launch (filter flips, zero fills) is done
   bool has_wc = false;                      // class weights of the training loss (drs_net_set_class_weights); none: the unweighted kernels
   float wc[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+  float focal_gamma = 0.f;                  // focusing parameter of the training loss (drs_net_set_focal_gamma); 0: no focal term
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -1073,6 +1074,20 @@ int drs_net_get_class_weights(const drs_net_t* n, float* host_w, int K_cap, int*
   return DRS_OK;
 }
 
+// Focusing parameter of the training loss (drs_train_step only): 0 or finite in (0, 8].  The step hands it to the classifier launch
+// by value (drs_classifier_loss_focal).
+int drs_net_set_focal_gamma(drs_net_t* n, float gamma) {
+  if (!n || !std::isfinite(gamma) || gamma < 0.f || gamma > 8.f) return DRS_ERR_ARG;
+  n->focal_gamma = gamma;
+  return DRS_OK;
+}
+
+int drs_net_get_focal_gamma(const drs_net_t* n, float* gamma) {
+  if (!n || !gamma) return DRS_ERR_ARG;
+  *gamma = n->focal_gamma;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1283,11 +1298,11 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   double* scratch = P.colsum_scratch;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
-    DRS_TRY(drs_classifier_loss_weighted(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
-                                         P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
-                                         (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                         n->has_wc ? n->wc : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr, P.pred, gfeat,
-                                         f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    DRS_TRY(drs_classifier_loss_focal(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+                                      P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                      (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
+                                      n->has_wc ? n->wc : nullptr, n->focal_gamma, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
+                                      P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
   }
   // the classifier's slab reductions (its kernel / bias gradients, the cross-entropy sum) and the L2 term: seven launches of ~5 us that
   // nothing needs before the end of the step -- in the two-stream backward pass they go to the filter-gradient stream (below), off

@@ -892,8 +892,13 @@ struct ClsArgs {
   int rows_per_block;
   int dma_span, nrows;       // classifier_dma_kernel: slab rows' worth of pixels per workgroup; slab rows in all
   float rcpS, rcpSS;
-  float wc[8];               // class weights of the weighted forms (WT), by value: scalar registers, no buffer and no load
+  float wc[8];               // class weights of the weighted and focal forms, by value: scalar registers, no buffer and no load
+  float gamma;               // focusing parameter of the focal forms (CLS_FOCAL), by value; the other forms do not read it
 };
+
+// Loss mode of the three classifier forms (template argument LM).  CLS_PLAIN: the cross-entropy, the code the kernels always had;
+// CLS_WEIGHTED: wc[y] * CE; CLS_FOCAL: wc[y] * (1 - p_t)^gamma * CE -- it always multiplies wc[y] in (ones when no weights are set).
+constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2;
 
 // The weight of a pixel's label: a register select over the eight by-value weights (a label outside [0, K) never enters the loss:
 // whatever comes out for it is multiplied into nothing)
@@ -905,10 +910,39 @@ __device__ __forceinline__ float cls_weight(const ClsArgs& a, int y) {
   return w;
 }
 
+// The per-pixel terms of the focal loss (include/drs.h) from the pieces of the max-subtracted softmax: so = the sum of
+// ex_k over k != y, ey = ex_y, inv = 1 / se, ce_log = CE in the form the cross-entropy kernels use (log se + max - logit_y).
+//   q  = 1 - p_t = so / se: a sum of positive terms, no cancellation however confident the pixel is
+//   m  = q^gamma = exp2(gamma log2 q), 0 at q = 0
+//   r  = CE / q = -log(1 - q) / q: for q < 1/8 its series 1 + q/2 + q^2/3 + ... + q^8/9 (next term q^9/10 < 8e-10), where the log form
+//        has lost its digits (CE -> 0 as the difference of numbers near 1) -- there CE is taken as q r too; else ce_log / q
+//   f  = m (1 + gamma p_t r) = q^g + g p_t q^(g-1) CE written so that 0 < g < 1 never forms inf * 0; f = 0 at q = 0
+// Out: q, m, ce (the loss term is wc[y] m ce) and f (the logit gradient is wc[y] f (P_k - [k == y]) inv_n).
+__device__ __forceinline__ void focal_terms(float gamma, float so, float ey, float inv, float ce_log, float& q, float& m, float& ce,
+                                            float& f) {
+  q = fminf(so * inv, 1.f);
+  const float pt = ey * inv;
+  const bool small = q < 0.125f;
+  float r = 1.f / 9.f;
+  r = r * q + 1.f / 8.f;
+  r = r * q + 1.f / 7.f;
+  r = r * q + 1.f / 6.f;
+  r = r * q + 1.f / 5.f;
+  r = r * q + 1.f / 4.f;
+  r = r * q + 1.f / 3.f;
+  r = r * q + 1.f / 2.f;
+  r = r * q + 1.f;
+  ce = small ? q * r : ce_log;
+  r = small ? r : ce_log / q;
+  m = q > 0.f ? exp2f(gamma * log2f(q)) : 0.f;
+  f = m * (1.f + gamma * pt * r);
+}
+
 // CI = C / 64; KM = class slots carried per lane: the exact class count for the reference's 2 / 6 / 7 classes (no masked
-// slots, no wasted multiplies), 8 otherwise.  WT (all three forms): class-weighted loss, L = inv_n * sum wc[y] CE -- the pixel's
-// weight scales the logit gradients (through inv_n) and its loss term; without WT the code is what it was, no multiply by one
-template <int CI, int KM, bool WT>
+// slots, no wasted multiplies), 8 otherwise.  LM (all three forms): CLS_WEIGHTED, class-weighted loss, L = inv_n * sum wc[y] CE -- the
+// pixel's weight scales the logit gradients (through inv_n) and its loss term; CLS_FOCAL: the focal factor f (focal_terms) joins the
+// weight in that slot and m the loss term; CLS_PLAIN: the code is what it was, no multiply by one
+template <int CI, int KM, int LM>
 __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
   __shared__ float red[4][CI * 64 * KM];
   __shared__ float redb[4][KM];
@@ -1004,15 +1038,32 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
     const float inv = 1.0f / se;
     float ly = 0.f;
     float dl[KM];
+    constexpr bool WT = LM != CLS_PLAIN;
     const float wy = WT ? cls_weight<KM>(a, y) : 1.f;
-    const float sc = WT ? a.inv_n * wy : a.inv_n;
+    if constexpr (LM == CLS_FOCAL) {
+      // every lane holds all the classes: so in ascending class order, then a few scalar-like operations per pixel
+      float so = 0.f;
 #pragma unroll
-    for (int k = 0; k < KM; ++k) {
-      const float pk = ex[k] * inv;
-      dl[k] = in_loss && k < K ? (pk - (k == y ? 1.f : 0.f)) * sc : 0.f;
-      if (k == y) ly = lg[k];
+      for (int k = 0; k < KM; ++k) {
+        so += k == y ? 0.f : ex[k];
+        if (k == y) ly = lg[k];
+      }
+      float q, m, ce, f;
+      focal_terms(a.gamma, so, __expf(ly - mx), inv, __logf(se) + mx - ly, q, m, ce, f);      // (ex_y again: the same bits as ex[y])
+      const float sc = a.inv_n * wy * f;
+#pragma unroll
+      for (int k = 0; k < KM; ++k) dl[k] = in_loss && k < K ? (k == y ? -q : ex[k] * inv) * sc : 0.f;      // P_y - 1 = -q, uncancelled
+      if (in_loss) lsum += (double)wy * ((double)m * (double)ce);
+    } else {
+      const float sc = WT ? a.inv_n * wy : a.inv_n;
+#pragma unroll
+      for (int k = 0; k < KM; ++k) {
+        const float pk = ex[k] * inv;
+        dl[k] = in_loss && k < K ? (pk - (k == y ? 1.f : 0.f)) * sc : 0.f;
+        if (k == y) ly = lg[k];
+      }
+      if (in_loss) lsum += WT ? (double)wy * (double)(__logf(se) + mx - ly) : (double)(__logf(se) + mx - ly);
     }
-    if (in_loss) lsum += WT ? (double)wy * (double)(__logf(se) + mx - ly) : (double)(__logf(se) + mx - ly);
     if (a.gfeat) {
 #pragma unroll
       for (int gi = 0; gi < CI / V; ++gi) {
@@ -1080,6 +1131,24 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
   }
 }
 
+// The focal terms in the two matrix-core forms: a lane holds two classes (cls0, cls1) of its pixel, the pixel's four lanes are
+// l, l ^ 16, l ^ 32, l ^ 48.  so (the sum of ex_k over k != y) and the label's logit travel over them by the exchange pattern that forms
+// se, so that every lane of the pixel gets the same bits (the logit sum has one non-zero term: exact); ex_y is recomputed from it,
+// the same instruction on the same operands as in the lane that owns class y.
+struct FocalPixel { float q, m, ce, f; };
+__device__ __forceinline__ FocalPixel focal_pixel(float gamma, int y, int cls0, int cls1, float ex0, float ex1, float lg0, float lg1,
+                                                  float mx, float se, float inv) {
+  float so = (cls0 == y ? 0.f : ex0) + (cls1 == y ? 0.f : ex1);
+  so += __shfl_xor(so, 16);
+  so += __shfl_xor(so, 32);
+  float ly = cls0 == y ? lg0 : (cls1 == y ? lg1 : 0.f);
+  ly += __shfl_xor(ly, 16);
+  ly += __shfl_xor(ly, 32);
+  FocalPixel o;
+  focal_terms(gamma, so, __expf(ly - mx), inv, __logf(se) + mx - ly, o.q, o.m, o.ce, o.f);
+  return o;
+}
+
 // The same classifier block on the matrix cores (isprs:1024-1031 is a true dense contraction: [M x C] . [C x K]): three
 // products per tile of 16 pixels, all on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains), the class dimension padded to 16 / 8:
 //   logits^T [class][px] = W^T [class][c] . feat^T [c][px]            (k = channel;  C / 4 MFMAs)
@@ -1094,7 +1163,7 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
 // instruction for the first (k = channel on l >> 4), 4 pixels x 256 B for the third (k = pixel on l >> 4) -- the second time
 // out of L2.  One workgroup = 4 waves, each walking its own 16-pixel tiles of the workgroup's pixel range; the filter sits in
 // LDS in the two operand arrangements.  Sums over pixels (dW, db, the loss) stay per workgroup and are added in wave order.
-template <int CQ, bool TRAIN, bool WT>
+template <int CQ, bool TRAIN, int LM>
 __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
   constexpr int C = CQ * 64, NJ = C / 16, KP = 16;
   __shared__ __attribute__((aligned(16))) float W1[C * KP];      // [c / 16][(c % 16) / 4][row i <-> class (i >> 2) + 4 (i & 3)][c % 4]: A operand of the first product
@@ -1194,12 +1263,22 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     se += __shfl_xor(se, 16);                       // (a + b == b + a bit for bit: every lane of the pixel gets the same sum)
     se += __shfl_xor(se, 32);
     const float inv = 1.0f / se;
+    constexpr bool WT = LM != CLS_PLAIN;
     const float wy = WT ? cls_weight(a, y) : 1.f;
-    const float sc = WT ? a.inv_n * wy : a.inv_n;
-    const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
-    const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
-    if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
-    if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
+    float dl0, dl1;
+    if constexpr (LM == CLS_FOCAL) {
+      const FocalPixel fp = focal_pixel(a.gamma, y, cls0, cls1, ex0, ex1, lg0, lg1, mx, se, inv);
+      const float sc = a.inv_n * wy * fp.f;
+      dl0 = (in_loss && cls0 < K) ? (cls0 == y ? -fp.q : ex0 * inv) * sc : 0.f;      // P_y - 1 = -q, uncancelled
+      dl1 = (in_loss && cls1 < K) ? (cls1 == y ? -fp.q : ex1 * inv) * sc : 0.f;
+      if (in_loss && (cls0 == y || cls1 == y)) lsum += (double)wy * ((double)fp.m * (double)fp.ce);
+    } else {
+      const float sc = WT ? a.inv_n * wy : a.inv_n;
+      dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
+      dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
+      if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
+      if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
+    }
     db0 += dl0;
     db1 += dl1;
     if (!a.gfeat) continue;
@@ -1290,7 +1369,7 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
 // hidden behind a whole tile of arithmetic.  Every vector-memory operation inside the loop is counted by hand: the label / mask
 // bytes are inline-asm loads waited for with vmcnt(#DMA instructions), the DMA itself with vmcnt(#feature-gradient stores).
 // Products, orientations, class permutation and every sum are those of classifier_mfma_kernel: results are bitwise the same.
-template <int CQ, bool TRAIN, bool WT>
+template <int CQ, bool TRAIN, int LM>
 __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int C = CQ * 64, NJ = C / 16, KP = 16, NI = 4 * CQ;      // NI: 1-KiB DMA instructions per tile
@@ -1418,12 +1497,23 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       const float inv = 1.0f / se;
       // (the weight select: vector-ALU work of the softmax section, after the logits' MFMAs have been issued and before the filter
       // gradient's -- no MFMA waits for it)
+      // (the focal factor likewise: its four cross-lane moves and its arithmetic sit here, in the softmax section)
+      constexpr bool WT = LM != CLS_PLAIN;
       const float wy = WT ? cls_weight(a, y) : 1.f;
-      const float sc = WT ? a.inv_n * wy : a.inv_n;
-      const float dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
-      const float dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
-      if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
-      if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
+      float dl0, dl1;
+      if constexpr (LM == CLS_FOCAL) {
+        const FocalPixel fp = focal_pixel(a.gamma, y, cls0, cls1, ex0, ex1, lg0, lg1, mx, se, inv);
+        const float sc = a.inv_n * wy * fp.f;
+        dl0 = (in_loss && cls0 < K) ? (cls0 == y ? -fp.q : ex0 * inv) * sc : 0.f;
+        dl1 = (in_loss && cls1 < K) ? (cls1 == y ? -fp.q : ex1 * inv) * sc : 0.f;
+        if (in_loss && (cls0 == y || cls1 == y)) lsum += (double)wy * ((double)fp.m * (double)fp.ce);
+      } else {
+        const float sc = WT ? a.inv_n * wy : a.inv_n;
+        dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
+        dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
+        if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
+        if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
+      }
       db0 += dl0;
       db1 += dl1;
       if (a.gfeat) {
@@ -1814,13 +1904,16 @@ int drs_debug_cls_variant(int v) { const int old = g_cls_variant; if (v >= 0) g_
 #endif
 
 // class_weights: HOST pointer to K floats or NULL.  NULL, all weights exactly 1, or no labels (inference): the unweighted kernels,
-// which do not multiply at all (bit for bit drs_classifier_loss); otherwise the WT instantiations with the weights by value.
-int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
-                                 const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
-                                 const unsigned char* acc_mask, float inv_n, const float* class_weights, float* logits,
-                                 unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
-                                 double* loss_partial, unsigned int* conf, void* stream) {
+// which do not multiply at all (bit for bit drs_classifier_loss); otherwise the CLS_WEIGHTED instantiations with the weights by
+// value.  focal_gamma: 0 is not a focal launch -- the dispatch above, unchanged; in (0, 8] with labels the CLS_FOCAL instantiations,
+// which carry gamma by value and multiply the weights in, ones when none are set.
+int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                              float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
+                              float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
   if (!feat || !w || !bias || K < 1 || K > 8 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
+  if (!std::isfinite(focal_gamma) || focal_gamma < 0.f || focal_gamma > 8.f) return DRS_ERR_ARG;
   bool wt = false;
   if (class_weights)
     for (int k = 0; k < K; ++k) {
@@ -1828,6 +1921,8 @@ int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld,
       wt = wt || class_weights[k] != 1.0f;
     }
   wt = wt && labels;
+  const bool focal = focal_gamma > 0.f && labels;
+  const int lm = focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
   const long long M = (long long)B * S * S;
   if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
   if (labels && !loss_partial) return DRS_ERR_ARG;
@@ -1840,6 +1935,7 @@ int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld,
   a.loss_partial = loss_partial; a.conf = conf;
   a.rcpS = 1.0f / (float)S; a.rcpSS = 1.0f / (float)(S * S);
   for (int k = 0; k < 8; ++k) a.wc[k] = wt && k < K ? class_weights[k] : 1.f;
+  a.gamma = focal ? focal_gamma : 0.f;
   const int nblk = drs_classifier_rows(B, S);
   a.rows_per_block = (int)(((M + nblk - 1) / nblk + 63) / 64 * 64);      // whole 16-pixel tiles per wave; trailing workgroups may be empty
   hipStream_t st = (hipStream_t)stream;
@@ -1853,24 +1949,27 @@ int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld,
   if (mfma && C / 64 <= 4 && g_cls_variant != 2 && (g_cls_variant == 3 || M >= (1 << 18))) {
     a.dma_span = (nblk + 255) / 256;
     const int ndma = (nblk + a.dma_span - 1) / a.dma_span;
-#define DRS_CLS_D(cq) do { if (wt) DRS_LAUNCH((classifier_dma_kernel<cq, true, true>), dim3(ndma), dim3(256), 0, st, a); \
-                           else if (labels) DRS_LAUNCH((classifier_dma_kernel<cq, true, false>), dim3(ndma), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_dma_kernel<cq, false, false>), dim3(ndma), dim3(256), 0, st, a); } while (0)
+#define DRS_CLS_D(cq) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_FOCAL>), dim3(ndma), dim3(256), 0, st, a); \
+                           else if (wt) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_WEIGHTED>), dim3(ndma), dim3(256), 0, st, a); \
+                           else if (labels) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_PLAIN>), dim3(ndma), dim3(256), 0, st, a); \
+                           else DRS_LAUNCH((classifier_dma_kernel<cq, false, CLS_PLAIN>), dim3(ndma), dim3(256), 0, st, a); } while (0)
     switch (C / 64) { case 1: DRS_CLS_D(1); break; case 2: DRS_CLS_D(2); break; case 3: DRS_CLS_D(3); break; default: DRS_CLS_D(4); break; }
 #undef DRS_CLS_D
     return DRS_LAUNCH_CHECK();
   }
   if (mfma) {
-#define DRS_CLS_M(cq) do { if (wt) DRS_LAUNCH((classifier_mfma_kernel<cq, true, true>), dim3(nblk), dim3(256), 0, st, a); \
-                           else if (labels) DRS_LAUNCH((classifier_mfma_kernel<cq, true, false>), dim3(nblk), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_mfma_kernel<cq, false, false>), dim3(nblk), dim3(256), 0, st, a); } while (0)
+#define DRS_CLS_M(cq) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_FOCAL>), dim3(nblk), dim3(256), 0, st, a); \
+                           else if (wt) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_WEIGHTED>), dim3(nblk), dim3(256), 0, st, a); \
+                           else if (labels) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); \
+                           else DRS_LAUNCH((classifier_mfma_kernel<cq, false, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); } while (0)
     switch (C / 64) { case 1: DRS_CLS_M(1); break; case 2: DRS_CLS_M(2); break; case 3: DRS_CLS_M(3); break; case 4: DRS_CLS_M(4); break;
                       case 5: DRS_CLS_M(5); break; case 6: DRS_CLS_M(6); break; default: DRS_CLS_M(7); break; }
 #undef DRS_CLS_M
     return DRS_LAUNCH_CHECK();
   }
-#define DRS_CLS_CASE(ci, km) do { if (wt) DRS_LAUNCH((classifier_loss_kernel<ci, km, true>), dim3(nblk), dim3(256), 0, st, a); \
-                                  else DRS_LAUNCH((classifier_loss_kernel<ci, km, false>), dim3(nblk), dim3(256), 0, st, a); } while (0)
+#define DRS_CLS_CASE(ci, km) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_FOCAL>), dim3(nblk), dim3(256), 0, st, a); \
+                                  else if (wt) DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_WEIGHTED>), dim3(nblk), dim3(256), 0, st, a); \
+                                  else DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); } while (0)
 #define DRS_CLS_KM(km) switch (C / 64) { case 1: DRS_CLS_CASE(1, km); break; case 2: DRS_CLS_CASE(2, km); break; case 3: DRS_CLS_CASE(3, km); break; \
     case 4: DRS_CLS_CASE(4, km); break; case 5: DRS_CLS_CASE(5, km); break; case 6: DRS_CLS_CASE(6, km); break; default: DRS_CLS_CASE(7, km); break; }
   if (K == 2) DRS_CLS_KM(2) else if (K == 6) DRS_CLS_KM(6) else if (K == 7) DRS_CLS_KM(7) else DRS_CLS_KM(8)
@@ -1884,8 +1983,17 @@ int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff
                         const unsigned char* acc_mask, float inv_n, float* logits, unsigned char* pred, float* gfeat,
                         int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial,
                         unsigned int* conf, void* stream) {
-  return drs_classifier_loss_weighted(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, nullptr, logits, pred,
-                                      gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
+  return drs_classifier_loss_focal(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, nullptr, 0.f, logits, pred,
+                                   gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
+}
+
+int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                                 const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                                 const unsigned char* acc_mask, float inv_n, const float* class_weights, float* logits,
+                                 unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
+                                 double* loss_partial, unsigned int* conf, void* stream) {
+  return drs_classifier_loss_focal(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, class_weights, 0.f, logits,
+                                   pred, gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
 }
 
 // counts[k] += number of labels equal to k, k < K, other than void_label (-1: none); counts: K 64-bit counters (device), ADDED to

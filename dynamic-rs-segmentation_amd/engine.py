@@ -302,6 +302,17 @@ class EngineNet(DilatedNet):
         _lib.call("drs_net_get_class_weights", self.h, w.ctypes.data_as(C.c_void_p), int(w.size), C.byref(is_set))
         return w if is_set.value else None
 
+    def _focal_gamma_changed(self):
+        """hand gamma to the library's net (drs_net_set_focal_gamma: the step passes it to its classifier launch by value)"""
+        _lib.call("drs_net_set_focal_gamma", self.h, float(self._focal_gamma))
+
+    @property
+    def focal_gamma(self):
+        """the focusing parameter the library's net holds (drs_net_get_focal_gamma); 0.0: no focal term"""
+        g = C.c_float()
+        _lib.call("drs_net_get_focal_gamma", self.h, C.byref(g))
+        return float(g.value)
+
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always
         (drs_net_set_two_streams; bitwise the same step in every mode)"""

@@ -90,11 +90,35 @@ def load_class_weights(net, former_model_path):
             print("Class weights (restored from " + path + "): weights " + _weights_str(net.class_weights))
 
 
+FOCAL_GAMMA_SIDE = "focal_gamma_step_"
+
+
+def save_focal_gamma(net, output_path, step):
+    """the focusing parameter of the training loss, when set (> 0), as the side file `focal_gamma_step_<step>.npy` beside the size
+    scores: one float32 (state of the run, not of the model, as the class weights are)"""
+    g = float(getattr(net, "focal_gamma", 0.0) or 0.0)
+    if g > 0.0:
+        np.save(output_path + FOCAL_GAMMA_SIDE + str(step) + ".npy", np.asarray(g, dtype=np.float32))
+
+
+def load_focal_gamma(net, former_model_path):
+    """set the gamma that save_focal_gamma left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep:
+        return
+    path = head + FOCAL_GAMMA_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        net.set_focal_gamma(float(np.load(path)))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Focal loss (restored from " + path + "): gamma " + "{:.6g}".format(net.focal_gamma))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
     """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights
-    of the loss when set (save_class_weights)."""
+    and the focal gamma of the loss when set (save_class_weights, save_focal_gamma)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
+    save_focal_gamma(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -114,6 +138,7 @@ def load_checkpoint(net, former_model_path):
     with np.load(path) as d:
         net.load_state_dict({k: d[k] for k in d.files})
     load_class_weights(net, former_model_path)
+    load_focal_gamma(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -179,6 +204,20 @@ def setup_class_weights(net, pool, num_classes, class_weights, comm, say, void_l
         " weights " + _weights_str(wc) +
         ("" if restored is None or restored.tobytes() == wc.tobytes() else " -- replacing the weights restored from the checkpoint, " + _weights_str(restored)))
     return wc
+
+
+def setup_focal_gamma(net, focal_gamma, comm, say):
+    """The focusing parameter of a training run (train's `focal_gamma`; patches.check_focal_gamma): every rank must hold the same one,
+    asserted once over the ranks on its float32 bits.  Given, it replaces a gamma restored from a checkpoint's side file.  One log
+    line names it; gamma = 0 on a run that restored none is today's run and says nothing."""
+    g = P.check_focal_gamma(focal_gamma)
+    comm.agree([int(np.asarray(g, dtype=np.float32).view(np.uint32))], "focal gamma")
+    restored = float(net.focal_gamma)
+    net.set_focal_gamma(g)
+    if g > 0.0 or restored != g:
+        say("Focal loss: gamma " + "{:.6g}".format(g) + (" (the loss is wc[y] (1 - p_t)^gamma CE)" if g > 0.0 else " (off: the cross-entropy)") +
+            ("" if restored == 0.0 or restored == g else " -- replacing the gamma restored from the checkpoint, " + "{:.6g}".format(restored)))
+    return g
 
 
 # ------------------------------------------------------------------------------------------------- data parallelism
@@ -252,12 +291,17 @@ def train(training_data, training_labels, training_class_distribution, training_
           mean_full, std_full, update_type, distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values,
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
-          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None):
+          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
     update_type="loss", is then the WEIGHTED one (inv_n * sum wc[y] CE + the L2 term); accuracies, confusion matrices and validation
-    are not weighted.  Given here, it replaces weights restored from a checkpoint's side file; None keeps those."""
+    are not weighted.  Given here, it replaces weights restored from a checkpoint's side file; None keeps those.
+    focal_gamma (opt-in; None or 0 = today's run, bit for bit): the focusing parameter of the focal loss, finite in (0, 8]
+    (setup_focal_gamma, DilatedNet.set_focal_gamma; with or without class_weights).  The loss this loop prints, and that feeds the
+    size scores with update_type="loss", is then the MODULATED one (inv_n * sum wc[y] (1 - p_t)^gamma CE + the L2 term); accuracies,
+    confusion matrices and validation are not modulated.  Given here, it replaces a gamma restored from a checkpoint's side file;
+    None keeps that."""
     comm = comm or NoComm()
     say = (lambda *a: print(*a)) if comm.rank == 0 else (lambda *a: None)
     say(BatchColors.OKGREEN + "TRAINING" + BatchColors.ENDC)
@@ -298,6 +342,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         say("Model totally initialized!")
     if class_weights is not None:
         setup_class_weights(net, train_pool, num_classes, class_weights, comm, say)
+    if focal_gamma is not None:
+        setup_focal_gamma(net, focal_gamma, comm, say)
 
     it = 0
     epoch_mean = 0.0

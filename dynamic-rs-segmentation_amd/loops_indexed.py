@@ -84,9 +84,12 @@ def create_mean_and_std_contest(data, class_distribution, crop_size):
 def train(training_data, training_labels, test_data, test_labels, class_distribution, mean_full, std_full, output_path,
           current_model, lr_initial, weight_decay, batch_size, niter, net_type, distribution_type, update_type, patch_acc_loss,
           patch_occur, patch_chosen_values, probs, values, *, num_classes, void_label=-1, side_names=None, device="cuda:0",
-          comm=None, display_step=50, quiet_sizes=False, quantize_f16=False, flavour="isprs", class_weights=None):
+          comm=None, display_step=50, quiet_sizes=False, quantize_f16=False, flavour="isprs", class_weights=None,
+          focal_gamma=None):
     """class_weights (opt-in; None = the reference's loss): "balanced" | "median" | K numbers, as loops.train takes them; the counts of
-    the recipes leave the void label out.  The printed loss and the loss-based size scores are then the weighted ones."""
+    the recipes leave the void label out.  The printed loss and the loss-based size scores are then the weighted ones.
+    focal_gamma (opt-in; None or 0 = today's run): the focusing parameter of the focal loss, as loops.train takes it; the printed loss
+    and the loss-based size scores are then the modulated ones."""
     comm = comm or NoComm()
     if batch_size % comm.world:
         raise ValueError("batch_size must be divisible by the number of ranks")
@@ -119,11 +122,14 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
         say("Model totally initialized!")
     if class_weights is not None:
         loops.setup_class_weights(net, train_pool, num_classes, class_weights, comm, say, void_label if void_label >= 0 else None)
+    if focal_gamma is not None:
+        loops.setup_focal_gamma(net, focal_gamma, comm, say)
 
     def save(step):
         if comm.rank == 0:
             np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
             loops.save_class_weights(net, output_path, step)
+            loops.save_focal_gamma(net, output_path, step)
             if sized:
                 np.save(output_path + side[0] + str(step) + ".npy", patch_acc_loss)
                 np.save(output_path + side[1] + str(step) + ".npy", patch_occur)

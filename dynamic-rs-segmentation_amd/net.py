@@ -152,6 +152,7 @@ class DilatedNet(object):
         self.lr_decay_factor = lr_decay_factor      # 0.5 isprs:1686; 0.1 coffee:1228, contest:1021
         self.global_step = 0
         self._class_weights = None
+        self._focal_gamma = 0.0
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -238,6 +239,26 @@ class DilatedNet(object):
     def class_weights(self):
         """the weights in use (float32 [K], a copy), or None"""
         return None if self._class_weights is None else self._class_weights.copy()
+
+    # ------------------------------------------------------------------ focal loss (the focusing parameter of the training loss)
+    def set_focal_gamma(self, gamma):
+        """Focal training loss (opt-in): gamma = 0 / None (the cross-entropy step, bit for bit) or finite in (0, 8].
+        train_step's data term becomes inv_n * sum over the pixels in the loss of wc[y] * (1 - p_t)^gamma * CE with p_t the softmax
+        probability of the label (wc: the class weights, ones when none are set; inv_n unchanged), and the gradients follow.  The loss
+        train_step reports is then the MODULATED one; logits, pred, the confusion matrix, the L2 term and every forward pass are not
+        modulated.  State of the training run, not of the model: loops.save_checkpoint keeps it in a side file, the TensorFlow
+        checkpoint does not hold it, and an inference twin does not copy it."""
+        from .patches import check_focal_gamma
+        self._focal_gamma = 0.0 if gamma is None else check_focal_gamma(gamma)
+        self._focal_gamma_changed()
+
+    def _focal_gamma_changed(self):
+        pass
+
+    @property
+    def focal_gamma(self):
+        """the focusing parameter in use (a float32 value as a Python float); 0.0: no focal term"""
+        return self._focal_gamma
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

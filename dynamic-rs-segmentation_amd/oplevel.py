@@ -338,9 +338,9 @@ class OpLevelNet(DilatedNet):
         gfeat, ldg, cg = self.gbuf[p.feat], p.buffers[p.feat][0], 0
         self.conf.zero_()
         wc = self._class_weights          # (HOST pointer: the library copies the K floats into the kernel arguments; None: unweighted)
-        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_weighted", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
+        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_focal", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
                 self.params[woff:].data_ptr(), self.params[boff:].data_ptr(), _ptr(self.labels), _ptr(self.loss_mask) if use_loss_mask else None,
-                  _ptr(self.acc_mask) if use_acc_mask else None, 1.0 / n_glob, None if wc is None else wc.ctypes.data,
+                  _ptr(self.acc_mask) if use_acc_mask else None, 1.0 / n_glob, None if wc is None else wc.ctypes.data, float(self._focal_gamma),
                   _ptr(self.logits) if want_logits else None,
                   _ptr(self.pred), _ptr(gfeat), ldg, cg, _ptr(self.dw_partial), _ptr(self.db_partial), _ptr(self.loss_partial),
                   _ptr(self.conf), st)

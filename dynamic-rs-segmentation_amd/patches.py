@@ -287,6 +287,34 @@ def parse_class_weights(text):
     return tuple(vals)
 
 
+# ------------------------------------------------------------------- focal loss of the training loss
+MAX_FOCAL_GAMMA = 8.0    # the classifier kernels take gamma = 0 (no focal term) or a finite gamma in (0, 8] (include/drs.h)
+
+
+def check_focal_gamma(g):
+    """The focusing parameter of the focal training loss as the kernels take it: a Python float holding a float32 value,
+    0 (no focal term: the cross-entropy kernels, bit for bit) or finite in (0, 8].  Negative, NaN, infinite, above 8 or not a number:
+    ValueError."""
+    if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, float, np.integer, np.floating)):
+        raise ValueError("focal gamma %r: expected a number, 0 or in (0, %g]" % (g, MAX_FOCAL_GAMMA))
+    v = float(g)
+    if not math.isfinite(v) or v < 0.0 or v > MAX_FOCAL_GAMMA:
+        raise ValueError("focal gamma %r: expected 0 or a finite value in (0, %g]" % (g, MAX_FOCAL_GAMMA))
+    return float(np.float32(v))
+
+
+def parse_focal_gamma(text):
+    """The value of the command lines' --focal-gamma option: one number as check_focal_gamma takes it.  Anything else raises
+    ValueError."""
+    try:
+        v = float(text) if text and text == text.strip() else None
+    except ValueError:
+        v = None
+    if v is None:
+        raise ValueError("focal gamma %r: expected one number, 0 or in (0, %g]" % (text, MAX_FOCAL_GAMMA))
+    return check_focal_gamma(v)
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

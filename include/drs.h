@@ -233,6 +233,23 @@ int drs_classifier_loss_weighted(const float* feat, int B, int S, int P, int ld,
                                  const unsigned char* acc_mask, float inv_n, const float* class_weights, float* logits,
                                  unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
                                  double* loss_partial, unsigned int* conf, void* stream);
+/* The same with the focal modulation (opt-in; Lin et al., "Focal loss for dense object detection").  focal_gamma is
+ * the focusing parameter: 0, or finite in (0, 8]; anything else is DRS_ERR_ARG.  With wc the class weights (ones when class_weights
+ * is NULL), P = softmax(logits_p) in the max-subtracted form (ex_k = exp(logit_k - max), se = sum_k ex_k), for a pixel in the loss:
+ *     p_t = P[y]          q = 1 - p_t, formed as (sum over k != y, ascending, of ex_k) / se -- never as 1 - p_t, which cancels
+ *     CE  = -log p_t      m = q^gamma, 0 at q == 0
+ *     L   = inv_n * sum over the pixels in the loss of wc[y] * m * CE                      (the alpha-balanced focal loss)
+ *     f   = m * (1 + gamma * p_t * r),  r = CE / q, taken as its limit 1 as q -> 0         (= q^g + g p_t q^(g-1) CE, no inf * 0)
+ *     d L / d logit_k = wc[y] * f * (P_k - [k == y]) * inv_n
+ * gfeat, dw_partial, db_partial follow from that gradient as in drs_classifier_loss; loss_partial is the fp64 sum of wc[y] * m * CE.
+ * logits, pred and conf are not modulated.  inv_n stays the normaliser it is (not 1 / sum of modulators): no pre-pass, no collective.
+ * focal_gamma == 0 (or labels == NULL) is NOT a focal launch: it is drs_classifier_loss_weighted, every output bit for bit.  With
+ * focal_gamma > 0 the focal instantiations run and multiply wc[y] in even when it is one. */
+int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                              float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
+                              float* db_partial, double* loss_partial, unsigned int* conf, void* stream);
 /* per-class pixel counts of n label bytes (the class-weight recipes): counts[k] += #{i : labels[i] == k}, k < K <= 8, leaving out
  * labels equal to void_label (-1: none) or >= K; counts = K 64-bit counters on the device, ADDED to (integer atomics: exact and
  * order-independent), so the maps of a pool accumulate over several calls.  n < 2^40. */
@@ -480,6 +497,11 @@ int drs_net_set_two_streams(drs_net_t* net, int mode);
  * drs_net_get_class_weights: host_w (K_cap >= K floats) <- the weights in use, ones when none are set; *is_set (may be NULL) says which. */
 int drs_net_set_class_weights(drs_net_t* net, const float* host_w, int K);
 int drs_net_get_class_weights(const drs_net_t* net, float* host_w, int K_cap, int* is_set);
+/* focusing parameter of drs_train_step's loss (drs_classifier_loss_focal; the "scalars"[0] it leaves is then the focal loss, with
+ * the class weights when set): 0 (the default: the cross-entropy step, bit for bit) or finite in (0, 8], kept in the handle; anything
+ * else DRS_ERR_ARG.  drs_forward and drs_forward_staged have no loss and ignore it. */
+int drs_net_set_focal_gamma(drs_net_t* net, float gamma);
+int drs_net_get_focal_gamma(const drs_net_t* net, float* gamma);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
