@@ -11,6 +11,7 @@
 // accesses), consecutive lanes own consecutive channel quads, so every wave access is a run of full cache lines.
 #include "drs_common.hpp"
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -938,6 +939,21 @@ __device__ __forceinline__ void focal_terms(float gamma, float so, float ey, flo
   f = m * (1.f + gamma * pt * r);
 }
 
+// What a loss mode does to one pixel, once for all three forms: the scale of its logit gradients (P_k - [k == y]) and its addend to
+// the loss sum.  wy = wc[y]; f, m, ce: focal_terms (CLS_FOCAL reads nothing else); ly = the label's logit.
+template <int LM>
+__device__ __forceinline__ float cls_grad_scale(float inv_n, float wy, float f) {
+  if constexpr (LM == CLS_FOCAL) return inv_n * wy * f;
+  else if constexpr (LM == CLS_WEIGHTED) return inv_n * wy;
+  else return inv_n;
+}
+template <int LM>
+__device__ __forceinline__ double cls_loss_term(float wy, float se, float mx, float ly, float m, float ce) {
+  if constexpr (LM == CLS_FOCAL) return (double)wy * ((double)m * (double)ce);
+  else if constexpr (LM == CLS_WEIGHTED) return (double)wy * (double)(__logf(se) + mx - ly);
+  else return (double)(__logf(se) + mx - ly);
+}
+
 // CI = C / 64; KM = class slots carried per lane: the exact class count for the reference's 2 / 6 / 7 classes (no masked
 // slots, no wasted multiplies), 8 otherwise.  LM (all three forms): CLS_WEIGHTED, class-weighted loss, L = inv_n * sum wc[y] CE -- the
 // pixel's weight scales the logit gradients (through inv_n) and its loss term; CLS_FOCAL: the focal factor f (focal_terms) joins the
@@ -1050,19 +1066,19 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
       }
       float q, m, ce, f;
       focal_terms(a.gamma, so, __expf(ly - mx), inv, __logf(se) + mx - ly, q, m, ce, f);      // (ex_y again: the same bits as ex[y])
-      const float sc = a.inv_n * wy * f;
+      const float sc = cls_grad_scale<LM>(a.inv_n, wy, f);
 #pragma unroll
       for (int k = 0; k < KM; ++k) dl[k] = in_loss && k < K ? (k == y ? -q : ex[k] * inv) * sc : 0.f;      // P_y - 1 = -q, uncancelled
-      if (in_loss) lsum += (double)wy * ((double)m * (double)ce);
+      if (in_loss) lsum += cls_loss_term<LM>(wy, se, mx, ly, m, ce);
     } else {
-      const float sc = WT ? a.inv_n * wy : a.inv_n;
+      const float sc = cls_grad_scale<LM>(a.inv_n, wy, 0.f);
 #pragma unroll
       for (int k = 0; k < KM; ++k) {
         const float pk = ex[k] * inv;
         dl[k] = in_loss && k < K ? (pk - (k == y ? 1.f : 0.f)) * sc : 0.f;
         if (k == y) ly = lg[k];
       }
-      if (in_loss) lsum += WT ? (double)wy * (double)(__logf(se) + mx - ly) : (double)(__logf(se) + mx - ly);
+      if (in_loss) lsum += cls_loss_term<LM>(wy, se, mx, ly, 0.f, 0.f);
     }
     if (a.gfeat) {
 #pragma unroll
@@ -1131,24 +1147,6 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
   }
 }
 
-// The focal terms in the two matrix-core forms: a lane holds two classes (cls0, cls1) of its pixel, the pixel's four lanes are
-// l, l ^ 16, l ^ 32, l ^ 48.  so (the sum of ex_k over k != y) and the label's logit travel over them by the exchange pattern that forms
-// se, so that every lane of the pixel gets the same bits (the logit sum has one non-zero term: exact); ex_y is recomputed from it,
-// the same instruction on the same operands as in the lane that owns class y.
-struct FocalPixel { float q, m, ce, f; };
-__device__ __forceinline__ FocalPixel focal_pixel(float gamma, int y, int cls0, int cls1, float ex0, float ex1, float lg0, float lg1,
-                                                  float mx, float se, float inv) {
-  float so = (cls0 == y ? 0.f : ex0) + (cls1 == y ? 0.f : ex1);
-  so += __shfl_xor(so, 16);
-  so += __shfl_xor(so, 32);
-  float ly = cls0 == y ? lg0 : (cls1 == y ? lg1 : 0.f);
-  ly += __shfl_xor(ly, 16);
-  ly += __shfl_xor(ly, 32);
-  FocalPixel o;
-  focal_terms(gamma, so, __expf(ly - mx), inv, __logf(se) + mx - ly, o.q, o.m, o.ce, o.f);
-  return o;
-}
-
 // The same classifier block on the matrix cores (isprs:1024-1031 is a true dense contraction: [M x C] . [C x K]): three
 // products per tile of 16 pixels, all on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains), the class dimension padded to 16 / 8:
 //   logits^T [class][px] = W^T [class][c] . feat^T [c][px]            (k = channel;  C / 4 MFMAs)
@@ -1159,21 +1157,23 @@ __device__ __forceinline__ FocalPixel focal_pixel(float gamma, int y, int cls0, 
 // accumulator register r -- the real classes (< 8) of a pixel sit in registers 0 and 1 of its four lanes, softmax / arg-max /
 // loss need the exchanges with lanes l ^ 16 and l ^ 32, and the logit gradients are already the B operand of the second
 // product (k slot l >> 4 <-> class (l >> 4) + 4 s at step s = 0, 1).  Only the third product needs them transposed: through a
-// 1-KiB LDS tile per wave.  The features are read twice, in the lane arrangement each product wants -- 16 pixels x 64 B per
-// instruction for the first (k = channel on l >> 4), 4 pixels x 256 B for the third (k = pixel on l >> 4) -- the second time
-// out of L2.  One workgroup = 4 waves, each walking its own 16-pixel tiles of the workgroup's pixel range; the filter sits in
-// LDS in the two operand arrangements.  Sums over pixels (dW, db, the loss) stay per workgroup and are added in wave order.
-template <int CQ, bool TRAIN, int LM>
-__global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
-  constexpr int C = CQ * 64, NJ = C / 16, KP = 16;
-  __shared__ __attribute__((aligned(16))) float W1[C * KP];      // [c / 16][(c % 16) / 4][row i <-> class (i >> 2) + 4 (i & 3)][c % 4]: A operand of the first product
-  __shared__ __attribute__((aligned(16))) float W2[C * 8];       // [c][2 G + s <-> class G + 4 s]: A operand of the second
-  __shared__ __attribute__((aligned(16))) float DL[4][16 * KP];  // per wave: logit gradients [px][class] of the current tile (classes 8 .. 15 stay zero)
-  __shared__ float redb[4][8];
-  __shared__ double redl[4];
-  __shared__ unsigned int confs[64];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int p = lane & 15, G = lane >> 4;
+// 1-KiB LDS tile per wave.  One workgroup = 4 waves, each walking its own 16-pixel tiles of the workgroup's pixel range; the filter
+// sits in LDS in the two operand arrangements.  Sums over pixels (dW, db, the loss) stay per workgroup and are added in wave order.
+// Two kernels run these products: classifier_mfma_kernel brings the features in through registers, classifier_dma_kernel by
+// LDS-DMA.  Everything else is the cls_mc_* functions below, which both call: the filter images, a pixel's arg-max, softmax and loss
+// gradient over its four lanes, and the workgroup's sums -- the class permutation, every operand order and every order of summation
+// exist once.  In all of them p = lane & 15 (pixel of the tile), G = lane >> 4, and the lane's two real class slots are
+// cls0 = G, cls1 = G + 4.
+
+// The filter into its two LDS images, the class permutation in both: W1 [c / 16][(c % 16) / 4][row i <-> class (i >> 2) + 4 (i & 3)]
+// [c % 4], the A operand of the first product, and W2 [c][2 G + s <-> class G + 4 s], the A operand of the second.  Zeroes the waves'
+// logit-gradient tiles DL (classes 8 .. 15 stay zero) and the workgroup's confusion counts, fetches the lane's two bias values, and
+// ends with the workgroup barrier that publishes all of it.
+template <int C>
+__device__ __forceinline__ void cls_mc_stage(const ClsArgs& a, float* W1, float* W2, float* DL, unsigned int* confs, float& bk0,
+                                             float& bk1) {
+  constexpr int KP = 16;
+  const int t = threadIdx.x, G = (t & 63) >> 4;
   const int K = a.K;
   for (int i = t; i < C * KP; i += 256) {
     const int c = i >> 4, row = i & 15;
@@ -1185,11 +1185,147 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     const int cls = (slot >> 1) + 4 * (slot & 1);
     W2[i] = cls < K ? a.w[(size_t)c * K + cls] : 0.f;
   }
-  for (int i = t; i < 4 * 16 * KP; i += 256) (&DL[0][0])[i] = 0.f;
+  for (int i = t; i < 4 * 16 * KP; i += 256) DL[i] = 0.f;
   if (t < 64) confs[t] = 0u;
-  const int cls0 = G, cls1 = G + 4;                 // this lane's two real class slots
-  const float bk0 = cls0 < K ? a.bias[cls0] : 0.f, bk1 = cls1 < K ? a.bias[cls1] : 0.f;
+  const int cls0 = G, cls1 = G + 4;
+  bk0 = cls0 < K ? a.bias[cls0] : 0.f;
+  bk1 = cls1 < K ? a.bias[cls1] : 0.f;
   __syncthreads();
+}
+
+// A pixel's maximum and its FIRST class over its four lanes (the larger value, the lower class on a tie), and the logits / pred
+// stores of a valid pixel
+__device__ __forceinline__ void cls_mc_argmax_store(const ClsArgs& a, int K, int pix, bool valid, int cls0, int cls1, float lg0, float lg1,
+                                                    float& mx, int& am) {
+  float mv = -INFINITY;
+  int mc = 0;
+  if (cls0 < K) { mv = lg0; mc = cls0; }
+  if (cls1 < K && lg1 > mv) { mv = lg1; mc = cls1; }
+#pragma unroll
+  for (int d = 16; d <= 32; d <<= 1) {
+    const float ov = __shfl_xor(mv, d);
+    const int oc = __shfl_xor(mc, d);
+    if (ov > mv || (ov == mv && oc < mc)) { mv = ov; mc = oc; }
+  }
+  mx = mv;
+  am = mc;
+  if (valid) {
+    if (a.logits) {
+      if (cls0 < K) a.logits[(size_t)pix * K + cls0] = lg0;
+      if (cls1 < K) a.logits[(size_t)pix * K + cls1] = lg1;
+    }
+    if (a.pred && cls0 == 0) a.pred[pix] = (unsigned char)am;
+  }
+}
+
+// A pixel's softmax and loss gradient: the lane's two logit gradients out, the loss term added to lsum in the lane that holds the
+// label's class.  Registers and cross-lane moves only, no global or LDS access: classifier_dma_kernel runs it inside its
+// hand-counted vmcnt window.  The sums over the pixel's four lanes l, l ^ 16, l ^ 32, l ^ 48 (se; for the focal terms so, the sum
+// of ex_k over k != y, and the label's logit) all use one exchange pattern, so that every lane of the pixel gets the same bits (a + b
+// == b + a bit for bit; the logit sum has one non-zero term: exact); the focal ex_y is recomputed from that logit, the same
+// instruction on the same operands as in the lane that owns class y.
+template <int LM>
+__device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, int cls0, int cls1, float lg0, float lg1,
+                                                  float mx, float& dl0, float& dl1, double& lsum) {
+  const float ex0 = cls0 < K ? __expf(lg0 - mx) : 0.f, ex1 = cls1 < K ? __expf(lg1 - mx) : 0.f;
+  float se = ex0 + ex1;
+  se += __shfl_xor(se, 16);
+  se += __shfl_xor(se, 32);
+  const float inv = 1.0f / se;
+  const float wy = LM != CLS_PLAIN ? cls_weight(a, y) : 1.f;
+  if constexpr (LM == CLS_FOCAL) {
+    float so = (cls0 == y ? 0.f : ex0) + (cls1 == y ? 0.f : ex1);
+    so += __shfl_xor(so, 16);
+    so += __shfl_xor(so, 32);
+    float ly = cls0 == y ? lg0 : (cls1 == y ? lg1 : 0.f);
+    ly += __shfl_xor(ly, 16);
+    ly += __shfl_xor(ly, 32);
+    float q, m, ce, f;
+    focal_terms(a.gamma, so, __expf(ly - mx), inv, __logf(se) + mx - ly, q, m, ce, f);
+    const float sc = cls_grad_scale<LM>(a.inv_n, wy, f);
+    dl0 = (in_loss && cls0 < K) ? (cls0 == y ? -q : ex0 * inv) * sc : 0.f;      // P_y - 1 = -q, uncancelled
+    dl1 = (in_loss && cls1 < K) ? (cls1 == y ? -q : ex1 * inv) * sc : 0.f;
+    if (in_loss && (cls0 == y || cls1 == y)) lsum += cls_loss_term<LM>(wy, se, mx, ly, m, ce);
+  } else {
+    const float sc = cls_grad_scale<LM>(a.inv_n, wy, 0.f);
+    dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
+    dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
+    if (in_loss && cls0 == y) lsum += cls_loss_term<LM>(wy, se, mx, lg0, 0.f, 0.f);
+    if (in_loss && cls1 == y) lsum += cls_loss_term<LM>(wy, se, mx, lg1, 0.f, 0.f);
+  }
+}
+
+// The workgroup's sums in wave order, into slab row blockIdx.x, and its confusion counts into a.conf.
+// dw[q][e][r] = dW[c = 64 q + 4 p + e][class 4 G + r]; every wave is done with W1 once the first barrier is passed: it becomes the
+// [C][8] accumulator.
+template <int CQ>
+__device__ __forceinline__ void cls_mc_epilogue(const ClsArgs& a, const f32x4 (&dw)[CQ][4], float db0, float db1, double lsum, float* W1,
+                                                float (*redb)[8], double* redl, const unsigned int* confs) {
+  constexpr int C = CQ * 64;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int p = lane & 15, G = lane >> 4;
+  const int K = a.K;
+  __syncthreads();
+  float* red = W1;
+  for (int w = 0; w < 4; ++w) {
+    if (wave == w && G < 2) {
+#pragma unroll
+      for (int q = 0; q < CQ; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int idx = (64 * q + 4 * p + e) * 8 + 4 * G + r;
+            red[idx] = (w ? red[idx] : 0.f) + dw[q][e][r];
+          }
+    }
+    __syncthreads();
+  }
+  // db: over the 16 pixels of a lane row (fixed butterfly), then over the waves
+  {
+    float v0 = db0, v1 = db1;
+    for (int d = 1; d < 16; d <<= 1) { v0 += __shfl_xor(v0, d); v1 += __shfl_xor(v1, d); }
+    if (p == 0) { redb[wave][G] = v0; redb[wave][G + 4] = v1; }
+  }
+  {
+    double v = lsum;
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
+    if (lane == 0) redl[wave] = v;
+  }
+  __syncthreads();
+  if (a.dw_partial) {
+    for (int e = t; e < C * K; e += 256) {
+      const int c = e / K, k = e - c * K;
+      a.dw_partial[(size_t)blockIdx.x * C * K + e] = red[c * 8 + k];
+    }
+    if (t < K) a.db_partial[(size_t)blockIdx.x * K + t] = ((redb[0][t] + redb[1][t]) + redb[2][t]) + redb[3][t];
+  }
+  if (t == 0) a.loss_partial[blockIdx.x] = ((redl[0] + redl[1]) + redl[2]) + redl[3];
+  if (a.conf && t < K * K) {
+    const int r = t / K, c = t - r * K;
+    const unsigned v = confs[r * 8 + c];
+    if (v) atomicAdd(&a.conf[t], v);
+  }
+}
+
+// The register-staged form.  The features are read twice, in the lane arrangement each product wants -- 16 pixels x 64 B per
+// instruction for the first (k = channel on l >> 4), 4 pixels x 256 B for the third (k = pixel on l >> 4) -- the second time
+// out of L2.
+template <int CQ, bool TRAIN, int LM>
+__global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
+  constexpr int C = CQ * 64, NJ = C / 16, KP = 16;
+  __shared__ __attribute__((aligned(16))) float W1[C * KP];      // A operand of the first product (cls_mc_stage)
+  __shared__ __attribute__((aligned(16))) float W2[C * 8];       // A operand of the second
+  __shared__ __attribute__((aligned(16))) float DL[4][16 * KP];  // per wave: logit gradients [px][class] of the current tile
+  __shared__ float redb[4][8];
+  __shared__ double redl[4];
+  __shared__ unsigned int confs[64];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int p = lane & 15, G = lane >> 4;
+  const int K = a.K;
+  const int cls0 = G, cls1 = G + 4;                 // this lane's two real class slots
+  float bk0, bk1;
+  cls_mc_stage<C>(a, W1, W2, &DL[0][0], confs, bk0, bk1);
 
   f32x4 dw[CQ][4];
 #pragma unroll
@@ -1234,51 +1370,15 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     acc[1] += acc_b[1];
     // this lane: pixel p, classes G (register 0) and G + 4 (register 1); registers 2, 3 are padding
     const float lg0 = acc[0] + bk0, lg1 = acc[1] + bk1;
-    float mv = -INFINITY;
-    int mc = 0;
-    if (cls0 < K) { mv = lg0; mc = cls0; }
-    if (cls1 < K && lg1 > mv) { mv = lg1; mc = cls1; }
-    // maximum and its FIRST class over the four lanes of the pixel: the larger value, the lower class on a tie
-#pragma unroll
-    for (int d = 16; d <= 32; d <<= 1) {
-      const float ov = __shfl_xor(mv, d);
-      const int oc = __shfl_xor(mc, d);
-      if (ov > mv || (ov == mv && oc < mc)) { mv = ov; mc = oc; }
-    }
-    const float mx = mv;
-    const int am = mc;
-    if (valid) {
-      if (a.logits) {
-        if (cls0 < K) a.logits[(size_t)pix * K + cls0] = lg0;
-        if (cls1 < K) a.logits[(size_t)pix * K + cls1] = lg1;
-      }
-      if (a.pred && G == 0) a.pred[pix] = (unsigned char)am;
-    }
+    float mx;
+    int am;
+    cls_mc_argmax_store(a, K, pix, valid, cls0, cls1, lg0, lg1, mx, am);
     if (!TRAIN) continue;
     const int y = a.labels[pixc];
     if (G == 0 && valid && a.conf && (!a.acc_mask || a.acc_mask[pix]) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
     const bool in_loss = valid && (!a.loss_mask || a.loss_mask[pixc]) && y < K;     // a label outside [0, K) never trains the net
-    const float ex0 = cls0 < K ? __expf(lg0 - mx) : 0.f, ex1 = cls1 < K ? __expf(lg1 - mx) : 0.f;
-    float se = ex0 + ex1;
-    se += __shfl_xor(se, 16);                       // (a + b == b + a bit for bit: every lane of the pixel gets the same sum)
-    se += __shfl_xor(se, 32);
-    const float inv = 1.0f / se;
-    constexpr bool WT = LM != CLS_PLAIN;
-    const float wy = WT ? cls_weight(a, y) : 1.f;
     float dl0, dl1;
-    if constexpr (LM == CLS_FOCAL) {
-      const FocalPixel fp = focal_pixel(a.gamma, y, cls0, cls1, ex0, ex1, lg0, lg1, mx, se, inv);
-      const float sc = a.inv_n * wy * fp.f;
-      dl0 = (in_loss && cls0 < K) ? (cls0 == y ? -fp.q : ex0 * inv) * sc : 0.f;      // P_y - 1 = -q, uncancelled
-      dl1 = (in_loss && cls1 < K) ? (cls1 == y ? -fp.q : ex1 * inv) * sc : 0.f;
-      if (in_loss && (cls0 == y || cls1 == y)) lsum += (double)wy * ((double)fp.m * (double)fp.ce);
-    } else {
-      const float sc = WT ? a.inv_n * wy : a.inv_n;
-      dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
-      dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
-      if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
-      if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
-    }
+    cls_mc_pixel_grad<LM>(a, K, y, in_loss, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
     db0 += dl0;
     db1 += dl1;
     if (!a.gfeat) continue;
@@ -1316,48 +1416,7 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     }
   }
   if (!TRAIN) return;
-  // ---- workgroup sums in wave order, one slab row per workgroup.  dw[q][e][r] = dW[c = 64 q + 4 p + e][class 4 G + r]
-  __syncthreads();                       // every wave is done with W1: it becomes the [C][8] accumulator
-  float* red = W1;
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w && G < 2) {
-#pragma unroll
-      for (int q = 0; q < CQ; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int idx = (64 * q + 4 * p + e) * 8 + 4 * G + r;
-            red[idx] = (w ? red[idx] : 0.f) + dw[q][e][r];
-          }
-    }
-    __syncthreads();
-  }
-  // db: over the 16 pixels of a lane row (fixed butterfly), then over the waves
-  {
-    float v0 = db0, v1 = db1;
-    for (int d = 1; d < 16; d <<= 1) { v0 += __shfl_xor(v0, d); v1 += __shfl_xor(v1, d); }
-    if (p == 0) { redb[wave][cls0] = v0; redb[wave][cls1] = v1; }
-  }
-  {
-    double v = lsum;
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-    if (lane == 0) redl[wave] = v;
-  }
-  __syncthreads();
-  if (a.dw_partial) {
-    for (int e = t; e < C * K; e += 256) {
-      const int c = e / K, k = e - c * K;
-      a.dw_partial[(size_t)blockIdx.x * C * K + e] = red[c * 8 + k];
-    }
-    if (t < K) a.db_partial[(size_t)blockIdx.x * K + t] = ((redb[0][t] + redb[1][t]) + redb[2][t]) + redb[3][t];
-  }
-  if (t == 0) a.loss_partial[blockIdx.x] = ((redl[0] + redl[1]) + redl[2]) + redl[3];
-  if (a.conf && t < K * K) {
-    const int r = t / K, c = t - r * K;
-    const unsigned v = confs[r * 8 + c];
-    if (v) atomicAdd(&a.conf[t], v);
-  }
+  cls_mc_epilogue<CQ>(a, dw, db0, db1, lsum, W1, redb, redl, confs);
 }
 
 // The MFMA classifier with its features brought in ONCE, by LDS-DMA, one tile ahead: a wave owns two 16-pixel feature tiles in LDS
@@ -1368,7 +1427,8 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
 // classifier_mfma_kernel pays per tile at two waves per SIMD (HBM round trip, then four L2 round trips for the second read) is
 // hidden behind a whole tile of arithmetic.  Every vector-memory operation inside the loop is counted by hand: the label / mask
 // bytes are inline-asm loads waited for with vmcnt(#DMA instructions), the DMA itself with vmcnt(#feature-gradient stores).
-// Products, orientations, class permutation and every sum are those of classifier_mfma_kernel: results are bitwise the same.
+// The filter images, the per-pixel arithmetic and the workgroup sums are the cls_mc_* functions classifier_mfma_kernel calls, and
+// the three products are written in its orientations and chain order: results are bitwise the same.
 template <int CQ, bool TRAIN, int LM>
 __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1384,21 +1444,9 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int p = lane & 15, G = lane >> 4;
   const int K = a.K;
-  for (int i = t; i < C * KP; i += 256) {
-    const int c = i >> 4, row = i & 15;
-    const int cls = (row >> 2) + 4 * (row & 3);
-    W1[(((c >> 4) * 4 + ((c & 15) >> 2)) * KP + row) * 4 + (c & 3)] = cls < K ? a.w[(size_t)c * K + cls] : 0.f;
-  }
-  for (int i = t; i < C * 8; i += 256) {
-    const int c = i >> 3, slot = i & 7;
-    const int cls = (slot >> 1) + 4 * (slot & 1);
-    W2[i] = cls < K ? a.w[(size_t)c * K + cls] : 0.f;
-  }
-  for (int i = t; i < 4 * 16 * KP; i += 256) (&DL[0][0])[i] = 0.f;
-  if (t < 64) confs[t] = 0u;
   const int cls0 = G, cls1 = G + 4;
-  const float bk0 = cls0 < K ? a.bias[cls0] : 0.f, bk1 = cls1 < K ? a.bias[cls1] : 0.f;
-  __syncthreads();
+  float bk0, bk1;
+  cls_mc_stage<C>(a, W1, W2, &DL[0][0], confs, bk0, bk1);
 
   f32x4 dw[CQ][4];
 #pragma unroll
@@ -1464,25 +1512,9 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
     acc[0] += acc_b[0];
     acc[1] += acc_b[1];
     const float lg0 = acc[0] + bk0, lg1 = acc[1] + bk1;
-    float mv = -INFINITY;
-    int mc = 0;
-    if (cls0 < K) { mv = lg0; mc = cls0; }
-    if (cls1 < K && lg1 > mv) { mv = lg1; mc = cls1; }
-#pragma unroll
-    for (int d = 16; d <= 32; d <<= 1) {
-      const float ov = __shfl_xor(mv, d);
-      const int oc = __shfl_xor(mc, d);
-      if (ov > mv || (ov == mv && oc < mc)) { mv = ov; mc = oc; }
-    }
-    const float mx = mv;
-    const int am = mc;
-    if (valid) {
-      if (a.logits) {
-        if (cls0 < K) a.logits[(size_t)pix * K + cls0] = lg0;
-        if (cls1 < K) a.logits[(size_t)pix * K + cls1] = lg1;
-      }
-      if (a.pred && G == 0) a.pred[pix] = (unsigned char)am;
-    }
+    float mx;
+    int am;
+    cls_mc_argmax_store(a, K, pix, valid, cls0, cls1, lg0, lg1, mx, am);
     if (TRAIN) {
       // the three byte loads are older than the NI DMA instructions (or nothing, on the last tile) issued after them
       if (tb + 64 < pend) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(ylab), "+v"(vlm), "+v"(vam) : "n"(NI) : "memory");
@@ -1490,30 +1522,10 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       const int y = (int)ylab;
       if (G == 0 && valid && a.conf && (!a.acc_mask || vam) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
       const bool in_loss = valid && (!a.loss_mask || vlm) && y < K;
-      const float ex0 = cls0 < K ? __expf(lg0 - mx) : 0.f, ex1 = cls1 < K ? __expf(lg1 - mx) : 0.f;
-      float se = ex0 + ex1;
-      se += __shfl_xor(se, 16);
-      se += __shfl_xor(se, 32);
-      const float inv = 1.0f / se;
-      // (the weight select: vector-ALU work of the softmax section, after the logits' MFMAs have been issued and before the filter
-      // gradient's -- no MFMA waits for it)
-      // (the focal factor likewise: its four cross-lane moves and its arithmetic sit here, in the softmax section)
-      constexpr bool WT = LM != CLS_PLAIN;
-      const float wy = WT ? cls_weight(a, y) : 1.f;
+      // (the weight select and the focal factor's four cross-lane moves and arithmetic: vector-ALU work of the softmax section,
+      // after the logits' MFMAs have been issued and before the filter gradient's -- no MFMA waits for it)
       float dl0, dl1;
-      if constexpr (LM == CLS_FOCAL) {
-        const FocalPixel fp = focal_pixel(a.gamma, y, cls0, cls1, ex0, ex1, lg0, lg1, mx, se, inv);
-        const float sc = a.inv_n * wy * fp.f;
-        dl0 = (in_loss && cls0 < K) ? (cls0 == y ? -fp.q : ex0 * inv) * sc : 0.f;
-        dl1 = (in_loss && cls1 < K) ? (cls1 == y ? -fp.q : ex1 * inv) * sc : 0.f;
-        if (in_loss && (cls0 == y || cls1 == y)) lsum += (double)wy * ((double)fp.m * (double)fp.ce);
-      } else {
-        const float sc = WT ? a.inv_n * wy : a.inv_n;
-        dl0 = (in_loss && cls0 < K) ? (ex0 * inv - (cls0 == y ? 1.f : 0.f)) * sc : 0.f;
-        dl1 = (in_loss && cls1 < K) ? (ex1 * inv - (cls1 == y ? 1.f : 0.f)) * sc : 0.f;
-        if (in_loss && cls0 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg0) : (double)(__logf(se) + mx - lg0);
-        if (in_loss && cls1 == y) lsum += WT ? (double)wy * (double)(__logf(se) + mx - lg1) : (double)(__logf(se) + mx - lg1);
-      }
+      cls_mc_pixel_grad<LM>(a, K, y, in_loss, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
       db0 += dl0;
       db1 += dl1;
       if (a.gfeat) {
@@ -1553,41 +1565,7 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   if (!TRAIN) return;
-  __syncthreads();
-  float* red = W1;
-  for (int w = 0; w < 4; ++w) {
-    if (wave == w && G < 2) {
-#pragma unroll
-      for (int q = 0; q < CQ; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int idx = (64 * q + 4 * p + e) * 8 + 4 * G + r;
-            red[idx] = (w ? red[idx] : 0.f) + dw[q][e][r];
-          }
-    }
-    __syncthreads();
-  }
-  {
-    float v0 = db0, v1 = db1;
-    for (int d = 1; d < 16; d <<= 1) { v0 += __shfl_xor(v0, d); v1 += __shfl_xor(v1, d); }
-    if (p == 0) { redb[wave][cls0] = v0; redb[wave][cls1] = v1; }
-  }
-  {
-    double v = lsum;
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
-    if (lane == 0) redl[wave] = v;
-  }
-  __syncthreads();
-  if (a.dw_partial) {
-    for (int e = t; e < C * K; e += 256) {
-      const int c = e / K, k = e - c * K;
-      a.dw_partial[(size_t)blockIdx.x * C * K + e] = red[c * 8 + k];
-    }
-    if (t < K) a.db_partial[(size_t)blockIdx.x * K + t] = ((redb[0][t] + redb[1][t]) + redb[2][t]) + redb[3][t];
-  }
-  if (t == 0) a.loss_partial[blockIdx.x] = ((redl[0] + redl[1]) + redl[2]) + redl[3];
+  cls_mc_epilogue<CQ>(a, dw, db0, db1, lsum, W1, redb, redl, confs);
   for (int r = gridDim.x + blockIdx.x; r < a.nrows; r += gridDim.x) {        // slab rows beyond the launch: zero (the caller sums a.nrows rows)
     if (a.dw_partial) {
       for (int e = t; e < C * K; e += 256) a.dw_partial[(size_t)r * C * K + e] = 0.f;
@@ -1595,12 +1573,24 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
     }
     if (t == 0) a.loss_partial[r] = 0.0;
   }
-  if (a.conf && t < K * K) {
-    const int r = t / K, c = t - r * K;
-    const unsigned v = confs[r * 8 + c];
-    if (v) atomicAdd(&a.conf[t], v);
-  }
 #endif
+}
+
+// Run-time launch parameters onto template arguments, handed to a generic lambda as std::integral_constants.
+// cls_width: the width C / 64 = Q .. QMAX - 1, anything else QMAX.  cls_mode: (loss mode, labels present) onto <TRAIN, LM> -- the
+// weighted and focal modes exist for training only, so no TRAIN = false kernel is instantiated with them.
+template <int Q, int QMAX, typename F>
+static void cls_width(int cq, F&& f) {
+  if constexpr (Q < QMAX)
+    if (cq != Q) return cls_width<Q + 1, QMAX>(cq, f);
+  f(std::integral_constant<int, Q>{});
+}
+template <typename F>
+static void cls_mode(int lm, bool train, F&& f) {
+  if (lm == CLS_FOCAL) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL>{});
+  else if (lm == CLS_WEIGHTED) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED>{});
+  else if (train) f(std::true_type{}, std::integral_constant<int, CLS_PLAIN>{});
+  else f(std::false_type{}, std::integral_constant<int, CLS_PLAIN>{});
 }
 
 __global__ void sum_f64_kernel(const double* __restrict__ in, int n, double* __restrict__ out) {
@@ -1949,32 +1939,31 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
   if (mfma && C / 64 <= 4 && g_cls_variant != 2 && (g_cls_variant == 3 || M >= (1 << 18))) {
     a.dma_span = (nblk + 255) / 256;
     const int ndma = (nblk + a.dma_span - 1) / a.dma_span;
-#define DRS_CLS_D(cq) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_FOCAL>), dim3(ndma), dim3(256), 0, st, a); \
-                           else if (wt) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_WEIGHTED>), dim3(ndma), dim3(256), 0, st, a); \
-                           else if (labels) DRS_LAUNCH((classifier_dma_kernel<cq, true, CLS_PLAIN>), dim3(ndma), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_dma_kernel<cq, false, CLS_PLAIN>), dim3(ndma), dim3(256), 0, st, a); } while (0)
-    switch (C / 64) { case 1: DRS_CLS_D(1); break; case 2: DRS_CLS_D(2); break; case 3: DRS_CLS_D(3); break; default: DRS_CLS_D(4); break; }
-#undef DRS_CLS_D
+    cls_width<1, 4>(C / 64, [&](auto cq) {
+      cls_mode(lm, labels != nullptr, [&](auto train, auto mode) {
+        DRS_LAUNCH((classifier_dma_kernel<cq(), train(), mode()>), dim3(ndma), dim3(256), 0, st, a);
+      });
+    });
     return DRS_LAUNCH_CHECK();
   }
   if (mfma) {
-#define DRS_CLS_M(cq) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_FOCAL>), dim3(nblk), dim3(256), 0, st, a); \
-                           else if (wt) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_WEIGHTED>), dim3(nblk), dim3(256), 0, st, a); \
-                           else if (labels) DRS_LAUNCH((classifier_mfma_kernel<cq, true, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); \
-                           else DRS_LAUNCH((classifier_mfma_kernel<cq, false, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); } while (0)
-    switch (C / 64) { case 1: DRS_CLS_M(1); break; case 2: DRS_CLS_M(2); break; case 3: DRS_CLS_M(3); break; case 4: DRS_CLS_M(4); break;
-                      case 5: DRS_CLS_M(5); break; case 6: DRS_CLS_M(6); break; default: DRS_CLS_M(7); break; }
-#undef DRS_CLS_M
+    cls_width<1, 7>(C / 64, [&](auto cq) {
+      cls_mode(lm, labels != nullptr, [&](auto train, auto mode) {
+        DRS_LAUNCH((classifier_mfma_kernel<cq(), train(), mode()>), dim3(nblk), dim3(256), 0, st, a);
+      });
+    });
     return DRS_LAUNCH_CHECK();
   }
-#define DRS_CLS_CASE(ci, km) do { if (lm == CLS_FOCAL) DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_FOCAL>), dim3(nblk), dim3(256), 0, st, a); \
-                                  else if (wt) DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_WEIGHTED>), dim3(nblk), dim3(256), 0, st, a); \
-                                  else DRS_LAUNCH((classifier_loss_kernel<ci, km, CLS_PLAIN>), dim3(nblk), dim3(256), 0, st, a); } while (0)
-#define DRS_CLS_KM(km) switch (C / 64) { case 1: DRS_CLS_CASE(1, km); break; case 2: DRS_CLS_CASE(2, km); break; case 3: DRS_CLS_CASE(3, km); break; \
-    case 4: DRS_CLS_CASE(4, km); break; case 5: DRS_CLS_CASE(5, km); break; case 6: DRS_CLS_CASE(6, km); break; default: DRS_CLS_CASE(7, km); break; }
-  if (K == 2) DRS_CLS_KM(2) else if (K == 6) DRS_CLS_KM(6) else if (K == 7) DRS_CLS_KM(7) else DRS_CLS_KM(8)
-#undef DRS_CLS_KM
-#undef DRS_CLS_CASE
+  // (the vector-ALU form has no inference instantiation: without labels it runs its plain one, as train = true)
+  cls_width<1, 7>(C / 64, [&](auto ci) {
+    cls_mode(lm, true, [&](auto, auto mode) {
+      auto launch = [&](auto km) { DRS_LAUNCH((classifier_loss_kernel<ci(), km(), mode()>), dim3(nblk), dim3(256), 0, st, a); };
+      if (K == 2) launch(std::integral_constant<int, 2>{});
+      else if (K == 6) launch(std::integral_constant<int, 6>{});
+      else if (K == 7) launch(std::integral_constant<int, 7>{});
+      else launch(std::integral_constant<int, 8>{});
+    });
+  });
   return DRS_LAUNCH_CHECK();
 }
 

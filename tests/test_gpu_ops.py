@@ -632,11 +632,17 @@ def test_filter_gradient_chunk_walk_over_patch_sides(lib, S, B):
     assert float((gw_eq - outs[0]).abs().max() / outs[0].abs().max()) < 2e-6
 
 
-@pytest.mark.parametrize("C,K,B,S,P", [(256, 6, 3, 21, 0), (128, 4, 2, 17, 2), (64, 7, 1, 40, 1), (192, 8, 5, 9, 0), (256, 6, 16, 25, 0)])
-def test_classifier_forms_agree(lib, C, K, B, S, P):
+@pytest.mark.parametrize("C,K,B,S,P,mode", [pytest.param(*c, "plain", id="-".join(map(str, c))) for c in
+                                            [(256, 6, 3, 21, 0), (128, 4, 2, 17, 2), (64, 7, 1, 40, 1), (192, 8, 5, 9, 0), (256, 6, 16, 25, 0)]] +
+                         [(128, 4, 2, 17, 2, "weighted"), (256, 6, 3, 21, 0, "weighted"), (128, 4, 2, 17, 2, "focal"), (256, 6, 3, 21, 0, "focal")])
+def test_classifier_forms_agree(lib, C, K, B, S, P, mode):
     """The classifier block exists in a vector-ALU form (2-3 classes), a register-staged MFMA form and an LDS-DMA MFMA form (features
     brought in once, one tile ahead; up to C = 256).  The two MFMA forms run the same products in the same order: bitwise equal,
-    ragged last tiles, haloed feature slabs and masks included; the vector-ALU form agrees to rounding."""
+    ragged last tiles, haloed feature slabs and masks included; the vector-ALU form agrees to rounding.  The class-weighted and the
+    focal mode (gamma = 2, with weights; drs_classifier_loss_focal) hold the two MFMA forms and the product library's pick to the same
+    bitwise equality, with one weight exactly 0, the others unequal, and about 1 % of the labels 255, outside [0, K): (128, 4, 2, 17, 2)
+    is M = 578, a ragged last tile of 2 pixels in a haloed slab, (256, 6, 3, 21, 0) M = 1323 at the widest DMA tile.  (Those modes of the
+    vector-ALU form are held to fp64 by test_gpu_class_weights.py and test_gpu_focal_loss.py.)"""
     lib = lib.dev()
     rng = np.random.default_rng(C * 3 + K + S)
     M = B * S * S
@@ -646,47 +652,49 @@ def test_classifier_forms_agree(lib, C, K, B, S, P):
     y = rng.integers(0, K, size=M).astype(np.uint8)
     lm = rng.integers(0, 2, size=M).astype(np.uint8)
     am = rng.integers(0, 2, size=M).astype(np.uint8)
+    entry, mid = "drs_classifier_loss", ()
+    if mode != "plain":
+        y[rng.random(M) < 0.01] = 255
+        wc = np.asarray([0.5, 2.0, 0.0, 1.25, 7.0, 3.0][:K], dtype=np.float32)
+        entry, mid = "drs_classifier_loss_focal", (wc.ctypes.data, 2.0 if mode == "focal" else 0.0)
     fd = padded(feat, P, fill=3.0) if P else dev(feat)
     rows = lib.query("drs_classifier_rows", B, S)
     wdev, bdev, yd, lmd, amd = dev(w), dev(bias), dev(y), dev(lm), dev(am)
+
+    def train(which):
+        logits = torch.zeros(M * K, dtype=torch.float32, device=DEV)
+        pred = torch.zeros(M, dtype=torch.uint8, device=DEV)
+        gfeat = torch.zeros(M * C, dtype=torch.float32, device=DEV)
+        dwp = torch.zeros(rows * C * K, dtype=torch.float32, device=DEV)
+        dbp = torch.zeros(rows * K, dtype=torch.float32, device=DEV)
+        lp = torch.zeros(rows, dtype=torch.float64, device=DEV)
+        conf = torch.zeros(K * K, dtype=torch.int32, device=DEV)
+        which.call(entry, fd.data_ptr(), B, S, P, C, 0, C, K, wdev.data_ptr(), bdev.data_ptr(), yd.data_ptr(), lmd.data_ptr(), amd.data_ptr(),
+                   1.0 / max(1, int(lm.sum())), *mid, logits.data_ptr(), pred.data_ptr(), gfeat.data_ptr(), C, 0, dwp.data_ptr(), dbp.data_ptr(),
+                   lp.data_ptr(), conf.data_ptr(), stream())
+        return logits, pred, gfeat, dwp, dbp, lp, conf
     res = {}
     try:
-        for v in (0, 2, 3):
+        for v in (0, 2, 3) if mode == "plain" else (2, 3):
             lib.drs_debug_cls_variant(v)
-            logits = torch.zeros(M * K, dtype=torch.float32, device=DEV)
-            pred = torch.zeros(M, dtype=torch.uint8, device=DEV)
-            gfeat = torch.zeros(M * C, dtype=torch.float32, device=DEV)
-            dwp = torch.zeros(rows * C * K, dtype=torch.float32, device=DEV)
-            dbp = torch.zeros(rows * K, dtype=torch.float32, device=DEV)
-            lp = torch.zeros(rows, dtype=torch.float64, device=DEV)
-            conf = torch.zeros(K * K, dtype=torch.int32, device=DEV)
-            lib.call("drs_classifier_loss", fd.data_ptr(), B, S, P, C, 0, C, K, wdev.data_ptr(), bdev.data_ptr(), yd.data_ptr(), lmd.data_ptr(),
-                     amd.data_ptr(), 1.0 / max(1, int(lm.sum())), logits.data_ptr(), pred.data_ptr(), gfeat.data_ptr(), C, 0, dwp.data_ptr(), dbp.data_ptr(),
-                     lp.data_ptr(), conf.data_ptr(), stream())
+            out = train(lib)
             pred2 = torch.zeros(M, dtype=torch.uint8, device=DEV)
-            lib.call("drs_classifier_loss", fd.data_ptr(), B, S, P, C, 0, C, K, wdev.data_ptr(), bdev.data_ptr(), None, None, None, 0.0, None,
+            lib.call(entry, fd.data_ptr(), B, S, P, C, 0, C, K, wdev.data_ptr(), bdev.data_ptr(), None, None, None, 0.0, *mid, None,
                      pred2.data_ptr(), None, 0, 0, None, None, None, None, stream())
             torch.cuda.synchronize()
-            res[v] = (logits, pred, gfeat, dwp, dbp, lp, conf, pred2)
+            res[v] = out + (pred2,)
     finally:
         lib.drs_debug_cls_variant(1)
     for a, b in zip(res[2], res[3]):
         assert torch.equal(a, b)
     from drs_amd import _lib as prod                  # libdrs_hip.so picks the form by class count and pixel count
-    logits = torch.zeros(M * K, dtype=torch.float32, device=DEV)
-    pred = torch.zeros(M, dtype=torch.uint8, device=DEV)
-    gfeat = torch.zeros(M * C, dtype=torch.float32, device=DEV)
-    dwp = torch.zeros(rows * C * K, dtype=torch.float32, device=DEV)
-    dbp = torch.zeros(rows * K, dtype=torch.float32, device=DEV)
-    lp = torch.zeros(rows, dtype=torch.float64, device=DEV)
-    conf = torch.zeros(K * K, dtype=torch.int32, device=DEV)
     assert prod.query("drs_classifier_rows", B, S) == rows
-    prod.call("drs_classifier_loss", fd.data_ptr(), B, S, P, C, 0, C, K, wdev.data_ptr(), bdev.data_ptr(), yd.data_ptr(), lmd.data_ptr(),
-              amd.data_ptr(), 1.0 / max(1, int(lm.sum())), logits.data_ptr(), pred.data_ptr(), gfeat.data_ptr(), C, 0, dwp.data_ptr(), dbp.data_ptr(),
-              lp.data_ptr(), conf.data_ptr(), stream())
+    out = train(prod)
     torch.cuda.synchronize()
-    for a, b in zip((logits, pred, gfeat, dwp, dbp, lp, conf), res[2] if K >= 4 else res[0]):
+    for a, b in zip(out, res[2] if K >= 4 else res[0]):
         assert torch.equal(a, b)
+    if mode != "plain":
+        return
     assert torch.equal(res[0][1], res[2][1]) or float((res[0][1] != res[2][1]).float().mean()) < 1e-3
     assert torch.equal(res[0][6], res[2][6]) or float((res[0][6] - res[2][6]).abs().sum()) <= 2e-3 * M
     for i in (0, 2):

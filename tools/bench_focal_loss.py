@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Per-launch time of the fused classifier at the headline step's shape (128 x 64 x 64, C = 256, K = 6: the LDS-DMA form, training) in
 the three loss modes -- plain, class-weighted, focal -- and, with parent=<path to another build's libdrs_hip.so>, of
-that build's drs_classifier_loss beside them.  Alternating order, `rounds` rounds of `n` back-to-back launches per variant after a
-warm-up, HIP events on the launch stream; prints one JSON line.  Under `rocprofv3 --kernel-trace --stats` the same run gives the
-per-kernel times: the variants are four kernel names (classifier_dma_kernel<4, true, false> of the other build, <4, true, 0>,
-<4, true, 1>, <4, true, 2>).
+that build's drs_classifier_loss_focal in the same three modes beside them (parent_plain, parent_weighted, parent_focal against
+new_*).  Alternating order, `rounds` rounds of `n` back-to-back launches per variant after a warm-up, HIP events on the launch
+stream; prints one JSON line.  The two builds' kernels carry the same names (classifier_dma_kernel<4, true, 0 / 1 / 2>), so a kernel
+trace of this run cannot tell them apart: the event times are the comparison.
 
     python tools/bench_focal_loss.py [parent=/path/to/libdrs_hip.so] [B=128] [S=64] [C=256] [K=6] [gamma=2] [n=50] [rounds=5]"""
 import ctypes
@@ -23,9 +23,9 @@ OPTIONS = ("parent", "B", "S", "C", "K", "gamma", "n", "rounds")
 
 def load_parent(path):
     """a second build of the library in this process: it exports the same symbol names, which is safe because ctypes opens a
-    library RTLD_LOCAL -- each handle resolves its own drs_classifier_loss"""
+    library RTLD_LOCAL -- each handle resolves its own drs_classifier_loss_focal"""
     lib = ctypes.CDLL(path)
-    lib.drs_classifier_loss.restype, lib.drs_classifier_loss.argtypes = _lib.SIGNATURES["drs_classifier_loss"]
+    lib.drs_classifier_loss_focal.restype, lib.drs_classifier_loss_focal.argtypes = _lib.SIGNATURES["drs_classifier_loss_focal"]
     return lib
 
 
@@ -51,15 +51,14 @@ def main(parent, B, S, C, K, gamma, n, rounds):
     st = torch.cuda.current_stream(DEV).cuda_stream
     head = (feat.data_ptr(), B, S, 0, C, 0, C, K, w.data_ptr(), b.data_ptr(), lab.data_ptr(), None, am.data_ptr(), 1.0 / M)
     tail = (None, pred.data_ptr(), gfeat.data_ptr(), C, 0, dw.data_ptr(), db.data_ptr(), lp.data_ptr(), conf.data_ptr(), st)
-    mid = {"new_plain": (None, 0.0), "new_weighted": (wc.ctypes.data, 0.0), "new_focal": (None, gamma)}
+    mid = {"plain": (None, 0.0), "weighted": (wc.ctypes.data, 0.0), "focal": (None, gamma)}
+    libs = ({"parent": par} if par is not None else {}) | {"new": new}
 
     def run(which):
-        if which == "parent":
-            rc = par.drs_classifier_loss(*(head + tail))
-        else:
-            rc = new.drs_classifier_loss_focal(*(head + mid[which] + tail))
+        build, mode = which.split("_")
+        rc = libs[build].drs_classifier_loss_focal(*(head + mid[mode] + tail))
         assert rc == 0, (which, rc)
-    out = {k: [] for k in (("parent",) if par is not None else ()) + tuple(mid)}
+    out = {"%s_%s" % (build, mode): [] for build in libs for mode in mid}
     for k in out:
         for _ in range(10):
             run(k)
