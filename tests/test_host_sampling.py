@@ -162,6 +162,13 @@ def test_entry_points_reject_bad_arguments_before_any_launch():
         ("drs_filter_split", (p, 3, 5, 24, 64, 2, p, None, None)),                                              # cin_pad % 32
         ("drs_bn_act_pool_forward_terms", (p, 2, 8, 64, p, 0.1, 1, None, 2, 64, 0, None, None, 2, None)),       # no terms
         ("drs_bn_backward_apply_terms", (p, p, 2, 8, 64, p, p, 128.0, None, 2, 72, 0, p, 2, None)),             # ld % 32
+        ("drs_avg_pool_forward", (p, 2, 8, 64, 4, p, 2, 64, 0, None)),                                          # even k
+        ("drs_avg_pool_backward", (p, 64, 0, 2, 8, 64, 4, p, None)),                                            # even k
+        ("drs_avg_pool_forward", (p, 2, 8, 66, 5, p, 2, 68, 0, None)),                                          # C % 4
+        ("drs_avg_pool_backward", (p, 66, 0, 2, 8, 66, 5, p, None)),                                            # C % 4
+        ("drs_avg_pool_forward", (p, 4096, 14, 64, 5, p, 1, 64, 0, None)),                                      # B * (S + 2 P) = 65536 grid rows
+        ("drs_avg_pool_backward", (p, 64, 0, 4096, 16, 64, 5, p, None)),                                        # B * S = 65536 grid rows
+        ("drs_se_forward", (p, 4096, 14, 64, 16, p, p, p, p, p, p, p, p, 1, 64, 0, None)),                      # B * (S + 2 P) = 65536 grid rows
     ]
     for name, args in bad:
         with pytest.raises(_lib.DrsError):

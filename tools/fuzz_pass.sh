@@ -11,4 +11,5 @@ run fuzz_nets n=$((120 * K)) seed=$((S0 + 3))
 run fuzz_big n=$((250 * K)) seed=$((S0 + 4))
 run fuzz_big n=$((150 * K)) seed=$((S0 + 5)) sides=32,64,128
 run fuzz_split n=$((150 * K)) seed=$((S0 + 6))
+run fuzz_se_avgpool n=$((600 * K)) seed=$((S0 + 7))
 cat $O/fuzz_more.txt
