@@ -1,7 +1,8 @@
 """-m gpu: the convolution, batch-norm / activation / pool, classifier and optimizer entry points of include/drs.h against the CPU
 oracle (oracle/tf_ops.py, fp64) on the same seeded inputs; the remaining entry points have their op-level tests elsewhere: average
 pool, squeeze-and-excitation (training side), the term-writing batch-norm forms, softmax accumulation and drs_scale_f64 in
-test_gpu_pointwise_oplevel.py, the split-bf16 convolution in test_gpu_split.py, the whole-image SE gates in test_gpu_dense_se.py,
+test_gpu_pointwise_oplevel.py, the classifier on steep logits, exact arg-max ties, empty masks and tiny / ragged pixel counts in
+test_gpu_classifier_edges.py, the split-bf16 convolution in test_gpu_split.py, the whole-image SE gates in test_gpu_dense_se.py,
 crop / stitch / tile placement in test_gpu_patches.py and the test_gpu_dense_*.py modules.  Tolerances: fp32 kernels vs fp64 oracle, relative to the tensor's max magnitude,
 1e-5 for single ops (BASELINE north_star: logits within 1e-3 relative end to end); integer outputs exact."""
 import numpy as np
