@@ -58,6 +58,7 @@ SIGNATURES = {
     "drs_classifier_loss_focal": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _i, _i, _p, _p,
                                        _p, _p, _p]),
     "drs_label_histogram": (_i, [_p, _sz, _i, _i, _p, _p]),
+    "drs_reliability_histogram": (_i, [_p, _p, _p, _sz, _i, _i, _p, _p]),
     "drs_rows_reduce_f32": (_i, [_p, _i, _i, _p, _p, _p]),
     "drs_sum_f64": (_i, [_p, _i, _p, _p]),
     "drs_l2_loss": (_i, [_p, _sz, _p, _p, _p]),
@@ -67,6 +68,7 @@ SIGNATURES = {
                                 _p, _i, _i, _p]),
     "drs_stitch_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drs_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "drs_stitch_finalize_scores": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "drs_tile_place": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "drs_crop_dihedral": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "drs_tile_place_dihedral": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),

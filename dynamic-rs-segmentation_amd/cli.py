@@ -12,6 +12,9 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     --dense-tta
   + optionally, anywhere, with --dense-tile only, `--dense-se=global` (nets with squeeze-and-excitation blocks, which --dense-tile
     refuses without it): the blocks are gated by the mean over the whole image, computed exactly in tiles (predict_tile_dense's se)
+  + optionally, anywhere, `--score-maps=confidence,margin,entropy` (validate_test / generate_final_maps; with or without --dense-tile and
+    its companions): per-pixel uint8 score maps beside the labels -- written as `<stem>_<kind>.npy` / `.tif` by generate_final_maps --
+    and, in validate_test, a calibration line per map (loops.validate_test's / generate_final_maps' score_maps)
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -134,6 +137,28 @@ def parse_dense_se(argv):
     return (list(argv) if se is None else rest), se
 
 
+SCORE_MAPS_FLAG = "--score-maps"
+
+
+def parse_score_maps(argv):
+    """isprs flavour: the optional `--score-maps=kind,kind,...` (anywhere in argv; validate_test / generate_final_maps, which main
+    checks).  Returns (argv without the flag, tuple of kinds; patches.parse_score_maps), or (argv unchanged, None) without it.  A bare
+    flag, an unknown or repeated kind, or the flag given twice, raises ValueError."""
+    rest, kinds = [], None
+    for a in argv:
+        if a != SCORE_MAPS_FLAG and not a.startswith(SCORE_MAPS_FLAG + "="):
+            rest.append(a)
+            continue
+        if kinds is not None:
+            raise ValueError(SCORE_MAPS_FLAG + " given more than once")
+        try:
+            kinds = P.parse_score_maps(a[len(SCORE_MAPS_FLAG) + 1:])
+        except ValueError:
+            raise ValueError("%s: expected %s=%s (distinct kinds from these, comma-separated)"
+                             % (a, SCORE_MAPS_FLAG, ",".join(P.SCORE_KINDS))) from None
+    return (list(argv) if kinds is None else rest), kinds
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -238,6 +263,7 @@ def main(argv=None, device=None, comm=None):
         argv, dense_tta = parse_dense_tta(argv)
         argv, dense_scales = parse_dense_scales(argv)
         argv, dense_se = parse_dense_se(argv)
+        argv, score_maps = parse_score_maps(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
     except ValueError as e:
@@ -252,6 +278,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(DENSE_TILE_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if score_maps is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(SCORE_MAPS_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -319,11 +347,13 @@ def main(argv=None, device=None, comm=None):
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
+                                   score_maps=score_maps)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
+                                         score_maps=score_maps)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

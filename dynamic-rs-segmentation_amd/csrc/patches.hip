@@ -381,23 +381,31 @@ __global__ void crop_resampled_kernel(const CropResampledArgs a) {
   }
 }
 
-// the class-probability vector of pixel q of an hs x ws map: src / occur (a probability sum, src_is_prob) or the max-subtracted
-// softmax of src / occur (logits), written as in tile_place_dihedral_kernel; occur 0 counts as 1
-__device__ __forceinline__ void prob_vector(const float* src, const unsigned int* occur, size_t q, int K, int src_is_prob, float* p) {
-  const unsigned int o = occur[q];
-  const float oc = (float)(o ? o : 1u);
-  const float* s = src + q * K;
+// the class-probability vector of one pixel from its K accumulated values s and its divisor oc: s / oc (a probability sum,
+// src_is_prob) or the max-subtracted softmax of s / oc (logits), written as in tile_place_dihedral_kernel.  For logits mx is the
+// largest quotient and the return value the sum of the exponentials (what the entropy of score_maps_kernel is made of); for
+// probabilities mx is not set and the return value is 0.
+__device__ __forceinline__ float prob_from_sums(const float* s, float oc, int K, int src_is_prob, float* p, float& mx) {
   if (src_is_prob) {
     for (int k = 0; k < K; ++k) p[k] = s[k] / oc;
-    return;
+    return 0.f;
   }
-  float mx = s[0] / oc, sum = 0.f;
+  mx = s[0] / oc;
+  float sum = 0.f;
   for (int k = 1; k < K; ++k) mx = fmaxf(mx, s[k] / oc);
   for (int k = 0; k < K; ++k) {
     p[k] = expf(s[k] / oc - mx);
     sum += p[k];
   }
   for (int k = 0; k < K; ++k) p[k] = p[k] / sum;
+  return sum;
+}
+
+// the class-probability vector of pixel q of an hs x ws map: prob_from_sums of src[q] and occur[q]; occur 0 counts as 1
+__device__ __forceinline__ void prob_vector(const float* src, const unsigned int* occur, size_t q, int K, int src_is_prob, float* p) {
+  const unsigned int o = occur[q];
+  float mx = 0.f;
+  prob_from_sums(src + q * K, (float)(o ? o : 1u), K, src_is_prob, p, mx);
 }
 
 // acc[h][w][K] += U(hs x ws -> h x w) of the probability vectors: one thread per output pixel in image order (coalesced
@@ -432,6 +440,77 @@ __global__ void stitch_finalize_kernel(const float* __restrict__ prob, const uns
       if (v > best) { best = v; am = k; }
     }
     out[i] = (unsigned char)am;
+  }
+}
+
+// a score in [0, 1] as a byte: clamped (a NaN counts as 0), then rounded half up on the 255 scale
+__device__ __forceinline__ unsigned char score_byte(float s) {
+  s = s > 0.f ? (s < 1.f ? s : 1.f) : 0.f;
+  return (unsigned char)(int)(255.f * s + 0.5f);
+}
+
+// drs_stitch_finalize with the per-pixel score maps (include/drs.h: confidence, margin, normalised entropy) beside the label: one
+// thread per pixel, grid-stride, the pixel's K sums read once into registers (K is a template parameter: the loops unroll and
+// nothing spills).  The label is stitch_finalize_kernel's expression, the probability vector is prob_from_sums'.  Every output is one
+// byte per pixel in pixel order, so a wave writes 64 consecutive bytes per map; a NULL map is not computed for, nor written.
+template <int K>
+__global__ void score_maps_kernel(const float* __restrict__ sums, const unsigned int* __restrict__ occur, size_t npix, int sums_are_prob,
+                                  unsigned char* __restrict__ labels, unsigned char* __restrict__ confidence,
+                                  unsigned char* __restrict__ margin, unsigned char* __restrict__ entropy) {
+  const bool want_scores = confidence || margin || entropy;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned o = occur[i];
+    const unsigned oc = o ? o : 1u;
+    float s[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = sums[i * K + k];
+    int am = 0;
+    double best = (double)s[0] / (double)oc;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      const double v = (double)s[k] / (double)oc;
+      if (v > best) { best = v; am = k; }
+    }
+    if (labels) labels[i] = (unsigned char)am;
+    if (!want_scores) continue;
+    if (!o) {          // no window or tile reached this pixel: nothing is known about it
+      if (confidence) confidence[i] = 0;
+      if (margin) margin[i] = 0;
+      if (entropy) entropy[i] = 255;
+      continue;
+    }
+    const float ocf = (float)oc;
+    float p[K], mx = 0.f;
+    const float se = prob_from_sums(s, ocf, K, sums_are_prob, p, mx);
+    float top = p[0], second = 0.f;
+#pragma unroll
+    for (int k = 1; k < K; ++k) top = k == am ? p[k] : top;
+    bool first = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (k == am) continue;
+      second = first ? p[k] : fmaxf(second, p[k]);
+      first = false;
+    }
+    if (confidence) confidence[i] = score_byte(top);
+    if (margin) margin[i] = score_byte(top - second);
+    if (entropy) {
+      float hn = 0.f;          // one class: the entropy is 0, and so is its normalised form here
+      if (K > 1) {
+        float acc = 0.f;
+        if (sums_are_prob) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) acc += p[k] > 0.f ? p[k] * logf(p[k]) : 0.f;      // 0 ln 0 = 0
+          hn = -acc / logf((float)K);
+        } else {
+          // -sum p ln p with ln p_k = (v_k - max) - ln se: no logarithm of an underflowed p_k is formed
+#pragma unroll
+          for (int k = 0; k < K; ++k) acc += p[k] * (s[k] / ocf - mx);
+          hn = (logf(se) - acc) / logf((float)K);
+        }
+      }
+      entropy[i] = score_byte(hn);
+    }
   }
 }
 
@@ -561,6 +640,28 @@ int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(stitch_finalize_kernel, dim3(nb < 4096 ? (unsigned)nb : 4096u), dim3(256), 0, (hipStream_t)stream, prob, occur,
                      n, K, out);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob,
+                               unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
+                               void* stream) {
+  if (!sums || !occur || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
+  if (!labels && !confidence && !margin && !entropy) return DRS_ERR_ARG;
+  const size_t n = (size_t)h * w;
+  const size_t nb = (n + 255) / 256;
+  const dim3 grid(nb < 4096 ? (unsigned)nb : 4096u);
+  const int prob = sums_are_prob ? 1 : 0;
+#define DRS_SCORES_CASE(KK)                                                                                                        \
+  case KK:                                                                                                                         \
+    DRS_LAUNCH(score_maps_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, labels, confidence, margin,   \
+               entropy);                                                                                                           \
+    break;
+  switch (K) {
+    DRS_SCORES_CASE(1) DRS_SCORES_CASE(2) DRS_SCORES_CASE(3) DRS_SCORES_CASE(4)
+    DRS_SCORES_CASE(5) DRS_SCORES_CASE(6) DRS_SCORES_CASE(7) DRS_SCORES_CASE(8)
+  }
+#undef DRS_SCORES_CASE
   return DRS_LAUNCH_CHECK();
 }
 

@@ -1682,6 +1682,30 @@ __global__ void label_histogram_kernel(const unsigned char* __restrict__ labels,
   }
 }
 
+// Reliability table of a label map (metrics.calibration): per confidence byte c, how many counted pixels carry it and how many of
+// those are predicted right.  The counted pixels are those whose truth is neither ignore_label nor >= K.  Per-workgroup 32-bit
+// counters in LDS ([256][2]), added to the 64-bit table by integer atomics: order-independent, exact.  The 32-bit counters hold for
+// the reason label_histogram_kernel's do: drs_reliability_histogram has the same grid cap and the same bound on n.
+__global__ void reliability_histogram_kernel(const unsigned char* __restrict__ truth, const unsigned char* __restrict__ pred,
+                                             const unsigned char* __restrict__ confidence, size_t n, int K, int ignore_label,
+                                             unsigned long long* __restrict__ hist) {
+  __shared__ unsigned int sh[512];
+  for (int j = threadIdx.x; j < 512; j += blockDim.x) sh[j] = 0u;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int y = truth[i];
+    if (y == ignore_label || y >= K) continue;
+    const int c = confidence[i];
+    atomicAdd(&sh[2 * c], 1u);
+    if ((int)pred[i] == y) atomicAdd(&sh[2 * c + 1], 1u);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 512; j += blockDim.x) {
+    const unsigned v = sh[j];
+    if (v) atomicAdd(&hist[j], (unsigned long long)v);
+  }
+}
+
 inline int chain_hp() { return drs_chain_level(drs_tl_chain, drs_g_chain_mode) >= 2 ? 1 : 0; }
 
 inline ActView mkview(float* base, int S, int P, int ld, int coff) {
@@ -1993,6 +2017,18 @@ int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_l
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(label_histogram_kernel, dim3(nb < 1024 ? (unsigned)nb : 1024u), dim3(256), 0, (hipStream_t)stream, labels, n, K, void_label,
              counts);
+  return DRS_LAUNCH_CHECK();
+}
+
+// hist[c][0] += pixels of confidence byte c, hist[c][1] += those of them with pred == truth; hist: [256][2] 64-bit counters
+// (device), ADDED to
+int drs_reliability_histogram(const unsigned char* truth, const unsigned char* pred, const unsigned char* confidence, size_t n, int K,
+                              int ignore_label, unsigned long long* hist, void* stream) {
+  if (!truth || !pred || !confidence || !hist || K < 1 || K > 8 || n < 1 || n >= ((size_t)1 << 40)) return DRS_ERR_ARG;
+  // (grid cap 1024 and n < 2^40, as in drs_label_histogram: a workgroup sees fewer than 2^32 pixels)
+  const size_t nb = (n + 255) / 256;
+  DRS_LAUNCH(reliability_histogram_kernel, dim3(nb < 1024 ? (unsigned)nb : 1024u), dim3(256), 0, (hipStream_t)stream, truth, pred,
+             confidence, n, K, ignore_label, hist);
   return DRS_LAUNCH_CHECK();
 }
 

@@ -438,11 +438,49 @@ def train(training_data, training_labels, training_class_distribution, training_
 
 
 # ------------------------------------------------------------------------------------------------- whole tiles
-def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm=None, return_sums=False, flavour="isprs"):
+def _check_scores(scores, return_sums):
+    """The `scores` argument of an inference path as a tuple of kinds (patches.check_score_kinds), None without it.  Raw sums and scores
+    exclude each other: a caller of return_sums finalises itself."""
+    if scores is None:
+        return None
+    kinds = P.check_score_kinds(scores)
+    if return_sums:
+        raise ValueError("scores and return_sums exclude each other: the score maps are made where the sums are finalised")
+    return kinds
+
+
+def _score_buffers(scores, n, dev):
+    """The zeroed uint8 maps, one per kind asked for (patches.check_score_kinds), as a dict in the order asked; None without scores."""
+    if scores is None:
+        return None
+    return {k: torch.zeros(n, dtype=torch.uint8, device=dev) for k in P.check_score_kinds(scores)}
+
+
+def _finalize(sums_ptr, occur_ptr, rows, w, K, sums_are_prob, out, smaps, pix0, st):
+    """Labels of `rows` image rows from their sums (device addresses of the first of those rows) into out[pix0:], by
+    drs_stitch_finalize; with score maps (smaps: _score_buffers) by drs_stitch_finalize_scores, which writes the same labels and the
+    maps' bytes at the same offset.  sums_are_prob says what the path accumulated and matters to the scores only."""
+    from . import _lib
+    if smaps is None:
+        _lib.call("drs_stitch_finalize", sums_ptr, occur_ptr, rows, w, K, out.data_ptr() + pix0, st)
+        return
+    ptr = [smaps[k].data_ptr() + pix0 if k in smaps else None for k in P.SCORE_KINDS]
+    _lib.call("drs_stitch_finalize_scores", sums_ptr, occur_ptr, rows, w, K, 1 if sums_are_prob else 0, out.data_ptr() + pix0,
+              ptr[0], ptr[1], ptr[2], st)
+
+
+def _score_views(smaps, h, w):
+    return {k: v.view(h, w) for k, v in smaps.items()}
+
+
+def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm=None, return_sums=False, flavour="isprs",
+                 scores=None):
     """The inner loop of validate_test / generate_final_maps (isprs:1261-1284, 1925-1949) for one tile: windows at
     stride floor(s/2) (isprs:1243), logits overlap-added in window order, arg-max of the average.  Returns the
     uint8 label map as a DEVICE tensor [h, w].  Under data parallelism batches of windows go round-robin over the
-    ranks and the partial sums are added (sum all-reduce of prob / occur)."""
+    ranks and the partial sums are added (sum all-reduce of prob / occur).
+    scores (opt-in; a tuple of kinds from patches.SCORE_KINDS; not with return_sums): the return value is followed by a dict
+    {kind: uint8 device tensor [h, w]} of per-pixel score maps of the averaged logits (drs_stitch_finalize_scores)."""
     from . import _lib
     comm = comm or NoComm()
     h, w = pool.h[map_index], pool.w[map_index]
@@ -450,8 +488,13 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
     stride = int(math.floor(crop_size / 2.0))
     n_h, n_w = P.window_counts(h, w, crop_size, stride)
     total = n_h * n_w
+    scores = _check_scores(scores, return_sums)
     if comm.world > 1 and not return_sums and flavour == "isprs" and n_h >= comm.world:
+        if scores is not None:
+            out, sm = _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=scores)
+            return out, total, sm
         return _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm), total
+    smaps = _score_buffers(scores, h * w, net.dev)
     prob = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
     occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
     # batches are the REFERENCE's: batch i starts where its `batch_size` puts it (for flavour="contest" that start depends on the
@@ -476,7 +519,9 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
     if return_sums:
         return prob, occur, total
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _lib.call("drs_stitch_finalize", prob.data_ptr(), occur.data_ptr(), h, w, K, out.data_ptr(), st)
+    _finalize(prob.data_ptr(), occur.data_ptr(), h, w, K, False, out, smaps, 0, st)
+    if smaps is not None:
+        return out.view(h, w), total, _score_views(smaps, h, w)
     return out.view(h, w), total
 
 
@@ -493,17 +538,20 @@ def band_plan(h, crop_size, stride, n_h, world):
     return a, top, bot, own
 
 
-def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm):
+def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=None):
     """Sliding-window inference of one tile on several ranks: the window rows are cut into one contiguous band per
     rank, every rank overlap-adds its windows into a band-sized accumulator ([rows of the band][w][K] instead of the whole
     [h][w][K]), only the rows a band shares with the next ranks' territory are exchanged (one sum all-reduce of a buffer in which
     every rank fills its own segment: (world-1) x (S - stride) rows instead of the whole map), each rank divides and arg-maxes the
     rows it owns, and the uint8 label bands are gathered.  Sums are formed as (own windows in window order) + (lower ranks'
-    contributions in rank order): deterministic, and equal to the single-rank result up to the association of those float sums."""
+    contributions in rank order): deterministic, and equal to the single-rank result up to the association of those float sums.
+    scores (predict_tile's): every rank also writes the score maps of the rows it owns, gathered like the labels; returns (labels,
+    {kind: map})."""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     S = crop_size
+    smaps = _score_buffers(scores, h * w, net.dev)
     stride = int(math.floor(S / 2.0))
     n_h, n_w = P.window_counts(h, w, S, stride)
     W, r = comm.world, comm.rank
@@ -542,23 +590,32 @@ def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, 
             occur[dst * w:(dst + hi - lo) * w] += xo[src * w:(src + hi - lo) * w]
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
     n_own, d0 = own[r + 1] - own[r], own[r] - top[r]
-    _lib.call("drs_stitch_finalize", prob.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, n_own, w, K, out.data_ptr() + own[r] * w, st)
+    _finalize(prob.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, n_own, w, K, False, out, smaps, own[r] * w, st)
     comm.all_reduce_sum(out)    # every rank wrote only the rows it owns: the sum is the gather of the uint8 label bands
+    if smaps is not None:
+        for v in smaps.values():
+            comm.all_reduce_sum(v)
+        return out.view(h, w), _score_views(smaps, h, w)
     return out.view(h, w)
 
 
-def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_full, std_full, comm=None):
-    """isprs:1347-1474 inner part: for every scale the averaged-logit map, softmax over classes, summed; arg-max."""
+def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_full, std_full, comm=None, scores=None):
+    """isprs:1347-1474 inner part: for every scale the averaged-logit map, softmax over classes, summed; arg-max.
+    scores (predict_tile's): returns (labels, {kind: map}); the maps are of the MEAN of the scales' softmax vectors (the sum divided by
+    the number of scales, which leaves the arg-max where it is)."""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
+    smaps = _score_buffers(scores, h * w, net.dev)
     acc = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
     for s_ in crop_sizes:
         prob, occur, _ = predict_tile(net, pool, map_index, int(s_), batch_size, mean_full, std_full, comm, return_sums=True)
         _lib.call("drs_softmax_accumulate", prob.data_ptr(), occur.data_ptr(), h, w, K, acc.data_ptr(), net._stream())
-    ones = torch.ones(h * w, dtype=torch.int32, device=net.dev)
+    ones = torch.full((h * w,), 1 if smaps is None else len(crop_sizes), dtype=torch.int32, device=net.dev)
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _lib.call("drs_stitch_finalize", acc.data_ptr(), ones.data_ptr(), h, w, K, out.data_ptr(), net._stream())
+    _finalize(acc.data_ptr(), ones.data_ptr(), h, w, K, True, out, smaps, 0, net._stream())
+    if smaps is not None:
+        return out.view(h, w), _score_views(smaps, h, w)
     return out.view(h, w)
 
 
@@ -619,7 +676,7 @@ def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g=0):
 
 
 def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None,
-                       scales=None, se=None):
+                       scales=None, se=None, scores=None):
     """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
     size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
     pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
@@ -643,9 +700,13 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     sums its activated output over the cores in fp64 (_se_global_gates); the last sweep is the full forward with every gate.  The
     margin is the field with the SE layers as constants (Plan.gated_receptive_field).  The net is not equivariant (asymmetric SAME
     pads, unsymmetric filters), so the activation means of a flipped or rotated image are not those of the image: with tta every
-    code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale."""
+    code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale.
+    scores (opt-in; a tuple of kinds from patches.SCORE_KINDS; not with return_sums): the return value is followed by a dict
+    {kind: uint8 device tensor [h, w]} of per-pixel score maps (drs_stitch_finalize_scores): of the logits on the plain
+    path, of the mean probability vector with tta or scales.  Under data parallelism they are gathered as the labels are."""
     from . import _lib
     comm = comm or NoComm()
+    scores = _check_scores(scores, return_sums)
     if se is not None and se not in DENSE_SE_MODES:
         raise ValueError("se must be None or one of %s, not %r" % (list(DENSE_SE_MODES), se))
     if se is not None and not net.plan.se:
@@ -661,9 +722,10 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
         before = after = max(before, after)
     if scales is not None:
         return _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G,
-                                          P.check_scales(scales), before, after, se)
+                                          P.check_scales(scales), before, after, se, scores)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
+    smaps = _score_buffers(scores, h * w, net.dev)
     T = int(tile) if tile else min(h, w, DENSE_TILE)
     oy, ys, ye = P.dense_axis(h, T, before, after)
     boxes = P.dense_tiles(h, w, T, before, after)
@@ -710,15 +772,19 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     own0 = ys[a[r]] if a[r] < len(oy) else h
     own1 = ys[a[r + 1]] if a[r + 1] < len(oy) else h
     if own1 > own0:
-        _lib.call("drs_stitch_finalize", prob.data_ptr() + own0 * w * K * 4, occur.data_ptr() + own0 * w * 4, own1 - own0, w, K,
-                  out.data_ptr() + own0 * w, st)
+        _finalize(prob.data_ptr() + own0 * w * K * 4, occur.data_ptr() + own0 * w * 4, own1 - own0, w, K, G is not None, out, smaps,
+                  own0 * w, st)
     if W > 1:
         comm.all_reduce_sum(out)    # every rank wrote only the rows its cores own: the sum is the gather of the label bands
+        for v in (smaps or {}).values():
+            comm.all_reduce_sum(v)
+    if smaps is not None:
+        return out.view(h, w), len(boxes), _score_views(smaps, h, w)
     return out.view(h, w), len(boxes)
 
 
 def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after,
-                               se=None):
+                               se=None, scores=None):
     """predict_tile_dense with scales.  For each scale s, in the order given: the map resampled to hs x ws
     (patches.scaled_size; bilinear, half-pixel centres) is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) --
     each tile cropped from the source map by one fused gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its
@@ -728,10 +794,12 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
     occur = len(scales)) on every rank.  Returns (labels, total tile count), or (acc, occur, total tile count) with return_sums.
     One inference twin, sized once for max T_s, runs every scale's tiles.  With se (predict_tile_dense's) every scale is
     an image of its own, and so is every code of tta: gates from sweeps over the scale's hs x ws grid (tiles transformed by the code),
-    before that code's full forwards."""
+    before that code's full forwards.  scores (predict_tile_dense's): every rank holds the whole acc, so every rank makes the whole
+    score maps beside the labels; nothing is gathered."""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
+    smaps = _score_buffers(scores, h * w, net.dev)
     plans = []
     for s in scales:
         hs, ws = P.scaled_size(h, s), P.scaled_size(w, s)
@@ -785,7 +853,9 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
     if return_sums:
         return acc, occur, n_tiles
     out = torch.empty(h * w, dtype=torch.uint8, device=net.dev)
-    _lib.call("drs_stitch_finalize", acc.data_ptr(), occur.data_ptr(), h, w, K, out.data_ptr(), st)
+    _finalize(acc.data_ptr(), occur.data_ptr(), h, w, K, True, out, smaps, 0, st)
+    if smaps is not None:
+        return out.view(h, w), n_tiles, _score_views(smaps, h, w)
     return out.view(h, w), n_tiles
 
 
@@ -833,20 +903,37 @@ def _check_dense_se(dense_tile, dense_se):
         raise ValueError("dense_se must be one of %s, not %r" % (list(DENSE_SE_MODES), dense_se))
 
 
+def _calibration_str(cal):
+    return ("Calibration ECE= " + "{:.6f}".format(cal["ece"]) + " MCE= " + "{:.6f}".format(cal["mce"]) +
+            " Mean Confidence= " + "{:.6f}".format(cal["mean_confidence"]) + " Accuracy= " + "{:.6f}".format(cal["accuracy"]))
+
+
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None, dense_scales=None, dense_se=None):
+                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
     ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
     dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales).
-    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se)."""
+    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se).
+    score_maps (opt-in; a tuple of kinds from patches.SCORE_KINDS; any inference path): per-pixel score maps beside the labels and a
+    calibration report.  "confidence" is computed whether asked for or not: the report needs it.  Per map, and for all
+    maps, one line `---- Iter N -- Test Map M: Calibration ECE= ... MCE= ... Mean Confidence= ... Accuracy= ...` follows the
+    reference-format line, which stays as it is; the pixels are those the confusion matrix counts.  Returns (all-maps confusion
+    matrix, label maps, extra) with extra = {"scores": [per map {kind: uint8 numpy [h, w]}], "reliability": the all-maps table
+    [256][2] (drs_reliability_histogram), "calibration": metrics.calibration of it, plus "per_map": [the same per map]}."""
     from . import _lib
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
     _check_dense_se(dense_tile, dense_se)
+    kinds = None
+    if score_maps is not None:
+        kinds = P.check_score_kinds(score_maps)
+        kinds = kinds if "confidence" in kinds else kinds + ("confidence",)
+        all_hist = np.zeros((256, 2), dtype=np.int64)
+        score_list, cal_list = [], []
     K = net.plan.K
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
@@ -858,12 +945,15 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                         scales=dense_scales, se=dense_se)
+            res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
+                                     scales=dense_scales, se=dense_se, scores=kinds)
+            (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
-            pred = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm)
+            res = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, scores=kinds)
+            pred, smaps = (res, None) if kinds is None else res
         else:
-            pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour)
+            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour, scores=kinds)
+            (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         h, w = pool.h[k], pool.w[k]
         conf = torch.zeros(K * K, dtype=torch.int32, device=net.dev)
         lab = pool.labels[int(pool.lab_off[k].item()):int(pool.lab_off[k].item()) + h * w]
@@ -886,6 +976,16 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
                   " F1 Score= " + "{:.4f}".format(all_f1[k]) +
                   " Kappa= " + "{:.4f}".format(all_kappa[k]) +
                   " Confusion Matrix= " + _cm_str(cm))
+        if kinds is not None:
+            hist = torch.zeros(512, dtype=torch.int64, device=net.dev)
+            _lib.call("drs_reliability_histogram", lab.data_ptr(), pred.data_ptr(), smaps["confidence"].data_ptr(), h * w, K, ignore_label,
+                      hist.data_ptr(), net._stream())
+            hist = hist.cpu().numpy().reshape(256, 2)
+            all_hist += hist
+            score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})
+            cal_list.append(MT.calibration(hist))
+            if comm.rank == 0:
+                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _calibration_str(cal_list[-1]))
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -898,22 +998,33 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
               " Kappa= " + np.array_str(all_kappa).replace("\n", " ") +
               " Mean Kappa Score= " + "{:.6f}".format(np.sum(all_kappa) / float(len(testing_data))) +
               " Confusion Matrix= " + _cm_str(all_cm))
+    if kinds is not None:
+        cal = MT.calibration(all_hist)
+        cal["per_map"] = cal_list
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _calibration_str(cal))
+        return all_cm, maps, {"scores": score_list, "reliability": all_hist, "calibration": cal}
     return all_cm, maps
 
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None):
+                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
     ("flip", "d4" or a tuple of codes; with dense_tile only): its dihedral test-time augmentation (predict_tile_dense's tta).
     dense_scales (a list of factors; with dense_tile only): its multi-scale test-time augmentation (predict_tile_dense's scales).
-    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se)."""
+    dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se).
+    score_maps (opt-in; a tuple of kinds from patches.SCORE_KINDS; any inference path): per-pixel score maps written
+    beside each label file as `<stem>_<kind>.npy` (uint8 [h, w]) and an 8-bit grey `<stem>_<kind>.tif`, by rank 0 as the labels are;
+    returns (label maps, [per map {kind: uint8 numpy [h, w]}])."""
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
     _check_dense_se(dense_tile, dense_se)
+    kinds = None if score_maps is None else P.check_score_kinds(score_maps)
+    score_list = []
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
         crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
@@ -922,11 +1033,14 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     maps = []
     for k in range(len(testing_data)):
         if dense_tile is not None:
-            pred, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                         scales=dense_scales, se=dense_se)
+            res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
+                                     scales=dense_scales, se=dense_se, scores=kinds)
         else:
-            pred, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm)
+            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, scores=kinds)
+        (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         maps.append(pred.cpu().numpy())
+        if kinds is not None:
+            score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})
         if comm.rank == 0 and output_path:
             # isprs:1950-1955: the colour map under the reference's file names (ISPRS palette, isprs:118-139), plus the class ids as .npy
             from . import datasets
@@ -934,4 +1048,11 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
                     else "top_potsdam_" + str(testing_instances[k]) + "_label")
             datasets.create_prediction_map(output_path + stem + ".tif", maps[-1])
             np.save(output_path + stem + ".npy", maps[-1])
+            if kinds is not None:
+                from PIL import Image
+                for kd, v in score_list[-1].items():
+                    np.save(output_path + stem + "_" + kd + ".npy", v)
+                    Image.fromarray(v).save(output_path + stem + "_" + kd + ".tif")
+    if kinds is not None:
+        return maps, score_list
     return maps

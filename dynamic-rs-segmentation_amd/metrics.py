@@ -43,3 +43,38 @@ def cohen_kappa(cm):
     po = np.trace(cm) / n
     pe = float((cm.sum(axis=0) * cm.sum(axis=1)).sum()) / (n * n)
     return float((po - pe) / (1 - pe)) if pe != 1 else 0.0
+
+
+def calibration(hist, bins=15):
+    """Calibration scores from a reliability table (drs_reliability_histogram): hist [256][2] integers, hist[c] = (pixels whose
+    confidence byte is c, those of them predicted right).  The confidence of byte c is c / 255; the bins are `bins` equal-width
+    intervals of [0, 1], bin b = [b / bins, (b + 1) / bins), the last one closed (byte c falls into min(c * bins // 255, bins - 1)).
+    With n_b, conf_b, acc_b the pixel count, mean confidence and accuracy of bin b and N = sum n_b:
+      ece = sum_b (n_b / N) |acc_b - conf_b|      (expected calibration error)
+      mce = max over non-empty b of |acc_b - conf_b|
+    Returns {"ece", "mce", "mean_confidence", "accuracy", "count", "bins": [{"lo", "hi", "count", "confidence", "accuracy"}, ...]};
+    an empty table gives zeros (and zeros in the empty bins)."""
+    h = np.asarray(hist)
+    bins = int(bins)
+    if h.shape != (256, 2) or not np.issubdtype(h.dtype, np.integer) or np.any(h < 0) or np.any(h[:, 1] > h[:, 0]):
+        raise ValueError("reliability table: expected [256][2] non-negative integers with hist[c][1] <= hist[c][0]")
+    if bins < 1:
+        raise ValueError("calibration: bins must be >= 1, not %r" % bins)
+    n = h[:, 0].astype(np.float64)
+    right = h[:, 1].astype(np.float64)
+    conf = np.arange(256, dtype=np.float64) / 255.0
+    which = np.minimum(np.arange(256) * bins // 255, bins - 1)
+    n_b = np.bincount(which, weights=n, minlength=bins)
+    c_b = np.bincount(which, weights=n * conf, minlength=bins)
+    r_b = np.bincount(which, weights=right, minlength=bins)
+    total = float(n.sum())
+    some = n_b > 0
+    den = np.where(some, n_b, 1.0)
+    conf_b, acc_b = np.where(some, c_b / den, 0.0), np.where(some, r_b / den, 0.0)
+    gap = np.abs(acc_b - conf_b)
+    table = [{"lo": b / float(bins), "hi": (b + 1) / float(bins), "count": int(n_b[b]), "confidence": float(conf_b[b]),
+              "accuracy": float(acc_b[b])} for b in range(bins)]
+    if total == 0:
+        return {"ece": 0.0, "mce": 0.0, "mean_confidence": 0.0, "accuracy": 0.0, "count": 0, "bins": table}
+    return {"ece": float((n_b / total * gap).sum()), "mce": float(gap[some].max()), "mean_confidence": float(c_b.sum() / total),
+            "accuracy": float(r_b.sum() / total), "count": int(total), "bins": table}

@@ -315,6 +315,33 @@ def parse_focal_gamma(text):
     return check_focal_gamma(v)
 
 
+# ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
+SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores
+
+
+def check_score_kinds(kinds):
+    """The score maps asked of an inference path as a tuple of names in the order given: a non-empty tuple / list of distinct names
+    from SCORE_KINDS.  Anything else raises ValueError."""
+    if isinstance(kinds, (str, bytes)) or not isinstance(kinds, (tuple, list)) or not kinds:
+        raise ValueError("score maps %r: expected a non-empty tuple of names from %s" % (kinds, "|".join(SCORE_KINDS)))
+    for k in kinds:
+        if k not in SCORE_KINDS:
+            raise ValueError("score map %r: expected one of %s" % (k, "|".join(SCORE_KINDS)))
+    if len(set(kinds)) != len(kinds):
+        raise ValueError("score maps %r: a name is given twice" % (tuple(kinds),))
+    return tuple(kinds)
+
+
+def parse_score_maps(text):
+    """The value of the command line's --score-maps option: "confidence,entropy" as a tuple of names (check_score_kinds).  An empty
+    value, blanks, an unknown or a repeated name raise ValueError."""
+    names = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else None
+    if not names or any(n not in SCORE_KINDS for n in names) or len(set(names)) != len(names):
+        raise ValueError("score maps %r: expected distinct names from %s, comma-separated (e.g. confidence,entropy)"
+                         % (text, "|".join(SCORE_KINDS)))
+    return tuple(names)
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

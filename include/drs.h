@@ -254,6 +254,12 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
  * labels equal to void_label (-1: none) or >= K; counts = K 64-bit counters on the device, ADDED to (integer atomics: exact and
  * order-independent), so the maps of a pool accumulate over several calls.  n < 2^40. */
 int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_label, unsigned long long* counts, void* stream);
+/* reliability table of a prediction (the calibration report, metrics.calibration): for every i < n with truth[i] != ignore_label
+ * and truth[i] < K: hist[confidence[i]][0] += 1 and hist[confidence[i]][1] += (pred[i] == truth[i]).  hist = [256][2] 64-bit
+ * counters on the device, ADDED to (integer atomics: exact and order-independent), so the maps of a split accumulate.  A prediction
+ * >= K counts as wrong (drs_confusion leaves such a pixel out; a finalised map holds none).  K <= 8, n < 2^40. */
+int drs_reliability_histogram(const unsigned char* truth, const unsigned char* pred, const unsigned char* confidence, size_t n, int K,
+                              int ignore_label, unsigned long long* hist, void* stream);
 
 /* fixed-order column sums (scratch: drs_colsum_scratch_doubles(ncols) doubles) / scalar sums used on the slabs above */
 int drs_rows_reduce_f32(const float* in, int nrows, int ncols, float* out, double* scratch, void* stream);
@@ -350,6 +356,21 @@ int drs_crop_resampled(const void* tiles, int tiles_are_f64, const long long* ti
                        float* out, void* stream);
 int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs, int ws, int K, int src_is_prob, int h, int w, float* acc,
                             void* stream);
+/* per-pixel score maps beside the labels (opt-in): drs_stitch_finalize in one pass with up to three uint8 maps.
+ * Per pixel i: oc = occur[i] ? occur[i] : 1, v_k = sums[i][k] / oc.
+ *   labels[i]      what drs_stitch_finalize writes: the first maximum of the fp64 quotients (bit for bit)
+ *   p              sums_are_prob == 0 (sums of logits): the max-subtracted fp32 softmax of v, as drs_resample_accumulate forms it;
+ *                  sums_are_prob != 0 (sums of probabilities): p_k = v_k, not renormalised
+ *   confidence[i]  p[label]
+ *   margin[i]      p[label] - max over k != label of p_k              (K == 1: p[label])
+ *   entropy[i]     -sum_k p_k ln p_k / ln K, 0 ln 0 = 0; for logits formed as (ln se - sum_k p_k (v_k - max)) / ln K with se the sum of
+ *                  the exponentials, so that no logarithm of an underflowed p_k is taken   (K == 1: 0)
+ * Each score s is clamped to [0, 1] and stored as (unsigned char)(int)(255 s + 0.5f).  An uncovered pixel (occur[i] == 0) gets its
+ * label as before and confidence 0, margin 0, entropy 255.  Any of the four outputs may be NULL (it is then neither computed for nor
+ * written); all four NULL is DRS_ERR_ARG.  K <= 8. */
+int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob,
+                               unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
+                               void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);
