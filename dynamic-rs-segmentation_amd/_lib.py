@@ -59,6 +59,8 @@ SIGNATURES = {
                                        _p, _p, _p]),
     "drs_label_histogram": (_i, [_p, _sz, _i, _i, _p, _p]),
     "drs_reliability_histogram": (_i, [_p, _p, _p, _sz, _i, _i, _p, _p]),
+    "drs_temperature_scratch_doubles": (_sz, [_sz]),
+    "drs_temperature_stats": (_i, [_p, _p, _p, _sz, _i, _i, _i, _d, _p, _p, _p]),
     "drs_rows_reduce_f32": (_i, [_p, _i, _i, _p, _p, _p]),
     "drs_sum_f64": (_i, [_p, _i, _p, _p]),
     "drs_l2_loss": (_i, [_p, _sz, _p, _p, _p]),
@@ -69,6 +71,7 @@ SIGNATURES = {
     "drs_stitch_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drs_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_stitch_finalize_scores": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "drs_stitch_finalize_scores_t": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p]),
     "drs_tile_place": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "drs_crop_dihedral": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "drs_tile_place_dihedral": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),

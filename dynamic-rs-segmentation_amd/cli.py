@@ -15,6 +15,11 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
   + optionally, anywhere, `--score-maps=confidence,margin,entropy` (validate_test / generate_final_maps; with or without --dense-tile and
     its companions): per-pixel uint8 score maps beside the labels -- written as `<stem>_<kind>.npy` / `.tif` by generate_final_maps --
     and, in validate_test, a calibration line per map (loops.validate_test's / generate_final_maps' score_maps)
+  + optionally, anywhere, with --score-maps only, `--calibrate-temperature` (validate_test): temperature scaling: one
+    scalar is fitted on the test maps by a first inference pass (loops.fit_temperature), printed, written to
+    `<output_path>temperature_step_<N>.npy` (one float32, beta = 1 / T), and validate_test then reports with it
+  + optionally, anywhere, with --score-maps only, `--temperature=auto|<T>` (validate_test / generate_final_maps): the score maps are
+    of the probabilities at temperature T > 0; `auto` loads the file --calibrate-temperature wrote for the step being evaluated
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -159,6 +164,52 @@ def parse_score_maps(argv):
     return (list(argv) if kinds is None else rest), kinds
 
 
+CALIBRATE_FLAG = "--calibrate-temperature"
+TEMPERATURE_FLAG = "--temperature"
+
+
+def parse_calibrate_temperature(argv):
+    """isprs flavour: the optional bare `--calibrate-temperature` (anywhere in argv; validate_test with --score-maps, which main
+    checks).  Returns (argv without the flag, True), or (argv unchanged, None) without it.  A value, or the flag given twice, raises
+    ValueError."""
+    rest, on = [], None
+    for a in argv:
+        if a != CALIBRATE_FLAG and not a.startswith(CALIBRATE_FLAG + "="):
+            rest.append(a)
+            continue
+        if a != CALIBRATE_FLAG:
+            raise ValueError("%s: %s takes no value" % (a, CALIBRATE_FLAG))
+        if on is not None:
+            raise ValueError(CALIBRATE_FLAG + " given more than once")
+        on = True
+    return (list(argv) if on is None else rest), on
+
+
+def parse_temperature(argv):
+    """isprs flavour: the optional `--temperature=auto|T` (anywhere in argv; validate_test / generate_final_maps with --score-maps,
+    which main checks).  Returns (argv without the flag, "auto" or the inverse temperature beta = 1 / T; patches.parse_temperature), or
+    (argv unchanged, None) without it.  A bare flag, a value that is neither, or the flag given twice, raises ValueError."""
+    rest, beta = [], None
+    for a in argv:
+        if a != TEMPERATURE_FLAG and not a.startswith(TEMPERATURE_FLAG + "="):
+            rest.append(a)
+            continue
+        if beta is not None:
+            raise ValueError(TEMPERATURE_FLAG + " given more than once")
+        try:
+            beta = P.parse_temperature(a[len(TEMPERATURE_FLAG) + 1:])
+        except ValueError:
+            raise ValueError("%s: expected %s=auto or %s=T with a temperature T > 0, 1/64 <= 1/T <= 64"
+                             % (a, TEMPERATURE_FLAG, TEMPERATURE_FLAG)) from None
+    return (list(argv) if beta is None else rest), beta
+
+
+def temperature_file(output_path, step):
+    """where --calibrate-temperature writes, and --temperature=auto reads, the fitted inverse temperature of a step: beside the size
+    scores (patch_acc_loss_step_<N>.npy)"""
+    return output_path + "temperature_step_" + str(step) + ".npy"
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -264,6 +315,8 @@ def main(argv=None, device=None, comm=None):
         argv, dense_scales = parse_dense_scales(argv)
         argv, dense_se = parse_dense_se(argv)
         argv, score_maps = parse_score_maps(argv)
+        argv, calibrate = parse_calibrate_temperature(argv)
+        argv, temperature = parse_temperature(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
     except ValueError as e:
@@ -274,12 +327,22 @@ def main(argv=None, device=None, comm=None):
         sys.exit(DENSE_SCALES_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if dense_se is not None and dense_tile is None:
         sys.exit(DENSE_SE_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
+    if calibrate is not None and score_maps is None:
+        sys.exit(CALIBRATE_FLAG + " applies to the score maps only: give --score-maps as well")
+    if temperature is not None and score_maps is None:
+        sys.exit(TEMPERATURE_FLAG + " applies to the score maps only: give --score-maps as well")
+    if calibrate is not None and temperature is not None:
+        sys.exit(CALIBRATE_FLAG + " fits the temperature it reports with: " + TEMPERATURE_FLAG + " cannot be given as well")
     if len(argv) < len(ISPRS_PARAMS) + 1:
         sys.exit("Usage: " + argv[0] + " " + " ".join(ISPRS_PARAMS))
     if dense_tile is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(DENSE_TILE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if score_maps is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(SCORE_MAPS_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if calibrate is not None and argv[16] != "validate_test":
+        sys.exit(CALIBRATE_FLAG + " applies to the validate_test process only")
+    if temperature is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(TEMPERATURE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -343,17 +406,35 @@ def main(argv=None, device=None, comm=None):
     s_max = max(values)
     net = DilatedNet(net_type, training_data[0].shape[-1], 6, weight_decay, b_max=batch_size, s_max=s_max, device=device, comm=comm)
     loops.load_checkpoint(net, former_model_path)
+    if temperature == "auto":
+        if not os.path.isfile(temperature_file(output_path, step)):
+            sys.exit(TEMPERATURE_FLAG + "=auto: " + temperature_file(output_path, step) + " is missing (written by validate_test with "
+                     + CALIBRATE_FLAG + ")")
+        try:
+            temperature = P.check_temperature_beta(float(np.load(temperature_file(output_path, step)).reshape(-1)[0]))
+        except (ValueError, IndexError) as e:
+            sys.exit(TEMPERATURE_FLAG + "=auto: " + temperature_file(output_path, step) + ": " + str(e))
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
+        if calibrate:
+            fit = loops.fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, std_full, crop, comm,
+                                        dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+            temperature = fit["beta"]
+            if comm.rank == 0:
+                print("---- Iter " + str(step) + " -- Temperature= " + "{:.6f}".format(fit["temperature"]) +
+                      " Beta= " + "{:.6f}".format(fit["beta"]) + " NLL before= " + "{:.6f}".format(fit["nll_before"]) +
+                      " after= " + "{:.6f}".format(fit["nll_after"]) + " Pixels= " + str(fit["count"]) +
+                      " Iterations= " + str(fit["iterations"]))
+                np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
                                    step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
-                                   score_maps=score_maps)
+                                   score_maps=score_maps, temperature_beta=temperature)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
                                          dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
-                                         score_maps=score_maps)
+                                         score_maps=score_maps, temperature_beta=temperature)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -13,6 +13,7 @@
 // pass exists.  Arithmetic on pixel values is fp64 (the reference normalises float64 patches, then feeds float32),
 // rounded once to fp32 on the store, so the result is bit-identical to the reference's feed.
 #include "drs_common.hpp"
+#include <cfloat>
 
 // Everything in this file restates host arithmetic that the reference does in numpy / scipy and is held to it BIT FOR BIT: no
 // multiply-add may be fused.  hipcc contracts a * b + c into an fma by default, and HIP's __dmul_rn / __dadd_rn are no
@@ -514,6 +515,80 @@ __global__ void score_maps_kernel(const float* __restrict__ sums, const unsigned
   }
 }
 
+// score_maps_kernel at an inverse temperature beta != 1 (include/drs.h: drs_stitch_finalize_scores_t): a sibling
+// kernel, so that score_maps_kernel and its register figures stay what they are.  The label is the same expression; the scores are
+// of p = softmax(beta v), v the quotients (logits) or the logarithm of the quotients clamped at FLT_MIN (probabilities).  t = beta v
+// is rounded to fp32 before the maximum is subtracted (__fmul_rn keeps the product out of a fused multiply-subtract), so that the
+// kernel's t is the one an fp32 product gives.  Renormalised in both modes; the entropy is the logits' form of score_maps_kernel.
+template <int K>
+__global__ void score_maps_t_kernel(const float* __restrict__ sums, const unsigned int* __restrict__ occur, size_t npix, int sums_are_prob,
+                                    float beta, unsigned char* __restrict__ labels, unsigned char* __restrict__ confidence,
+                                    unsigned char* __restrict__ margin, unsigned char* __restrict__ entropy) {
+  const bool want_scores = confidence || margin || entropy;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned o = occur[i];
+    const unsigned oc = o ? o : 1u;
+    float s[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = sums[i * K + k];
+    int am = 0;
+    double best = (double)s[0] / (double)oc;
+#pragma unroll
+    for (int k = 1; k < K; ++k) {
+      const double v = (double)s[k] / (double)oc;
+      if (v > best) { best = v; am = k; }
+    }
+    if (labels) labels[i] = (unsigned char)am;
+    if (!want_scores) continue;
+    if (!o) {          // no window or tile reached this pixel: nothing is known about it
+      if (confidence) confidence[i] = 0;
+      if (margin) margin[i] = 0;
+      if (entropy) entropy[i] = 255;
+      continue;
+    }
+    const float ocf = (float)oc;
+    float t[K], p[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float q = s[k] / ocf;
+      t[k] = __fmul_rn(beta, sums_are_prob ? logf(fmaxf(q, FLT_MIN)) : q);
+    }
+    float mx = t[0], se = 0.f;
+#pragma unroll
+    for (int k = 1; k < K; ++k) mx = fmaxf(mx, t[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      t[k] = t[k] - mx;
+      p[k] = expf(t[k]);
+      se += p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) p[k] = p[k] / se;
+    float top = p[0], second = 0.f;
+#pragma unroll
+    for (int k = 1; k < K; ++k) top = k == am ? p[k] : top;
+    bool first = true;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (k == am) continue;
+      second = first ? p[k] : fmaxf(second, p[k]);
+      first = false;
+    }
+    if (confidence) confidence[i] = score_byte(top);
+    if (margin) margin[i] = score_byte(top - second);
+    if (entropy) {
+      float hn = 0.f;          // one class: the entropy is 0, and so is its normalised form here
+      if (K > 1) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc += p[k] * t[k];
+        hn = (logf(se) - acc) / logf((float)K);
+      }
+      entropy[i] = score_byte(hn);
+    }
+  }
+}
+
 // multi-scale evaluation (isprs:1347-1474): per scale, softmax over classes of the averaged logits, summed over scales
 __global__ void softmax_accumulate_kernel(const float* __restrict__ prob, const unsigned int* __restrict__ occur, size_t npix, int K,
                                           float* __restrict__ acc) {
@@ -662,6 +737,30 @@ int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int
     DRS_SCORES_CASE(5) DRS_SCORES_CASE(6) DRS_SCORES_CASE(7) DRS_SCORES_CASE(8)
   }
 #undef DRS_SCORES_CASE
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta,
+                                 unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
+                                 void* stream) {
+  if (!(beta >= 1.0f / 64.0f && beta <= 64.0f)) return DRS_ERR_ARG;          // (a NaN fails both comparisons)
+  if (beta == 1.0f) return drs_stitch_finalize_scores(sums, occur, h, w, K, sums_are_prob, labels, confidence, margin, entropy, stream);
+  if (!sums || !occur || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
+  if (!labels && !confidence && !margin && !entropy) return DRS_ERR_ARG;
+  const size_t n = (size_t)h * w;
+  const size_t nb = (n + 255) / 256;
+  const dim3 grid(nb < 4096 ? (unsigned)nb : 4096u);
+  const int prob = sums_are_prob ? 1 : 0;
+#define DRS_SCORES_T_CASE(KK)                                                                                                      \
+  case KK:                                                                                                                         \
+    DRS_LAUNCH(score_maps_t_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, beta, labels, confidence,   \
+               margin, entropy);                                                                                                   \
+    break;
+  switch (K) {
+    DRS_SCORES_T_CASE(1) DRS_SCORES_T_CASE(2) DRS_SCORES_T_CASE(3) DRS_SCORES_T_CASE(4)
+    DRS_SCORES_T_CASE(5) DRS_SCORES_T_CASE(6) DRS_SCORES_T_CASE(7) DRS_SCORES_T_CASE(8)
+  }
+#undef DRS_SCORES_T_CASE
   return DRS_LAUNCH_CHECK();
 }
 

@@ -10,6 +10,7 @@
 // so a step is bitwise reproducible.  Everything is channels-last; a thread owns 4 consecutive channels (16-B
 // accesses), consecutive lanes own consecutive channel quads, so every wave access is a run of full cache lines.
 #include "drs_common.hpp"
+#include <cfloat>
 #include <cmath>
 #include <type_traits>
 
@@ -1706,6 +1707,104 @@ __global__ void reliability_histogram_kernel(const unsigned char* __restrict__ t
   }
 }
 
+// Temperature scaling (include/drs.h): the five sufficient statistics (N, L, G, H, A) of the negative log-likelihood
+// of softmax(beta u) at one inverse temperature, over the counted pixels of one map.
+// Stage 1: one thread per pixel, grid-stride; the pixel's K sums are read once into registers (K is a template parameter: the loops
+// unroll, nothing spills), every per-pixel operation is fp64, every thread keeps five fp64 partials.  The 64 lanes of a wave are
+// added by a fixed xor butterfly, the four waves of the workgroup in wave order, and lanes 0..4 of wave 0 write the workgroup's row
+// of scratch[gridDim.x][5] with plain stores.  The grid depends on n alone (temperature_blocks), so two runs add in the same order.
+constexpr int TEMP_MAX_BLOCKS = 1024;
+constexpr int TEMP_STATS = 5;
+
+inline unsigned temperature_blocks(size_t n) {
+  const size_t nb = (n + 255) / 256;
+  return nb < (size_t)TEMP_MAX_BLOCKS ? (unsigned)nb : (unsigned)TEMP_MAX_BLOCKS;
+}
+
+template <int K>
+__global__ void __launch_bounds__(256)
+temperature_stats_kernel(const float* __restrict__ sums, const unsigned int* __restrict__ occur, const unsigned char* __restrict__ truth,
+                         size_t n, int sums_are_prob, int ignore_label, double beta, double* __restrict__ scratch) {
+  __shared__ double sh[4][TEMP_STATS];
+  double part[TEMP_STATS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const unsigned o = occur[i];
+    const int y = truth[i];
+    if (!o || y == ignore_label || y >= K) continue;
+    float s[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = sums[i * K + k];
+    double u[K];
+    if (sums_are_prob) {
+      const float ocf = (float)o;
+#pragma unroll
+      for (int k = 0; k < K; ++k) u[k] = log((double)fmaxf(s[k] / ocf, FLT_MIN));
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) u[k] = (double)s[k] / (double)o;
+    }
+    // (beta u_k is rounded before the maximum is subtracted -- __dmul_rn keeps it out of a fused multiply-subtract -- so that the
+    // largest term is exp(0) and m is the m of the definition)
+    double e[K], uy = u[0];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      e[k] = __dmul_rn(beta, u[k]);
+      uy = k == y ? u[k] : uy;
+    }
+    double m = e[0], se = 0.0;
+#pragma unroll
+    for (int k = 1; k < K; ++k) m = fmax(m, e[k]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      e[k] = exp(e[k] - m);
+      se += e[k];
+    }
+    double mu = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      e[k] = e[k] / se;
+      mu += e[k] * u[k];
+    }
+    double var = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) var += e[k] * ((u[k] - mu) * (u[k] - mu));
+    part[0] += 1.0;
+    part[1] += log(se) + m - __dmul_rn(beta, uy);
+    part[2] += mu - uy;
+    part[3] += var;
+    part[4] += fabs(mu - uy);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < TEMP_STATS; ++j) {
+    double v = part[j];
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
+    if (lane == 0) sh[wave][j] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < TEMP_STATS) {
+    const int j = threadIdx.x;
+    scratch[(size_t)blockIdx.x * TEMP_STATS + j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
+  }
+}
+
+// Stage 2: out[j] += the rows of scratch[rows][5] in a fixed order: workgroup j takes statistic j, thread t adds rows t, t + 256, ...
+// in order, then the 256 partials by sum_f64_kernel's tree
+__global__ void __launch_bounds__(256)
+temperature_stats_l2_kernel(const double* __restrict__ scratch, int rows, double* __restrict__ out) {
+  __shared__ double sh[256];
+  const int j = blockIdx.x;
+  double s = 0.0;
+  for (int r = threadIdx.x; r < rows; r += 256) s += scratch[(size_t)r * TEMP_STATS + j];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[j] += sh[0];
+}
+
 inline int chain_hp() { return drs_chain_level(drs_tl_chain, drs_g_chain_mode) >= 2 ? 1 : 0; }
 
 inline ActView mkview(float* base, int S, int P, int ld, int coff) {
@@ -2029,6 +2128,30 @@ int drs_reliability_histogram(const unsigned char* truth, const unsigned char* p
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(reliability_histogram_kernel, dim3(nb < 1024 ? (unsigned)nb : 1024u), dim3(256), 0, (hipStream_t)stream, truth, pred,
              confidence, n, K, ignore_label, hist);
+  return DRS_LAUNCH_CHECK();
+}
+
+size_t drs_temperature_scratch_doubles(size_t n) { return (size_t)TEMP_STATS * temperature_blocks(n); }
+
+// out[5] += (N, L, G, H, A) of one map at inverse temperature beta (include/drs.h); scratch: drs_temperature_scratch_doubles(n)
+int drs_temperature_stats(const float* sums, const unsigned int* occur, const unsigned char* truth, size_t n, int K, int sums_are_prob,
+                          int ignore_label, double beta, double* scratch, double* out, void* stream) {
+  if (!sums || !occur || !truth || !scratch || !out || K < 1 || K > 8 || n >= ((size_t)1 << 40)) return DRS_ERR_ARG;
+  if (!(beta >= 1.0 / 64.0 && beta <= 64.0)) return DRS_ERR_ARG;          // (a NaN fails both comparisons)
+  if (n == 0) return DRS_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nb = temperature_blocks(n);
+  const int prob = sums_are_prob ? 1 : 0;
+#define DRS_TEMP_CASE(KK)                                                                                                          \
+  case KK:                                                                                                                         \
+    DRS_LAUNCH(temperature_stats_kernel<KK>, dim3(nb), dim3(256), 0, st, sums, occur, truth, n, prob, ignore_label, beta, scratch); \
+    break;
+  switch (K) {
+    DRS_TEMP_CASE(1) DRS_TEMP_CASE(2) DRS_TEMP_CASE(3) DRS_TEMP_CASE(4)
+    DRS_TEMP_CASE(5) DRS_TEMP_CASE(6) DRS_TEMP_CASE(7) DRS_TEMP_CASE(8)
+  }
+#undef DRS_TEMP_CASE
+  DRS_LAUNCH(temperature_stats_l2_kernel, dim3(TEMP_STATS), dim3(256), 0, st, scratch, (int)nb, out);
   return DRS_LAUNCH_CHECK();
 }
 

@@ -456,15 +456,30 @@ def _score_buffers(scores, n, dev):
     return {k: torch.zeros(n, dtype=torch.uint8, device=dev) for k in P.check_score_kinds(scores)}
 
 
-def _finalize(sums_ptr, occur_ptr, rows, w, K, sums_are_prob, out, smaps, pix0, st):
+def _check_temperature(temperature_beta, scores):
+    """The `temperature_beta` argument of an inference path as the float the kernel takes (patches.check_temperature_beta), None without
+    it.  A temperature changes the score maps and nothing else, so it needs `scores`."""
+    if temperature_beta is None:
+        return None
+    if scores is None:
+        raise ValueError("temperature_beta needs score maps (scores / score_maps): a temperature never changes a label")
+    return P.check_temperature_beta(temperature_beta)
+
+
+def _finalize(sums_ptr, occur_ptr, rows, w, K, sums_are_prob, out, smaps, pix0, st, beta=None):
     """Labels of `rows` image rows from their sums (device addresses of the first of those rows) into out[pix0:], by
     drs_stitch_finalize; with score maps (smaps: _score_buffers) by drs_stitch_finalize_scores, which writes the same labels and the
-    maps' bytes at the same offset.  sums_are_prob says what the path accumulated and matters to the scores only."""
+    maps' bytes at the same offset.  sums_are_prob says what the path accumulated and matters to the scores only.
+    beta (an inverse temperature, _check_temperature; with smaps only): the maps are drs_stitch_finalize_scores_t's."""
     from . import _lib
     if smaps is None:
         _lib.call("drs_stitch_finalize", sums_ptr, occur_ptr, rows, w, K, out.data_ptr() + pix0, st)
         return
     ptr = [smaps[k].data_ptr() + pix0 if k in smaps else None for k in P.SCORE_KINDS]
+    if beta is not None:
+        _lib.call("drs_stitch_finalize_scores_t", sums_ptr, occur_ptr, rows, w, K, 1 if sums_are_prob else 0, beta,
+                  out.data_ptr() + pix0, ptr[0], ptr[1], ptr[2], st)
+        return
     _lib.call("drs_stitch_finalize_scores", sums_ptr, occur_ptr, rows, w, K, 1 if sums_are_prob else 0, out.data_ptr() + pix0,
               ptr[0], ptr[1], ptr[2], st)
 
@@ -474,13 +489,15 @@ def _score_views(smaps, h, w):
 
 
 def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm=None, return_sums=False, flavour="isprs",
-                 scores=None):
+                 scores=None, temperature_beta=None):
     """The inner loop of validate_test / generate_final_maps (isprs:1261-1284, 1925-1949) for one tile: windows at
     stride floor(s/2) (isprs:1243), logits overlap-added in window order, arg-max of the average.  Returns the
     uint8 label map as a DEVICE tensor [h, w].  Under data parallelism batches of windows go round-robin over the
     ranks and the partial sums are added (sum all-reduce of prob / occur).
     scores (opt-in; a tuple of kinds from patches.SCORE_KINDS; not with return_sums): the return value is followed by a dict
-    {kind: uint8 device tensor [h, w]} of per-pixel score maps of the averaged logits (drs_stitch_finalize_scores)."""
+    {kind: uint8 device tensor [h, w]} of per-pixel score maps of the averaged logits (drs_stitch_finalize_scores).
+    temperature_beta (opt-in; with scores only): the maps are those of softmax(beta x averaged logits); the labels
+    do not change."""
     from . import _lib
     comm = comm or NoComm()
     h, w = pool.h[map_index], pool.w[map_index]
@@ -489,9 +506,11 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
     n_h, n_w = P.window_counts(h, w, crop_size, stride)
     total = n_h * n_w
     scores = _check_scores(scores, return_sums)
+    beta = _check_temperature(temperature_beta, scores)
     if comm.world > 1 and not return_sums and flavour == "isprs" and n_h >= comm.world:
         if scores is not None:
-            out, sm = _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=scores)
+            out, sm = _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=scores,
+                                          temperature_beta=beta)
             return out, total, sm
         return _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm), total
     smaps = _score_buffers(scores, h * w, net.dev)
@@ -519,7 +538,7 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
     if return_sums:
         return prob, occur, total
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(prob.data_ptr(), occur.data_ptr(), h, w, K, False, out, smaps, 0, st)
+    _finalize(prob.data_ptr(), occur.data_ptr(), h, w, K, False, out, smaps, 0, st, beta)
     if smaps is not None:
         return out.view(h, w), total, _score_views(smaps, h, w)
     return out.view(h, w), total
@@ -538,16 +557,17 @@ def band_plan(h, crop_size, stride, n_h, world):
     return a, top, bot, own
 
 
-def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=None):
+def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=None, temperature_beta=None):
     """Sliding-window inference of one tile on several ranks: the window rows are cut into one contiguous band per
     rank, every rank overlap-adds its windows into a band-sized accumulator ([rows of the band][w][K] instead of the whole
     [h][w][K]), only the rows a band shares with the next ranks' territory are exchanged (one sum all-reduce of a buffer in which
     every rank fills its own segment: (world-1) x (S - stride) rows instead of the whole map), each rank divides and arg-maxes the
     rows it owns, and the uint8 label bands are gathered.  Sums are formed as (own windows in window order) + (lower ranks'
     contributions in rank order): deterministic, and equal to the single-rank result up to the association of those float sums.
-    scores (predict_tile's): every rank also writes the score maps of the rows it owns, gathered like the labels; returns (labels,
-    {kind: map})."""
+    scores, temperature_beta (predict_tile's): every rank also writes the score maps of the rows it owns, gathered like the labels;
+    returns (labels, {kind: map})."""
     from . import _lib
+    beta = _check_temperature(temperature_beta, scores)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     S = crop_size
@@ -590,7 +610,8 @@ def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, 
             occur[dst * w:(dst + hi - lo) * w] += xo[src * w:(src + hi - lo) * w]
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
     n_own, d0 = own[r + 1] - own[r], own[r] - top[r]
-    _finalize(prob.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, n_own, w, K, False, out, smaps, own[r] * w, st)
+    _finalize(prob.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, n_own, w, K, False, out, smaps, own[r] * w, st,
+              beta)
     comm.all_reduce_sum(out)    # every rank wrote only the rows it owns: the sum is the gather of the uint8 label bands
     if smaps is not None:
         for v in smaps.values():
@@ -599,21 +620,28 @@ def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, 
     return out.view(h, w)
 
 
-def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_full, std_full, comm=None, scores=None):
+def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_full, std_full, comm=None, scores=None,
+                            temperature_beta=None, return_sums=False):
     """isprs:1347-1474 inner part: for every scale the averaged-logit map, softmax over classes, summed; arg-max.
     scores (predict_tile's): returns (labels, {kind: map}); the maps are of the MEAN of the scales' softmax vectors (the sum divided by
-    the number of scales, which leaves the arg-max where it is)."""
+    the number of scales, which leaves the arg-max where it is).  temperature_beta (with scores only): the maps are of
+    softmax(beta x log of that mean).  return_sums (not with scores): returns (the summed softmax vectors [h*w*K],
+    occur = the number of scales everywhere) instead, on every rank."""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
+    scores = _check_scores(scores, return_sums)
+    beta = _check_temperature(temperature_beta, scores)
     smaps = _score_buffers(scores, h * w, net.dev)
     acc = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
     for s_ in crop_sizes:
         prob, occur, _ = predict_tile(net, pool, map_index, int(s_), batch_size, mean_full, std_full, comm, return_sums=True)
         _lib.call("drs_softmax_accumulate", prob.data_ptr(), occur.data_ptr(), h, w, K, acc.data_ptr(), net._stream())
-    ones = torch.full((h * w,), 1 if smaps is None else len(crop_sizes), dtype=torch.int32, device=net.dev)
+    ones = torch.full((h * w,), 1 if smaps is None and not return_sums else len(crop_sizes), dtype=torch.int32, device=net.dev)
+    if return_sums:
+        return acc, ones
     out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(acc.data_ptr(), ones.data_ptr(), h, w, K, True, out, smaps, 0, net._stream())
+    _finalize(acc.data_ptr(), ones.data_ptr(), h, w, K, True, out, smaps, 0, net._stream(), beta)
     if smaps is not None:
         return out.view(h, w), _score_views(smaps, h, w)
     return out.view(h, w)
@@ -676,7 +704,7 @@ def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g=0):
 
 
 def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None,
-                       scales=None, se=None, scores=None):
+                       scales=None, se=None, scores=None, temperature_beta=None):
     """Overlap-tile inference of one tile: the whole-tile forward of the net -- one function of the tile, whatever the patch
     size -- computed exactly in tiles of side T (default min(h, w, 512)).  Every block is stride 1, so an output pixel depends on input
     pixels [p - before, p + after] (nets.Plan.receptive_field); the plan (patches.dense_tiles) gives every tile a core at least that
@@ -703,10 +731,13 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale.
     scores (opt-in; a tuple of kinds from patches.SCORE_KINDS; not with return_sums): the return value is followed by a dict
     {kind: uint8 device tensor [h, w]} of per-pixel score maps (drs_stitch_finalize_scores): of the logits on the plain
-    path, of the mean probability vector with tta or scales.  Under data parallelism they are gathered as the labels are."""
+    path, of the mean probability vector with tta or scales.  Under data parallelism they are gathered as the labels are.
+    temperature_beta (opt-in; with scores only): the maps are of softmax(beta u), u the averaged logits on the plain path and the log of
+    the mean probability vector with tta or scales (drs_stitch_finalize_scores_t); the labels do not change."""
     from . import _lib
     comm = comm or NoComm()
     scores = _check_scores(scores, return_sums)
+    beta = _check_temperature(temperature_beta, scores)
     if se is not None and se not in DENSE_SE_MODES:
         raise ValueError("se must be None or one of %s, not %r" % (list(DENSE_SE_MODES), se))
     if se is not None and not net.plan.se:
@@ -722,7 +753,7 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
         before = after = max(before, after)
     if scales is not None:
         return _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G,
-                                          P.check_scales(scales), before, after, se, scores)
+                                          P.check_scales(scales), before, after, se, scores, beta)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     smaps = _score_buffers(scores, h * w, net.dev)
@@ -773,7 +804,7 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     own1 = ys[a[r + 1]] if a[r + 1] < len(oy) else h
     if own1 > own0:
         _finalize(prob.data_ptr() + own0 * w * K * 4, occur.data_ptr() + own0 * w * 4, own1 - own0, w, K, G is not None, out, smaps,
-                  own0 * w, st)
+                  own0 * w, st, beta)
     if W > 1:
         comm.all_reduce_sum(out)    # every rank wrote only the rows its cores own: the sum is the gather of the label bands
         for v in (smaps or {}).values():
@@ -784,7 +815,7 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
 
 
 def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after,
-                               se=None, scores=None):
+                               se=None, scores=None, temperature_beta=None):
     """predict_tile_dense with scales.  For each scale s, in the order given: the map resampled to hs x ws
     (patches.scaled_size; bilinear, half-pixel centres) is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) --
     each tile cropped from the source map by one fused gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its
@@ -794,9 +825,10 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
     occur = len(scales)) on every rank.  Returns (labels, total tile count), or (acc, occur, total tile count) with return_sums.
     One inference twin, sized once for max T_s, runs every scale's tiles.  With se (predict_tile_dense's) every scale is
     an image of its own, and so is every code of tta: gates from sweeps over the scale's hs x ws grid (tiles transformed by the code),
-    before that code's full forwards.  scores (predict_tile_dense's): every rank holds the whole acc, so every rank makes the whole
-    score maps beside the labels; nothing is gathered."""
+    before that code's full forwards.  scores, temperature_beta (predict_tile_dense's): every rank holds the whole acc, so every rank
+    makes the whole score maps beside the labels; nothing is gathered."""
     from . import _lib
+    beta = _check_temperature(temperature_beta, scores)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     smaps = _score_buffers(scores, h * w, net.dev)
@@ -853,7 +885,7 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
     if return_sums:
         return acc, occur, n_tiles
     out = torch.empty(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(acc.data_ptr(), occur.data_ptr(), h, w, K, True, out, smaps, 0, st)
+    _finalize(acc.data_ptr(), occur.data_ptr(), h, w, K, True, out, smaps, 0, st, beta)
     if smaps is not None:
         return out.view(h, w), n_tiles, _score_views(smaps, h, w)
     return out.view(h, w), n_tiles
@@ -908,9 +940,69 @@ def _calibration_str(cal):
             " Mean Confidence= " + "{:.6f}".format(cal["mean_confidence"]) + " Accuracy= " + "{:.6f}".format(cal["accuracy"]))
 
 
+FIT_RESIDENT_BYTES = 32 << 30       # default cap on the accumulators fit_temperature keeps on the device
+
+
+def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, std_full, crop_size, comm=None, pool=None, ignore_label=6,
+                    crop_sizes=None, flavour="isprs", dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None,
+                    max_resident_bytes=FIT_RESIDENT_BYTES, lo=P.BETA_MIN, hi=P.BETA_MAX, max_iter=60):
+    """Fit the one scalar of temperature scaling on labelled maps, for the inference path the arguments name (those of
+    validate_test).  One inference pass: per map the path's own accumulators (return_sums: the whole sums and occur on every rank) stay
+    on the device, 4 (K + 1) bytes per pixel; a split that needs more than max_resident_bytes raises ValueError, naming the need.  Then
+    metrics.fit_temperature, every evaluation one drs_temperature_stats launch per map into one zeroed [5], in the mode the path
+    accumulates in (8a.4's table; occur = len(crop_sizes) for the multi-size windows).  The counted pixels are the confusion matrix's,
+    less the uncovered ones.  Under data parallelism every rank computes the same statistics; the ranks check that they agree on
+    beta's float32 bits (comm.agree), no other collective is added.  Returns metrics.fit_temperature's dict, beta rounded to the
+    float32 the kernels take."""
+    from . import _lib
+    comm = comm or NoComm()
+    _check_dense_tta(dense_tile, dense_tta)
+    _check_dense_scales(dense_tile, dense_scales)
+    _check_dense_se(dense_tile, dense_se)
+    if dense_tile is not None and crop_sizes:
+        raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
+    if testing_labels is None and pool is None:
+        raise ValueError("fit_temperature needs labelled maps")
+    K = net.plan.K
+    pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
+    need = sum(4 * (K + 1) * pool.h[k] * pool.w[k] for k in range(len(testing_data)))
+    if need > max_resident_bytes:
+        raise ValueError("fit_temperature keeps the accumulators of the whole split on the device: %d bytes (4 (K + 1) per pixel) "
+                         "exceed max_resident_bytes = %d" % (need, max_resident_bytes))
+    kept = []
+    for k in range(len(testing_data)):
+        if dense_tile is not None:
+            sums, occur, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
+                                                scales=dense_scales, se=dense_se, return_sums=True)
+            is_prob = dense_tta is not None or dense_scales is not None
+        elif crop_sizes:
+            sums, occur = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, return_sums=True)
+            is_prob = True
+        else:
+            sums, occur, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, return_sums=True, flavour=flavour)
+            is_prob = False
+        n = pool.h[k] * pool.w[k]
+        off = int(pool.lab_off[k].item())
+        kept.append((sums, occur, pool.labels[off:off + n], n, 1 if is_prob else 0))
+    st = net._stream()
+    scratch = torch.zeros(max([1] + [_lib.query("drs_temperature_scratch_doubles", q[3]) for q in kept]), dtype=torch.float64, device=net.dev)
+
+    def stats_fn(beta):
+        out = torch.zeros(5, dtype=torch.float64, device=net.dev)
+        for sums, occur, lab, n, is_prob in kept:
+            _lib.call("drs_temperature_stats", sums.data_ptr(), occur.data_ptr(), lab.data_ptr(), n, K, is_prob, ignore_label,
+                      float(beta), scratch.data_ptr(), out.data_ptr(), st)
+        return out.cpu().tolist()
+    fit = MT.fit_temperature(stats_fn, lo=lo, hi=hi, max_iter=max_iter)
+    fit["beta"] = P.check_temperature_beta(fit["beta"])
+    fit["temperature"] = 1.0 / fit["beta"]
+    comm.agree([int(np.float32(fit["beta"]).view(np.uint32))], "the fitted inverse temperature")
+    return fit
+
+
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None):
+                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -922,12 +1014,17 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     maps, one line `---- Iter N -- Test Map M: Calibration ECE= ... MCE= ... Mean Confidence= ... Accuracy= ...` follows the
     reference-format line, which stays as it is; the pixels are those the confusion matrix counts.  Returns (all-maps confusion
     matrix, label maps, extra) with extra = {"scores": [per map {kind: uint8 numpy [h, w]}], "reliability": the all-maps table
-    [256][2] (drs_reliability_histogram), "calibration": metrics.calibration of it, plus "per_map": [the same per map]}."""
+    [256][2] (drs_reliability_histogram), "calibration": metrics.calibration of it, plus "per_map": [the same per map]}.
+    temperature_beta (opt-in; with score_maps only; an inverse temperature, e.g. fit_temperature's): the score maps, and so the
+    calibration report, are of the calibrated probabilities; every Calibration line then ends in ` Temperature= T`
+    (T = 1 / beta) and extra carries "temperature_beta".  Labels and reference-format lines do not change."""
     from . import _lib
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
     _check_dense_se(dense_tile, dense_se)
+    beta = _check_temperature(temperature_beta, score_maps)
+    cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
         kinds = P.check_score_kinds(score_maps)
@@ -946,13 +1043,15 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     for k in range(len(testing_data)):
         if dense_tile is not None:
             res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                     scales=dense_scales, se=dense_se, scores=kinds)
+                                     scales=dense_scales, se=dense_se, scores=kinds, temperature_beta=beta)
             (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
-            res = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, scores=kinds)
+            res = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, scores=kinds,
+                                          temperature_beta=beta)
             pred, smaps = (res, None) if kinds is None else res
         else:
-            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour, scores=kinds)
+            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour, scores=kinds,
+                                temperature_beta=beta)
             (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         h, w = pool.h[k], pool.w[k]
         conf = torch.zeros(K * K, dtype=torch.int32, device=net.dev)
@@ -985,7 +1084,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})
             cal_list.append(MT.calibration(hist))
             if comm.rank == 0:
-                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _calibration_str(cal_list[-1]))
+                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _calibration_str(cal_list[-1]) + cal_tail)
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -1002,14 +1101,17 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         cal = MT.calibration(all_hist)
         cal["per_map"] = cal_list
         if comm.rank == 0:
-            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _calibration_str(cal))
-        return all_cm, maps, {"scores": score_list, "reliability": all_hist, "calibration": cal}
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _calibration_str(cal) + cal_tail)
+        extra = {"scores": score_list, "reliability": all_hist, "calibration": cal}
+        if beta is not None:
+            extra["temperature_beta"] = beta
+        return all_cm, maps, extra
     return all_cm, maps
 
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None):
+                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
@@ -1018,11 +1120,13 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     dense_se ("global"; with dense_tile only, nets with squeeze-and-excitation blocks): its whole-image gates (predict_tile_dense's se).
     score_maps (opt-in; a tuple of kinds from patches.SCORE_KINDS; any inference path): per-pixel score maps written
     beside each label file as `<stem>_<kind>.npy` (uint8 [h, w]) and an 8-bit grey `<stem>_<kind>.tif`, by rank 0 as the labels are;
-    returns (label maps, [per map {kind: uint8 numpy [h, w]}])."""
+    returns (label maps, [per map {kind: uint8 numpy [h, w]}]).  temperature_beta (opt-in; with score_maps only; an inverse
+    temperature): the score files are of the calibrated probabilities; the label files do not change."""
     comm = comm or NoComm()
     _check_dense_tta(dense_tile, dense_tta)
     _check_dense_scales(dense_tile, dense_scales)
     _check_dense_se(dense_tile, dense_se)
+    beta = _check_temperature(temperature_beta, score_maps)
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
     score_list = []
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -1034,9 +1138,9 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     for k in range(len(testing_data)):
         if dense_tile is not None:
             res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                     scales=dense_scales, se=dense_se, scores=kinds)
+                                     scales=dense_scales, se=dense_se, scores=kinds, temperature_beta=beta)
         else:
-            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, scores=kinds)
+            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, scores=kinds, temperature_beta=beta)
         (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
         maps.append(pred.cpu().numpy())
         if kinds is not None:

@@ -78,3 +78,58 @@ def calibration(hist, bins=15):
         return {"ece": 0.0, "mce": 0.0, "mean_confidence": 0.0, "accuracy": 0.0, "count": 0, "bins": table}
     return {"ece": float((n_b / total * gap).sum()), "mce": float(gap[some].max()), "mean_confidence": float(c_b.sum() / total),
             "accuracy": float(r_b.sum() / total), "count": int(total), "bins": table}
+
+
+def fit_temperature(stats_fn, lo=1.0 / 64.0, hi=64.0, max_iter=60):
+    """Temperature scaling (Guo et al., On calibration of modern neural networks): the inverse temperature beta = 1 / T
+    in [lo, hi] that minimises the negative log-likelihood L(beta) of softmax(beta u) on labelled pixels.  stats_fn(beta) returns the
+    sufficient statistics (N, L, G, H, A) of include/drs.h's drs_temperature_stats: the count, L, dL/dbeta, d2L/dbeta2 >= 0 and
+    sum |mu - u_y|, the scale G is judged against.  L is convex in beta, so this is a safeguarded Newton iteration on G = 0:
+      - G(lo) >= 0 returns lo and G(hi) <= 0 returns hi, both with at_bound (perfectly separable data ends at hi);
+      - otherwise, from beta = 1: stop when |G| <= 1e-12 A; else shrink the bracket (hi = beta if G > 0, else lo = beta), propose
+        beta - G / H, take sqrt(lo hi) instead if H <= 0 or the proposal leaves the open bracket, and stop when the step is
+        <= 1e-14 beta.  The value returned is the last beta evaluated, so nll_after is its L / N.
+      - N = 0, or A = 0 and H = 0 at lo (one class, or every score vector constant: L does not depend on beta), returns beta = 1 with
+        degenerate.
+    At most 2 + max_iter evaluations.  Returns {"beta", "temperature", "nll_before" (L / N at beta = 1), "nll_after", "count",
+    "iterations" (evaluations made), "at_bound", "degenerate"}."""
+    lo, hi, max_iter = float(lo), float(hi), int(max_iter)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= 1.0 <= hi) or max_iter < 1:
+        raise ValueError("fit_temperature: expected finite 0 < lo <= 1 <= hi and max_iter >= 1, not lo=%r hi=%r max_iter=%r" % (lo, hi, max_iter))
+    evals = [0]
+
+    def stats(beta):
+        evals[0] += 1
+        N, L, G, H, A = (float(x) for x in stats_fn(beta))
+        return N, L, G, H, A
+
+    def result(beta, before, after, N, at_bound=False, degenerate=False):
+        return {"beta": beta, "temperature": 1.0 / beta, "nll_before": before, "nll_after": after, "count": int(N),
+                "iterations": evals[0], "at_bound": at_bound, "degenerate": degenerate}
+    N, L_lo, G_lo, H_lo, A_lo = stats(lo)
+    if N == 0:
+        return result(1.0, 0.0, 0.0, 0, degenerate=True)
+    if A_lo == 0.0 and H_lo == 0.0:
+        return result(1.0, L_lo / N, L_lo / N, N, degenerate=True)
+    _, L_hi, G_hi, _, _ = stats(hi)
+    if G_lo >= 0.0 or G_hi <= 0.0:
+        beta, L_b = (lo, L_lo) if G_lo >= 0.0 else (hi, L_hi)
+        before = L_b / N if beta == 1.0 else stats(1.0)[1] / N
+        return result(beta, before, L_b / N, N, at_bound=True)
+    new, before = 1.0, None
+    for _ in range(max_iter):
+        beta = new
+        _, L, G, H, A = stats(beta)
+        before = L / N if before is None else before
+        if abs(G) <= 1e-12 * A:
+            break
+        if G > 0.0:
+            hi = beta
+        else:
+            lo = beta
+        new = beta - G / H if H > 0.0 else lo
+        if not lo < new < hi:
+            new = float(np.sqrt(lo * hi))
+        if abs(new - beta) <= 1e-14 * beta:
+            break
+    return result(beta, before, L / N, N)

@@ -342,6 +342,41 @@ def parse_score_maps(text):
     return tuple(names)
 
 
+# ------------------------------------------------------------------- temperature scaling of the score maps
+BETA_MIN, BETA_MAX = 1.0 / 64.0, 64.0     # the inverse temperatures include/drs.h accepts
+
+
+def check_temperature_beta(beta):
+    """An inverse temperature beta = 1 / T as the float the kernels take (rounded to float32): a finite number in [1/64, 64].
+    Anything else raises ValueError."""
+    try:
+        ok = not isinstance(beta, (bool, str, bytes)) and math.isfinite(float(beta))
+    except (TypeError, ValueError):
+        ok = False
+    b = float(np.float32(beta)) if ok else 0.0
+    if not BETA_MIN <= b <= BETA_MAX:
+        raise ValueError("temperature beta %r: expected a finite inverse temperature in [1/64, 64]" % (beta,))
+    return b
+
+
+def parse_temperature(text):
+    """The value of the command line's --temperature option: "auto" (the fitted file of the step being evaluated), or a temperature
+    T > 0 whose inverse is an accepted beta, returned as beta = 1 / T (check_temperature_beta).  Anything else raises ValueError."""
+    if text == "auto":
+        return "auto"
+    try:
+        ok = isinstance(text, str) and text == text.strip() and text != ""
+        T = float(text) if ok else 0.0
+    except ValueError:
+        T = 0.0
+    if not (math.isfinite(T) and T > 0.0):
+        raise ValueError("temperature %r: expected auto or a temperature T > 0 with 1/64 <= 1/T <= 64" % (text,))
+    try:
+        return check_temperature_beta(1.0 / T)
+    except ValueError:
+        raise ValueError("temperature %r: expected auto or a temperature T > 0 with 1/64 <= 1/T <= 64" % (text,)) from None
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

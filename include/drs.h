@@ -260,6 +260,27 @@ int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_l
  * >= K counts as wrong (drs_confusion leaves such a pixel out; a finalised map holds none).  K <= 8, n < 2^40. */
 int drs_reliability_histogram(const unsigned char* truth, const unsigned char* pred, const unsigned char* confidence, size_t n, int K,
                               int ignore_label, unsigned long long* hist, void* stream);
+/* temperature scaling (opt-in; Guo et al., On calibration of modern neural networks): the sufficient statistics of
+ * the fit of ONE scalar, the inverse temperature beta = 1 / T, on labelled maps.  beta is finite and 1/64 <= beta <= 64; anything else
+ * is DRS_ERR_ARG.  Per pixel i: oc = occur[i] ? occur[i] : 1, s_k = sums[i][k] (the accumulators handed to drs_stitch_finalize*).
+ *   score vector u (fp64)   sums_are_prob == 0: u_k = (double)s_k / (double)oc
+ *                           sums_are_prob != 0: q_k = s_k / (float)oc in fp32 (as drs_stitch_finalize_scores forms it), then
+ *                                               u_k = log((double)max(q_k, FLT_MIN)): the log of the mean probability, which is the
+ *                                               usual extension of temperature scaling to an ensemble
+ *   calibrated p(beta)      softmax(beta u), max-subtracted
+ *   counted pixels          occur[i] > 0, truth[i] != ignore_label and truth[i] < K (those drs_confusion counts, less the uncovered)
+ * With mu = sum_k p_k u_k, y = truth[i], m = max_k beta u_k, summed over the counted pixels in fp64:
+ *   out[0] += N   the count (exact below 2^53)
+ *   out[1] += L = sum [ log sum_k exp(beta u_k - m) + m - beta u_y ]      the negative log-likelihood; convex in beta
+ *   out[2] += G = sum (mu - u_y)                                           dL/dbeta
+ *   out[3] += H = sum sum_k p_k (u_k - mu)^2                               d2L/dbeta2 >= 0
+ *   out[4] += A = sum |mu - u_y|                                           the scale G is judged against
+ * out = 5 doubles on the device, ADDED to in stream order, so the maps of a split accumulate over several calls.  No float atomics:
+ * per-workgroup rows of `scratch` (drs_temperature_scratch_doubles(n) doubles, device) are added in a fixed order by a second
+ * launch, and the grid depends on n alone, so two runs give the same bits.  K <= 8, n < 2^40; n == 0 does nothing. */
+size_t drs_temperature_scratch_doubles(size_t n);
+int drs_temperature_stats(const float* sums, const unsigned int* occur, const unsigned char* truth, size_t n, int K, int sums_are_prob,
+                          int ignore_label, double beta, double* scratch, double* out /* [5] = N, L, G, H, A: ADDED to */, void* stream);
 
 /* fixed-order column sums (scratch: drs_colsum_scratch_doubles(ncols) doubles) / scalar sums used on the slabs above */
 int drs_rows_reduce_f32(const float* in, int nrows, int ncols, float* out, double* scratch, void* stream);
@@ -371,6 +392,18 @@ int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs,
 int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob,
                                unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
                                void* stream);
+/* drs_stitch_finalize_scores at an inverse temperature beta (drs_temperature_stats above: finite, 1/64 <= beta <= 64, else
+ * DRS_ERR_ARG).  The labels are drs_stitch_finalize's for every beta: a temperature never moves an arg-max.
+ *   beta == 1.0f   runs drs_stitch_finalize_scores: every output is bit for bit that function's; with sums_are_prob that means p is
+ *                  NOT renormalised
+ *   otherwise      in fp32, with ocf = (float)oc: v_k = s_k / ocf (sums_are_prob == 0) or logf(fmaxf(s_k / ocf, FLT_MIN)) (!= 0);
+ *                  t_k = beta v_k, rounded to fp32 BEFORE the maximum is subtracted; p = the max-subtracted softmax of t, the classes
+ *                  summed in order, renormalised in BOTH modes; confidence and margin of p as above;
+ *                  entropy = (ln se - sum_k p_k (t_k - max t)) / ln K with se the sum of the exponentials, in both modes
+ * Uncovered pixels, NULL outputs, the clamp and the byte are drs_stitch_finalize_scores'. */
+int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta,
+                                 unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
+                                 void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);
