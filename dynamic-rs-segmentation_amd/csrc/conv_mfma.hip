@@ -17,7 +17,13 @@
 // accumulator VGPRs; A tile [BM][32] and B tile [32][BN] are staged through LDS (register prefetch of the next
 // K-step while the current one is multiplied).
 #include "drs_common.hpp"
+#include <algorithm>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <numeric>
+#include <tuple>
+#include <vector>
 
 namespace {
 
@@ -50,6 +56,10 @@ struct ConvArgs {
   // launch order "long tiles first" (plain launches with halo-tap skipping, whole patches per XCD chunk): lpt_T = M tiles per patch
   // (0 = natural order), tiles [lpt_ta, lpt_tb) of a patch multiply every tap row, the others skip some; lpt_P = patches per XCD chunk
   int lpt_T, lpt_ta, lpt_tb, lpt_P;
+  // image tiles (plain launches of conv_dma_kernel without statistics; live_taps_image_tile in drs_common.hpp): img_g = log2 of the images per M tile
+  // (0 = spatial tiles), img_order = device table [M tiles]: logical M-tile position (after the XCD remap) -> M tile
+  int img_g;
+  const int* img_order;
 #ifdef DRS_DEV
   unsigned long long* trace;      // development build: [workgroup][2] = (start, end) of the workgroup on the 100 MHz real-time clock, or null
 #endif
@@ -110,14 +120,22 @@ __host__ __device__ __forceinline__ int sk_owner(int x, int U, int W) { return (
 
 // Epilogue shared by the forward / input-gradient kernels: bias, optional accumulate, store, and the tile's batch-norm statistics.
 // C/D map of the 32x32 tile: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).  `scratch`: LDS no wave reads any more.
-template <int BM, int BN, int WM, int WN>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], float* scratch, int m0, int n0) {
+// MAP (the plain LDS-DMA launches): tile row r is output pixel pix0 + (r >> pcs) S^2 + (r & (2^pcs - 1)) -- an image tile (pcs = log2
+// of its columns Pc, always full; never together with a.stats: launch_conv_dma), or with pcs = 30 and pix0 = m0 the spatial tile.
+template <int BM, int BN, int WM, int WN, bool MAP = false>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[BM / WM / 32][BN / WN / 32], float* scratch, int m0, int n0,
+                                              int pix0 = 0, int pcs = 30) {
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 32, TN = WTN / 32;
   const int t = threadIdx.x;
   const int lane = t & 63, wave = t >> 6;
   const int li = lane & 31, h = lane >> 5;
   const int wm = wave / WN, wn = wave % WN;
+  // (image tiles: r / Pc and r % Pc act on disjoint bits of r = [wave row + 4 h] + [32 mi + (reg&3) + 8 (reg>>2)], so the pixel is a
+  //  per-lane part worked out once + a scalar part per register: the same address form as the spatial tile's)
+  const int pcm = (1 << pcs) - 1, S2 = a.S * a.S;
+  const int lane_rl = wm * WTM + 4 * h;
+  const int lane_pix = MAP ? pix0 + (lane_rl >> pcs) * S2 + (lane_rl & pcm) : 0;
   float bv[TN];
 #pragma unroll
   for (int ni = 0; ni < TN; ++ni) {
@@ -127,7 +145,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
     for (int mi = 0; mi < TM; ++mi) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * WTM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int crl = mi * 32 + (r & 3) + 8 * (r >> 2);
+        const int row = MAP ? lane_pix + __builtin_amdgcn_readfirstlane((crl >> pcs) * S2 + (crl & pcm)) : m0 + lane_rl + crl;
         if (row < a.M) {
           float v = acc[mi][ni][r] + bv[ni];
           float* dst = a.out + (size_t)row * a.ld_out + a.coff_out + col;
@@ -360,7 +379,16 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvArgs a) {
   // the workgroups of a launch start in index order and the launch ends with its last round draining: let that round be the SHORT
   // tiles (r04, tools/conv_tail.py: the drain of conv8's forward launch 419 -> 216 us, idle workgroup slots 6.4 -> 3.5 % of the launch;
   // in-process A/B over the 14 forward / input-gradient launches at B = 128: -1.2 .. -5.5 % each, 29.7 -> 28.8 ms)
-  const int tile0 = (!SK && a.lpt_T) ? __builtin_amdgcn_readfirstlane(lpt_tile(wg, a.lpt_T, a.lpt_ta, a.lpt_tb, a.lpt_P, ntn)) : wg;
+  // image tiles: the M tile of this workgroup's position comes from the launch-order table (conv_image_order: every XCD chunk the
+  // same K-step total, long tiles first); its ntn column tiles stay adjacent
+  const int img_g = SK ? 0 : a.img_g;
+  int tile0 = wg;
+  if (!SK && img_g) {
+    const int mpos = wg / ntn;
+    tile0 = __builtin_amdgcn_readfirstlane(a.img_order[mpos] * ntn + (wg - mpos * ntn));
+  } else if (!SK && a.lpt_T) {
+    tile0 = __builtin_amdgcn_readfirstlane(lpt_tile(wg, a.lpt_T, a.lpt_ta, a.lpt_tb, a.lpt_P, ntn));
+  }
   bool first_seg = true;
   int quart = -1, done = 0, total = 1;
   if (a.prio == 3) __builtin_amdgcn_s_setprio(3);      // the whole launch above a filter gradient that shares the chip (drs_tl_chain)
@@ -384,16 +412,31 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvArgs a) {
     }
     const int m0 = (tile / ntn) * BM;
     const int n0 = (tile % ntn) * BN;
+    // image tile: (image group, row y, first column x0) of M tile m0 / BM, all wave-uniform
+    int ty = 0, tx0 = 0, timg0 = 0;
+    if (!SK && img_g) {
+      const int grp = image_tile_pos(tile / ntn, a.S, img_g, ty, tx0);
+      ty = __builtin_amdgcn_readfirstlane(ty);
+      tx0 = __builtin_amdgcn_readfirstlane(tx0);
+      timg0 = __builtin_amdgcn_readfirstlane(grp << img_g);
+    }
 
     // DMA lane roles.  A: instruction j covers pixel rows 16 j + (lane >> 2); this lane fills slot (lane & 3) of its row with
     // the source piece (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ ((lane >> 4) & 3)
     uint32_t offA[IA], offB[IB];
 #pragma unroll
     for (int i = 0; i < IA; ++i) {
-      int p = m0 + (wave + 4 * i) * 16 + (lane >> 2);
-      p = p < a.M ? p : a.M - 1;
-      offA[i] = (padded_pixel_off(p, a.S, a.P, a.ld_in, a.rcpS, a.rcpSS, -a.pad, -a.pad) + (uint32_t)a.coff_in) * 4u +
-                (uint32_t)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
+      const int r = (wave + 4 * i) * 16 + (lane >> 2);
+      uint32_t pix;
+      if (!SK && img_g) {     // tile row r = column x0 + r % Pc of image timg0 + r / Pc, row ty
+        const int pcs = 7 - img_g;
+        pix = (uint32_t)(((timg0 + (r >> pcs)) * Sp + ty + a.P - a.pad) * Sp + (tx0 + (r & ((1 << pcs) - 1)) + a.P - a.pad)) * (uint32_t)a.ld_in;
+      } else {
+        int p = m0 + r;
+        p = p < a.M ? p : a.M - 1;
+        pix = padded_pixel_off(p, a.S, a.P, a.ld_in, a.rcpS, a.rcpSS, -a.pad, -a.pad);
+      }
+      offA[i] = (pix + (uint32_t)a.coff_in) * 4u + (uint32_t)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
     }
     // B: instruction j moves pieces 64 j + lane of the linear half image: piece f is the 16-byte column f % BQ of k-row f / BQ
     // (BN = 192: a k-row is 768 B, so an instruction spans rows; every lane has its own (row, column) per instruction)
@@ -411,16 +454,19 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
 
-    int u_lo, u_hi;
-    live_tap_rows(m0, BM, a.M, a.S, a.k, a.rate, a.pad, a.rcpS, a.rcpSS, u_lo, u_hi);
-    if (!a.skip_halo || SK) { u_lo = 0; u_hi = a.k; }          // (stream-K: every tile has the same number of K-steps)
+    int u_lo, u_hi, v_lo = 0, v_hi = a.k;                      // live tap rows and -- image tiles only -- live tap columns
+    if (!SK && img_g) live_taps_image_tile(ty, tx0, 128 >> img_g, a.S, a.k, a.rate, a.pad, u_lo, u_hi, v_lo, v_hi);
+    else live_tap_rows(m0, BM, a.M, a.S, a.k, a.rate, a.pad, a.rcpS, a.rcpSS, u_lo, u_hi);
+    if (!a.skip_halo || SK) { u_lo = 0; u_hi = a.k; v_lo = 0; v_hi = a.k; }          // (stream-K: every tile has the same number of K-steps)
     u_lo = __builtin_amdgcn_readfirstlane(u_lo);
     u_hi = __builtin_amdgcn_readfirstlane(u_hi);
-    const int nks = (u_hi - u_lo) * a.k * cpt;
+    v_lo = __builtin_amdgcn_readfirstlane(v_lo);
+    v_hi = __builtin_amdgcn_readfirstlane(v_hi);
+    const int nks = (u_hi - u_lo) * (v_hi - v_lo) * cpt;
     if (!SK) ke = nks;
     const uint32_t wlive_off = (uint32_t)(u_lo * a.k * a.Cin * a.Cout) * 4u;      // byte offset of the first live tap row's filter rows
     // (tap row, tap col, channel chunk) of the K-step being fetched; K-step j of a tile is (chunk, tap row, tap col) = (j / (rows k), ...)
-    int lu = u_lo, lv = 0, lc = 0;
+    int lu = u_lo, lv = v_lo, lc = 0;
     if (SK && kb) {
       const int per_chunk = (u_hi - u_lo) * a.k;
       lc = kb / per_chunk;
@@ -450,7 +496,7 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvArgs a) {
     // when they are read again.  Against (tap row, tap column, chunk), in-process A/B with a run-time switch (profiles/r02/
     // conv_korder_ab.txt): fabric-side fetch per launch 6.1 -> 0.9 GB (conv6), 7.8 -> 2.2 GB (conv8); forward -1 %, dgrad -2.4 %.
     // (The switch itself is gone: it sent the loop counters to scratch memory and their arithmetic to the vector ALU, -7 %.)
-    auto next_kstep = [&]() { if (++lv == a.k) { lv = 0; if (++lu == u_hi) { lu = u_lo; ++lc; } } };
+    auto next_kstep = [&]() { if (++lv == v_hi) { lv = v_lo; if (++lu == u_hi) { lu = u_lo; ++lc; } } };
 
     auto compute = [&](int stage) {
       const float* As = lds + stage * STAGE;
@@ -503,7 +549,9 @@ __global__ __launch_bounds__(256, 3) void conv_dma_kernel(const ConvArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
     }
-    if (!SK || (kb == 0 && ke == nks)) {
+    if (!SK) {
+      conv_epilogue<BM, BN, WM, WN, true>(a, acc, lds, m0, n0, img_g ? (timg0 * a.S + ty) * a.S + tx0 : m0, img_g ? 7 - img_g : 30);
+    } else if (kb == 0 && ke == nks) {
       conv_epilogue<BM, BN, WM, WN>(a, acc, lds, m0, n0);
     } else {
       // partial sums of a tile this workgroup shares with others: a piece of the slab in accumulator order, four registers per
@@ -1470,6 +1518,85 @@ void conv_lpt_setup(ConvArgs& a, int BM, int mt, int nt, int W) {
   if (ok && (ta > 0 || tb < T)) { a.lpt_T = T; a.lpt_ta = ta; a.lpt_tb = tb; a.lpt_P = nblk / 8 / (T * nt); a.skip_halo = 1; }
 }
 
+// ---- image tiles (live_taps_image_tile in drs_common.hpp)
+int g_conv_image_tiles = -1; // development switch (drs_debug_conv_image_tiles): -1 = by conv_image_tiles_rule, 0 = never, 4..7 = 2^g images per tile where the shape allows it
+
+// The rule: log2 of the images per tile a plain launch of this layer takes, 0 = spatial tiles.  One place, keyed on what the kernel
+// sees.  A layer is listed only where the in-process A/B (tools/ab_image_tiles.py, profiles/image_tiles/ab_image_tiles.txt: off and
+// g = 4..7 alternating, 7 repeats) showed a gain larger than the spread between repeats: the slowest repeat of the arm below the
+// fastest repeat of spatial tiles.  (The launch itself adds: no tile statistics -- launch_conv_dma.)  Measured at 128 x 64 x 64 only, so the rule holds there only.  g = 7 (one pixel position of 128
+// images) won or tied everywhere it gained: -1.4 % (conv5 dgrad) .. -8 % (conv8).  NOT listed: conv2 (5x5, rate 2: 3.7 % of the
+// K-steps to gain, medians -3 % but the arms' ranges overlap) and conv3's input gradient (128 -> 64 channels: g = 5 -4.8 % in the
+// median, its slowest repeat 2 us above the fastest of spatial tiles).
+int conv_image_tiles_rule(int k, int rate, int cin, int cout, int B, int S) {
+  if (B != 128 || S != 64) return 0;
+  struct Row { int k, rate, cin, cout; };
+  static const Row gains[] = {{4, 3, 64, 128},                        // conv3 forward (without statistics: inference)
+                              {4, 4, 128, 128},                       // conv4 forward, input gradient
+                              {3, 5, 128, 192}, {3, 5, 192, 128},     // conv5
+                              {3, 6, 192, 192},                       // conv6
+                              {3, 7, 192, 256}, {3, 7, 256, 192},     // conv7
+                              {3, 8, 256, 256}};                      // conv8
+  for (const Row& r : gains)
+    if (r.k == k && r.rate == rate && r.cin == cin && r.cout == cout) return 7;
+  return 0;
+}
+
+// log2 of the images per tile of the PLAIN launch of this shape that writes no tile statistics, 0 = spatial tiles: the rule or the
+// switch, and the shape must allow it (whole image groups, whole column groups, a filter with more than one tap, the LDS-DMA path).
+// Depends on nothing else -- not on the skip / launch-order switches.
+int conv_image_tiles_g(int B, int S, int k, int rate, int cin, int cout) {
+  const int g = g_conv_image_tiles < 0 ? conv_image_tiles_rule(k, rate, cin, cout, B, S) : g_conv_image_tiles;
+  if (g < 4 || g > 7 || k < 2 || cin < BK || cin % BK || g_conv_variant == 0) return 0;
+  if (B % (1 << g) || S % (128 >> g)) return 0;
+  return g;
+}
+
+// K-steps per channel chunk of M tile mt under the image-tile map, with the all-halo taps left out
+inline int image_tile_taps(int mt, int S, int k, int rate, int pad, int g) {
+  int y, x0, ul, uh, vl, vh;
+  image_tile_pos(mt, S, g, y, x0);
+  live_taps_image_tile(y, x0, 128 >> g, S, k, rate, pad, ul, uh, vl, vh);
+  return (uh - ul) * (vh - vl);
+}
+
+// Launch order of an image-tile launch: order[position] = M tile, position = logical workgroup index / ntn (after the XCD remap
+// every XCD owns one contiguous eighth of the positions).  The M tiles are sorted by their K-steps, longest first (ties in tile
+// order), and dealt out to the eight chunks in turn: chunk c takes sorted[c], sorted[8 + c], ...  Every chunk then runs its tiles
+// in non-increasing order (the draining round of the launch is the short tiles: the principle of lpt_tile) and the chunk totals
+// differ by less than one tile (the differences telescope).  A tile count that is no multiple of 8 keeps the sorted order.
+std::vector<int> conv_image_order(int B, int S, int k, int rate, int pad, int g) {
+  const int mt = B * S * S / 128;
+  std::vector<int> taps(mt), sorted(mt), order(mt);
+  for (int i = 0; i < mt; ++i) taps[i] = image_tile_taps(i, S, k, rate, pad, g);
+  std::iota(sorted.begin(), sorted.end(), 0);
+  std::stable_sort(sorted.begin(), sorted.end(), [&](int x, int y) { return taps[x] > taps[y]; });
+  if (mt % 8) return sorted;
+  const int per = mt / 8;
+  for (int c = 0; c < 8; ++c)
+    for (int j = 0; j < per; ++j) order[c * per + j] = sorted[j * 8 + c];
+  return order;
+}
+
+// the table on the current device: built at the first launch of a shape and kept for the life of the process (a few KiB per layer:
+// 16 KiB at 128 x 64 x 64), so the launches of a training step neither allocate nor copy
+const int* conv_image_order_device(int B, int S, int k, int rate, int pad, int g) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, int, int, int, int, int, int>, const int*> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_tuple(dev, B, S, k, rate, pad, g);
+  const auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  const std::vector<int> order = conv_image_order(B, S, k, rate, pad, g);
+  int* d = nullptr;
+  if (hipMalloc((void**)&d, order.size() * sizeof(int)) != hipSuccess) return nullptr;
+  if (hipMemcpy(d, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
+  cache[key] = d;
+  return d;
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_conv_dma(ConvArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
   const int mt = (a.M + BM - 1) / BM, nt = a.Cout / BN;
@@ -1488,6 +1615,19 @@ int launch_conv_dma(ConvArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
   // two-stream backward pass): the whole launch at the top priority, no lowering by progress
   if (g_conv_prio < 0 && drs_chain_level(drs_tl_chain, drs_g_chain_mode) >= 1) a.prio = 3;
   conv_lpt_setup(a, BM, mt, nt, g.G);
+  // Image tiles only where the launch writes no tile statistics (input gradient, inference forward): the statistics are per-tile
+  // two-pass partials, and a tile of other pixels would group them differently -- the moments would move at fp32 rounding level, and
+  // with them near-tie activation signs / pool winners and, from there, a training run.  Without statistics the map changes no bit.
+  if (!g.G && !a.stats) {
+    const int B = a.M / (a.S * a.S);
+    a.img_g = conv_image_tiles_g(B, a.S, a.k, a.rate, a.Cin, a.Cout);
+    if (a.img_g) {
+      a.img_order = conv_image_order_device(B, a.S, a.k, a.rate, a.pad, a.img_g);
+      if (!a.img_order) return DRS_ERR_HIP;
+      a.lpt_T = 0;                                         // the table is the launch order
+      a.skip_halo = drs_g_skip_halo_taps != 0;             // long tiles first at any tile count, so skipping pays wherever the map is taken
+    }
+  }
   if (g.G) DRS_LAUNCH((conv_dma_kernel<BM, BN, WM, WN, true>), dim3(g.G), dim3(256), 0, st, a);
   else DRS_LAUNCH((conv_dma_kernel<BM, BN, WM, WN, false>), dim3(mt * nt), dim3(256), 0, st, a);
   int rc = DRS_LAUNCH_CHECK();
@@ -1776,6 +1916,17 @@ int wgrad_setup(int B, int S, int k, int rate, int pad_before, int cin, int cout
   return DRS_OK;
 }
 
+// log2 of the images per tile of drs_conv_forward_ws's launch of this shape (a caller with the full workspace, no statistics slab), 0 = spatial tiles:
+// conv_image_tiles_g on the LDS-DMA path's plain launches
+int conv_plain_image_g(int B, int S, int k, int rate, int cin, int cout) {
+  if (cin < 32 || cin % 32) return 0;
+  const int bn = pick_conv_tile(cout, cin);
+  if (bn < 64) return 0;
+  const int mt = (int)(((long long)B * S * S + 127) / 128), nt = cout / bn;
+  if (sk_geometry(mt * nt, k * k * (cin / 32), bn, 2ull * (size_t)sk_max_w() * 128 * (size_t)bn).G) return 0;      // (the full workspace)
+  return conv_image_tiles_g(B, S, k, rate, cin, cout);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1823,6 +1974,19 @@ int drs_debug_conv_order(int B, int S, int k, int rate, int pad_before, int cin,
   for (int w = 0; w < mt * nt && w < cap; ++w) out[w] = lpt_tile(w, a.lpt_T, a.lpt_ta, a.lpt_tb, a.lpt_P, nt);
   return mt * nt;
 }
+int drs_debug_conv_image_tiles(int g) { const int old = g_conv_image_tiles; if (g >= -1) g_conv_image_tiles = g; return old; }
+/* the same report for the image-tile launch of the shape (rule or switch): out[w] = tile (M tile * column tiles + column tile) of
+   logical workgroup w; returns the workgroup count, 0 when the launch keeps spatial tiles, negative on a rejected shape */
+int drs_debug_conv_order_image(int B, int S, int k, int rate, int pad_before, int cin, int cout, int* out, int cap) {
+  const long long M = (long long)B * S * S;
+  if (M <= 0 || M >= (1 << 24) || cout % 32 || k < 1 || rate < 1) return -1;
+  const int g = conv_plain_image_g(B, S, k, rate, cin, cout);
+  if (!g) return 0;
+  const int mt = (int)(M / 128), nt = cout / pick_conv_tile(cout, cin);
+  const std::vector<int> order = conv_image_order(B, S, k, rate, pad_before, g);
+  for (int w = 0; w < mt * nt && w < cap; ++w) out[w] = order[w / nt] * nt + w % nt;
+  return mt * nt;
+}
 int drs_debug_conv_trace(void* dev_buffer) { g_conv_trace = (unsigned long long*)dev_buffer; return 0; }
 
 int drs_debug_conv_splitk(int v) { const int old = g_conv_splitk; if (v >= -1) g_conv_splitk = v; return old; }
@@ -1868,6 +2032,37 @@ int drs_conv_halo_skip(int B, int S, int k, int rate, int pad_before, int cin, i
   return a.skip_halo;
 }
 
+// K-steps (32 channels of one filter tap for one tile) the launch of this shape (a caller with the full workspace and no statistics
+// slab: an input gradient, an inference forward) executes, and the K-steps of the algorithm (every tap for every tile): equal unless all-halo taps are left out -- tap rows of spatial tiles
+// (drs_conv_halo_skip), tap rows and columns of image tiles.  Follows the library's own rules; 0 on success.
+int drs_conv_executed_ksteps(int B, int S, int k, int rate, int pad_before, int cin, int cout, long long* executed, long long* total) {
+  const long long M = (long long)B * S * S;
+  if (M <= 0 || M >= (1 << 24) || cout % 32 || cin < 1 || k < 1 || rate < 1 || !executed || !total) return DRS_ERR_ARG;
+  const int bn = pick_conv_tile(cout, cin), bm = bn >= 64 ? 128 : 256;
+  const int mt = (int)((M + bm - 1) / bm), nt = cout / bn;
+  const long long cpt = cin < 32 ? 1 : cin / 32;
+  *total = *executed = cin < 32 ? (long long)mt * nt * ((k * k * cin + 31) / 32) : (long long)mt * nt * k * k * cpt;
+  if (cin < 32 || cin % 32) return DRS_OK;
+  const int g = conv_plain_image_g(B, S, k, rate, cin, cout);
+  long long taps = 0;
+  if (g) {
+    if (drs_g_skip_halo_taps == 0) return DRS_OK;
+    for (int i = 0; i < mt; ++i) taps += image_tile_taps(i, S, k, rate, pad_before, g);
+  } else {
+    if (!drs_conv_halo_skip(B, S, k, rate, pad_before, cin, cout)) return DRS_OK;
+    for (int i = 0; i < mt; ++i) {       // live_tap_rows' rule, in integers
+      const int p0 = i * bm, p1 = (int)(p0 + bm < M ? p0 + bm : M) - 1;
+      int y0 = (p0 % (S * S)) / S, y1 = (p1 % (S * S)) / S;
+      if (p0 / (S * S) != p1 / (S * S)) { y0 = 0; y1 = S - 1; }
+      int lo = pad_before - y1 > 0 ? (pad_before - y1 + rate - 1) / rate : 0, hi = (S - 1 - y0 + pad_before) / rate + 1;
+      hi = hi < k ? hi : k;
+      if (lo >= hi) { lo = 0; hi = k; }
+      taps += (hi - lo) * k;
+    }
+  }
+  *executed = taps * nt * cpt;
+  return DRS_OK;
+}
 
 int drs_conv_forward_ws(const float* in, int B, int S, int P, int ld_in, int coff_in, const float* w, const float* bias,
                         int k, int rate, int pad_before, int cin, int cout, float* out, int ld_out, int coff_out,
@@ -1888,6 +2083,7 @@ int drs_conv_forward_ws(const float* in, int B, int S, int P, int ld_in, int cof
   a.skip_halo = drs_skip_halo_taps_fwd(M, cout);
   a.sk_slab = nullptr; a.sk_W = 0; a.sk_nks = 0; a.sk_U = 0; a.sk_T = a.sk_tiles = a.sk_G = a.sk_order = 0; a.prio = 0;
   a.lpt_T = a.lpt_ta = a.lpt_tb = a.lpt_P = 0;
+  a.img_g = 0; a.img_order = nullptr;
 #ifdef DRS_DEV
   a.trace = g_conv_trace;
 #endif

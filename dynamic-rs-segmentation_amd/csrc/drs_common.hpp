@@ -92,6 +92,35 @@ __device__ __forceinline__ void live_tap_rows(int m0, int BM, int M, int S, int 
   if (lo >= hi) { lo = 0; hi = k; }        // cannot happen for SAME padding (the centre taps always land inside); stay safe
 }
 
+// Image tiles (forward / input gradient, plain launches): an M tile of 128 rows holds the SAME Pc = 128 >> g consecutive columns of
+// one image row y of 2^g consecutive images, instead of 128 consecutive pixels of one image.  A tap (u, v) then meets only halo
+// zeros for the WHOLE tile exactly when the shifted position leaves the image, in either axis, so tap columns can be left out as
+// well as tap rows -- and the lane's source offset stays loop-invariant and the tap shift wave-uniform, as with spatial tiles.
+//   M tile index  mt = (group * S + y) * (S / Pc) + xg          tile row r -> image group * 2^g + r / Pc, column xg * Pc + r % Pc
+// [u_lo, u_hi) x [v_lo, v_hi) = the taps with 0 <= y + u rate - pad < S and some column x of [x0, x0 + Pc) with
+// 0 <= x + v rate - pad < S.  An empty range in either axis (every product of the tile is then a zero) keeps all taps.
+// Host and device share this one statement of the rule (the launch-order table and drs_conv_executed_ksteps count with it).
+__host__ __device__ __forceinline__ void live_taps_image_tile(int y, int x0, int Pc, int S, int k, int rate, int pad,
+                                                              int& u_lo, int& u_hi, int& v_lo, int& v_hi) {
+  const int au = pad - y, av = pad - (x0 + Pc - 1);
+  u_lo = au > 0 ? (au + rate - 1) / rate : 0;
+  v_lo = av > 0 ? (av + rate - 1) / rate : 0;
+  u_hi = (S - 1 - y + pad) / rate + 1;
+  v_hi = (S - 1 - x0 + pad) / rate + 1;
+  u_hi = u_hi < k ? u_hi : k;
+  v_hi = v_hi < k ? v_hi : k;
+  if (u_lo >= u_hi || v_lo >= v_hi) { u_lo = v_lo = 0; u_hi = v_hi = k; }
+}
+// (y, first column) of M tile mt under the image-tile map; returns the image group
+__host__ __device__ __forceinline__ int image_tile_pos(int mt, int S, int g, int& y, int& x0) {
+  const int Pc = 128 >> g, npc = S / Pc;
+  const int t2 = mt / npc;
+  x0 = (mt - t2 * npc) * Pc;
+  const int grp = t2 / S;
+  y = t2 - grp * S;
+  return grp;
+}
+
 // Filter gradient: a tile of filter rows belongs to tap rows u_first .. u_last; pixel rows y whose shifted rows y + u*rate - pad
 // all fall outside the image meet only halo zeros in X.  [lo, hi) = the pixel range (inside one image of S*S pixels) of the rows
 // that do meet image data; everything outside contributes exact zeros and is never fetched.

@@ -57,6 +57,12 @@ size_t drs_conv_workspace_floats(int cout);
  * tile of 128 pixels (exact zeros: results do not change): plain launches of >= 4096 tiles, and any plain launch whose tiles are whole
  * image rows of whole patches (S = 32, 64, 128: those start their full tiles first, the skipping ones last); never a stream-K launch */
 int drs_conv_halo_skip(int B, int S, int k, int rate, int pad_before, int cin, int cout);
+/* K-steps (32 input channels of one filter tap, for one output tile) that drs_conv_forward_ws (full workspace, stats_partial NULL:
+ * an input gradient or an inference forward; a launch that writes tile statistics keeps the tiles of 128 consecutive pixels) executes for this
+ * shape, and the K-steps of the algorithm (every tap for every tile).  executed < total where taps that meet only the zero halo for a
+ * whole tile are left out: tap rows of the tiles of 128 consecutive pixels (drs_conv_halo_skip), tap rows and columns where the
+ * library groups the same pixel position of many images into a tile.  Returns DRS_OK or DRS_ERR_ARG. */
+int drs_conv_executed_ksteps(int B, int S, int k, int rate, int pad_before, int cin, int cout, long long* executed, long long* total);
 int drs_conv_forward_ws(const float* in, int B, int S, int P, int ld_in, int coff_in, const float* w, const float* bias,
                         int k, int rate, int pad_before, int cin, int cout, float* out, int ld_out, int coff_out,
                         int accumulate, float* stats_partial, float* workspace, size_t workspace_floats, void* stream);

@@ -18,6 +18,8 @@ int drs_debug_conv_variant(int v);       /* forward / input gradient: 0 register
 int drs_debug_conv_wide192(int v);       /* Cout = 192 as one 128 x 192 tile (1, default) or three 128 x 64 tiles (0) */
 int drs_debug_conv_lpt(int v);           /* plain forward / input-gradient launches: 1 start the full tiles first and the halo-skipping ones last (default), 0 natural order */
 int drs_debug_conv_order(int B, int S, int k, int rate, int pad_before, int cin, int cout, int* out, int cap);   /* out[w] = tile of logical workgroup w of that plain launch; returns the workgroup count, 0 = natural order */
+int drs_debug_conv_image_tiles(int g);   /* plain forward / input-gradient launches, M tiles of 2^g images x 128 >> g columns of one image row (tap rows AND columns that meet only the halo are left out; never a launch that writes tile statistics -- its partials keep their pixels): -1 by the library's rule (default), 0 never, 4..7 that g where the shape allows it (B % 2^g == 0, S % (128 >> g) == 0, k > 1, cin % 32 == 0, no stream-K) */
+int drs_debug_conv_order_image(int B, int S, int k, int rate, int pad_before, int cin, int cout, int* out, int cap);   /* as drs_debug_conv_order, for the image-tile launch of the shape: out[w] = tile (M tile * column tiles + column tile; M tile = (image group * S + y) * (S / Pc) + column group); 0 = the launch keeps spatial tiles */
 int drs_debug_conv_trace(void* dev_buffer); /* forward / input gradient (LDS-DMA form): device buffer [workgroups][2] of u64 that receives every workgroup's (start, end) on the 100 MHz real-time clock; NULL = off */
 int drs_debug_conv_splitk(int v);        /* split-K of the forward / input-gradient pass: -1 by the cost model (default), 0 never, n >= 1 that many ranges */
 int drs_debug_conv_hybrid(int v);        /* stream-K launches of more tiles than workgroups: 1 whole tiles for the full rounds, only the remainder cut (default), 0 every tile cut (r03) */
