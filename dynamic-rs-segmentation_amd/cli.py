@@ -51,6 +51,39 @@ ISPRS_PARAMS = ["input_path", "output_path(for model, images, etc)", "currentMod
                 "process [training|validate_test|generate_final_maps]"]
 
 
+def _take_flag(argv, flag, parse_value, bare=None):
+    """The optional `flag=value` -- or the bare `flag`, where `bare` (its value) says that form exists -- anywhere in argv.  Returns
+    (argv without the flag, parse_value(the argument as given, the text after `=`)), or (argv unchanged, as a new list, None) without the
+    flag.  The flag given twice raises ValueError; a bare flag that has no bare form reaches parse_value with an empty text, to be
+    refused in the flag's own words."""
+    rest, found, value = [], False, None
+    for a in argv:
+        if a != flag and not a.startswith(flag + "="):
+            rest.append(a)
+            continue
+        if found:
+            raise ValueError(flag + " given more than once")
+        found = True
+        value = bare if a == flag and bare is not None else parse_value(a, a[len(flag) + 1:])
+    return (rest if found else list(argv)), value
+
+
+def _or_expected(parse, a, v, expected):
+    """parse(v), its ValueError reworded as `<argument>: expected <form>`"""
+    try:
+        return parse(v)
+    except ValueError:
+        raise ValueError("%s: expected %s" % (a, expected)) from None
+
+
+def _one_of(choices, flag):
+    def parse(v):
+        if v not in choices:
+            raise ValueError(v)
+        return v
+    return lambda a, v: _or_expected(parse, a, v, "%s=%s" % (flag, "|".join(choices)))
+
+
 DENSE_TILE_FLAG = "--dense-tile"
 
 
@@ -58,21 +91,11 @@ def parse_dense_tile(argv):
     """isprs flavour: the optional `--dense-tile[=T]` (anywhere in argv) that switches validate_test / generate_final_maps to
     overlap-tile inference (loops.predict_tile_dense).  Returns (argv without the flag, T) -- T = 0 for the bare flag (the default
     side), None without it, in which case argv comes back unchanged.  A malformed value, or the flag given twice, raises ValueError."""
-    rest, tile = [], None
-    for a in argv:
-        if a != DENSE_TILE_FLAG and not a.startswith(DENSE_TILE_FLAG + "="):
-            rest.append(a)
-            continue
-        if tile is not None:
-            raise ValueError(DENSE_TILE_FLAG + " given more than once")
-        if a == DENSE_TILE_FLAG:
-            tile = 0
-            continue
-        v = a[len(DENSE_TILE_FLAG) + 1:]
+    def side(a, v):
         if not (v.isascii() and v.isdigit()) or int(v) < 1:
             raise ValueError("%s=%s: the tile side must be a positive integer" % (DENSE_TILE_FLAG, v))
-        tile = int(v)
-    return (list(argv) if tile is None else rest), tile
+        return int(v)
+    return _take_flag(argv, DENSE_TILE_FLAG, side, bare=0)
 
 
 DENSE_TTA_FLAG = "--dense-tta"
@@ -82,18 +105,7 @@ def parse_dense_tta(argv):
     """isprs flavour: the optional `--dense-tta=flip|d4` (anywhere in argv; with --dense-tile only, which main checks).  Returns (argv
     without the flag, "flip" / "d4"), or (argv unchanged, None) without it.  Any other value, a bare flag, or the flag given twice,
     raises ValueError."""
-    rest, tta = [], None
-    for a in argv:
-        if a != DENSE_TTA_FLAG and not a.startswith(DENSE_TTA_FLAG + "="):
-            rest.append(a)
-            continue
-        if tta is not None:
-            raise ValueError(DENSE_TTA_FLAG + " given more than once")
-        v = a[len(DENSE_TTA_FLAG) + 1:]
-        if v not in P.TTA_GROUPS:
-            raise ValueError("%s: expected %s=%s" % (a, DENSE_TTA_FLAG, "|".join(P.TTA_GROUPS)))
-        tta = v
-    return (list(argv) if tta is None else rest), tta
+    return _take_flag(argv, DENSE_TTA_FLAG, _one_of(P.TTA_GROUPS, DENSE_TTA_FLAG))
 
 
 DENSE_SCALES_FLAG = "--dense-scales"
@@ -103,22 +115,12 @@ def parse_dense_scales(argv):
     """isprs flavour: the optional `--dense-scales=s1,s2,...` (anywhere in argv; with --dense-tile only, which main checks).  Returns
     (argv without the flag, tuple of floats; patches.check_scales), or (argv unchanged, None) without it.  A bare flag, a malformed
     or invalid list, or the flag given twice, raises ValueError."""
-    rest, scales = [], None
-    for a in argv:
-        if a != DENSE_SCALES_FLAG and not a.startswith(DENSE_SCALES_FLAG + "="):
-            rest.append(a)
-            continue
-        if scales is not None:
-            raise ValueError(DENSE_SCALES_FLAG + " given more than once")
-        v = a[len(DENSE_SCALES_FLAG) + 1:]
-        try:
-            vals = [float(t) for t in v.split(",")] if v and v == v.strip() and " " not in v else None
-        except ValueError:
-            vals = None
-        if vals is None:
-            raise ValueError("%s: expected %s=s1,s2,... (factors such as 0.75,1,1.25)" % (a, DENSE_SCALES_FLAG))
-        scales = P.check_scales(vals)
-    return (list(argv) if scales is None else rest), scales
+    def factors(v):
+        if not v or v != v.strip() or " " in v:
+            raise ValueError(v)
+        return [float(t) for t in v.split(",")]
+    return _take_flag(argv, DENSE_SCALES_FLAG, lambda a, v: P.check_scales(_or_expected(
+        factors, a, v, DENSE_SCALES_FLAG + "=s1,s2,... (factors such as 0.75,1,1.25)")))
 
 
 DENSE_SE_FLAG = "--dense-se"
@@ -128,18 +130,7 @@ def parse_dense_se(argv):
     """isprs flavour: the optional `--dense-se=global` (anywhere in argv; with --dense-tile only, which main checks).  Returns (argv
     without the flag, "global"), or (argv unchanged, None) without it.  Any other value, a bare flag, or the flag given twice, raises
     ValueError."""
-    rest, se = [], None
-    for a in argv:
-        if a != DENSE_SE_FLAG and not a.startswith(DENSE_SE_FLAG + "="):
-            rest.append(a)
-            continue
-        if se is not None:
-            raise ValueError(DENSE_SE_FLAG + " given more than once")
-        v = a[len(DENSE_SE_FLAG) + 1:]
-        if v not in loops.DENSE_SE_MODES:
-            raise ValueError("%s: expected %s=%s" % (a, DENSE_SE_FLAG, "|".join(loops.DENSE_SE_MODES)))
-        se = v
-    return (list(argv) if se is None else rest), se
+    return _take_flag(argv, DENSE_SE_FLAG, _one_of(loops.DENSE_SE_MODES, DENSE_SE_FLAG))
 
 
 SCORE_MAPS_FLAG = "--score-maps"
@@ -149,19 +140,8 @@ def parse_score_maps(argv):
     """isprs flavour: the optional `--score-maps=kind,kind,...` (anywhere in argv; validate_test / generate_final_maps, which main
     checks).  Returns (argv without the flag, tuple of kinds; patches.parse_score_maps), or (argv unchanged, None) without it.  A bare
     flag, an unknown or repeated kind, or the flag given twice, raises ValueError."""
-    rest, kinds = [], None
-    for a in argv:
-        if a != SCORE_MAPS_FLAG and not a.startswith(SCORE_MAPS_FLAG + "="):
-            rest.append(a)
-            continue
-        if kinds is not None:
-            raise ValueError(SCORE_MAPS_FLAG + " given more than once")
-        try:
-            kinds = P.parse_score_maps(a[len(SCORE_MAPS_FLAG) + 1:])
-        except ValueError:
-            raise ValueError("%s: expected %s=%s (distinct kinds from these, comma-separated)"
-                             % (a, SCORE_MAPS_FLAG, ",".join(P.SCORE_KINDS))) from None
-    return (list(argv) if kinds is None else rest), kinds
+    return _take_flag(argv, SCORE_MAPS_FLAG, lambda a, v: _or_expected(
+        P.parse_score_maps, a, v, "%s=%s (distinct kinds from these, comma-separated)" % (SCORE_MAPS_FLAG, ",".join(P.SCORE_KINDS))))
 
 
 CALIBRATE_FLAG = "--calibrate-temperature"
@@ -172,36 +152,17 @@ def parse_calibrate_temperature(argv):
     """isprs flavour: the optional bare `--calibrate-temperature` (anywhere in argv; validate_test with --score-maps, which main
     checks).  Returns (argv without the flag, True), or (argv unchanged, None) without it.  A value, or the flag given twice, raises
     ValueError."""
-    rest, on = [], None
-    for a in argv:
-        if a != CALIBRATE_FLAG and not a.startswith(CALIBRATE_FLAG + "="):
-            rest.append(a)
-            continue
-        if a != CALIBRATE_FLAG:
-            raise ValueError("%s: %s takes no value" % (a, CALIBRATE_FLAG))
-        if on is not None:
-            raise ValueError(CALIBRATE_FLAG + " given more than once")
-        on = True
-    return (list(argv) if on is None else rest), on
+    def no_value(a, v):
+        raise ValueError("%s: %s takes no value" % (a, CALIBRATE_FLAG))
+    return _take_flag(argv, CALIBRATE_FLAG, no_value, bare=True)
 
 
 def parse_temperature(argv):
     """isprs flavour: the optional `--temperature=auto|T` (anywhere in argv; validate_test / generate_final_maps with --score-maps,
     which main checks).  Returns (argv without the flag, "auto" or the inverse temperature beta = 1 / T; patches.parse_temperature), or
     (argv unchanged, None) without it.  A bare flag, a value that is neither, or the flag given twice, raises ValueError."""
-    rest, beta = [], None
-    for a in argv:
-        if a != TEMPERATURE_FLAG and not a.startswith(TEMPERATURE_FLAG + "="):
-            rest.append(a)
-            continue
-        if beta is not None:
-            raise ValueError(TEMPERATURE_FLAG + " given more than once")
-        try:
-            beta = P.parse_temperature(a[len(TEMPERATURE_FLAG) + 1:])
-        except ValueError:
-            raise ValueError("%s: expected %s=auto or %s=T with a temperature T > 0, 1/64 <= 1/T <= 64"
-                             % (a, TEMPERATURE_FLAG, TEMPERATURE_FLAG)) from None
-    return (list(argv) if beta is None else rest), beta
+    return _take_flag(argv, TEMPERATURE_FLAG, lambda a, v: _or_expected(
+        P.parse_temperature, a, v, "%s=auto or %s=T with a temperature T > 0, 1/64 <= 1/T <= 64" % (TEMPERATURE_FLAG, TEMPERATURE_FLAG)))
 
 
 def temperature_file(output_path, step):
@@ -217,22 +178,15 @@ def parse_class_weights(argv, num_classes=None):
     """all flavours: the optional `--class-weights=balanced|median|w0,w1,...` (anywhere in argv; training).  Returns (argv without the
     flag, "balanced" / "median" / tuple of floats), or (argv unchanged, None) without it.  A bare flag, a malformed list, a negative
     or non-finite weight, a list whose length is not num_classes (when given), or the flag given twice, raises ValueError."""
-    rest, cw = [], None
-    for a in argv:
-        if a != CLASS_WEIGHTS_FLAG and not a.startswith(CLASS_WEIGHTS_FLAG + "="):
-            rest.append(a)
-            continue
-        if cw is not None:
-            raise ValueError(CLASS_WEIGHTS_FLAG + " given more than once")
-        form = "%s=%s|w0,w1,... (%s finite weights >= 0)" % (CLASS_WEIGHTS_FLAG, "|".join(P.CLASS_WEIGHT_RECIPES),
-                                                             "one per class:" if num_classes is None else str(num_classes))
-        try:
-            cw = P.parse_class_weights(a[len(CLASS_WEIGHTS_FLAG) + 1:])
-        except ValueError:
-            raise ValueError("%s: expected %s" % (a, form)) from None
+    form = "%s=%s|w0,w1,... (%s finite weights >= 0)" % (CLASS_WEIGHTS_FLAG, "|".join(P.CLASS_WEIGHT_RECIPES),
+                                                         "one per class:" if num_classes is None else str(num_classes))
+
+    def weights(a, v):
+        cw = _or_expected(P.parse_class_weights, a, v, form)
         if not isinstance(cw, str) and num_classes is not None and len(cw) != num_classes:
             raise ValueError("%s: %d weights given, expected %s" % (a, len(cw), form))
-    return (list(argv) if cw is None else rest), cw
+        return cw
+    return _take_flag(argv, CLASS_WEIGHTS_FLAG, weights)
 
 
 FOCAL_GAMMA_FLAG = "--focal-gamma"
@@ -242,18 +196,8 @@ def parse_focal_gamma(argv):
     """all flavours: the optional `--focal-gamma=G` (anywhere in argv; training).  Returns (argv without the flag, G as a float), or
     (argv unchanged, None) without it.  A bare flag, a value that is not one number, 0 or finite in (0, 8], or the flag given twice,
     raises ValueError."""
-    rest, g = [], None
-    for a in argv:
-        if a != FOCAL_GAMMA_FLAG and not a.startswith(FOCAL_GAMMA_FLAG + "="):
-            rest.append(a)
-            continue
-        if g is not None:
-            raise ValueError(FOCAL_GAMMA_FLAG + " given more than once")
-        try:
-            g = P.parse_focal_gamma(a[len(FOCAL_GAMMA_FLAG) + 1:])
-        except ValueError:
-            raise ValueError("%s: expected %s=G (one number, 0 or finite in (0, %g])" % (a, FOCAL_GAMMA_FLAG, P.MAX_FOCAL_GAMMA)) from None
-    return (list(argv) if g is None else rest), g
+    return _take_flag(argv, FOCAL_GAMMA_FLAG, lambda a, v: _or_expected(
+        P.parse_focal_gamma, a, v, "%s=G (one number, 0 or finite in (0, %g])" % (FOCAL_GAMMA_FLAG, P.MAX_FOCAL_GAMMA)))
 
 
 def print_params(list_params, argv):
@@ -414,12 +358,12 @@ def main(argv=None, device=None, comm=None):
             temperature = P.check_temperature_beta(float(np.load(temperature_file(output_path, step)).reshape(-1)[0]))
         except (ValueError, IndexError) as e:
             sys.exit(TEMPERATURE_FLAG + "=auto: " + temperature_file(output_path, step) + ": " + str(e))
+    path_kw = dict(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
         if calibrate:
-            fit = loops.fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, std_full, crop, comm,
-                                        dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+            fit = loops.fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, std_full, crop, comm, **path_kw)
             temperature = fit["beta"]
             if comm.rank == 0:
                 print("---- Iter " + str(step) + " -- Temperature= " + "{:.6f}".format(fit["temperature"]) +
@@ -428,13 +372,11 @@ def main(argv=None, device=None, comm=None):
                       " Iterations= " + str(fit["iterations"]))
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
-                                   score_maps=score_maps, temperature_beta=temperature)
+                                   step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se,
-                                         score_maps=score_maps, temperature_beta=temperature)
+                                         score_maps=score_maps, temperature_beta=temperature, **path_kw)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

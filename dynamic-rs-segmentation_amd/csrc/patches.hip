@@ -207,16 +207,24 @@ struct TilePlaceArgs {
   int h, w, K, T;
 };
 
+// the image pixel (y, x) under pixel (ty, tx) of tile i, if it lies in the tile's core: false for a thread past the tile, a box outside
+// the image or outside its tile, or a pixel outside the core
+__device__ __forceinline__ bool core_pixel(const int* boxes, int i, int ty, int tx, int h, int w, int T, int& y, int& x) {
+  if (tx >= T || ty >= T) return false;
+  const int* b = boxes + 6 * (size_t)i;
+  const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
+  if (y0 < 0 || x0 < 0 || y0 > h - T || x0 > w - T) return false;
+  if (cy0 < y0 || cy1 > y0 + T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + T || cx0 > cx1) return false;
+  y = y0 + ty;
+  x = x0 + tx;
+  return y >= cy0 && y < cy1 && x >= cx0 && x < cx1;
+}
+
 __global__ void tile_place_kernel(const TilePlaceArgs a) {
   const int i = blockIdx.z, ty = blockIdx.y;
   const int tx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tx >= a.T || ty >= a.T) return;
-  const int* b = a.boxes + 6 * (size_t)i;
-  const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
-  if (y0 < 0 || x0 < 0 || y0 > a.h - a.T || x0 > a.w - a.T) return;
-  if (cy0 < y0 || cy1 > y0 + a.T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + a.T || cx0 > cx1) return;
-  const int y = y0 + ty, x = x0 + tx;
-  if (y < cy0 || y >= cy1 || x < cx0 || x >= cx1) return;
+  int y, x;
+  if (!core_pixel(a.boxes, i, ty, tx, a.h, a.w, a.T, y, x)) return;
   const float* lg = a.logits + (((size_t)i * a.T + ty) * a.T + tx) * a.K;
   float* pp = a.prob + ((size_t)y * a.w + x) * a.K;
   for (int k = 0; k < a.K; ++k) pp[k] = lg[k];
@@ -236,51 +244,6 @@ __device__ __forceinline__ void dihedral_inv(int g, int T, int a, int b, int& si
   sj = (g & 1) ? T - 1 - tb : tb;
 }
 
-// conv1's haloed slab of the g-transformed T x T tile at (row, col) of map `map`: the normalisation of crop_kernel without
-// augmentation (fp64 until the one rounding on the store, bands 0..2), the source pixel permuted by sigma_g.  One thread per slab
-// pixel, so the stores are coalesced; a transposed code reads its source with a row stride (absorbed by L2 / the Infinity Cache).
-// inst is device data: a tile outside its map, or a map index out of range, leaves that patch's slab all zeros.
-struct CropDihedralArgs {
-  const void* tiles;
-  const long long* tile_off;
-  const int* tile_h; const int* tile_w;
-  int n_maps, C;
-  const int* inst;              // [B][3]: map, row, col
-  int g;
-  double mean[3], stdv[3];
-  float* out; int T, P, ld;     // [B][T+2P][T+2P][ld]
-};
-
-template <typename Tp>
-__global__ void crop_dihedral_kernel(const CropDihedralArgs a) {
-  const int Tp2 = a.T + 2 * a.P;
-  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (xx >= Tp2) return;
-  const int b = blockIdx.y / Tp2, yy = blockIdx.y - b * Tp2;
-  float* dst = a.out + ((size_t)(b * Tp2 + yy) * Tp2 + xx) * a.ld;
-  const int i = yy - a.P, j = xx - a.P;
-  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i >= 0 && i < a.T && j >= 0 && j < a.T) {
-    const int map = a.inst[3 * b], row = a.inst[3 * b + 1], col = a.inst[3 * b + 2];
-    if (map >= 0 && map < a.n_maps && row >= 0 && col >= 0 && row <= a.tile_h[map] - a.T && col <= a.tile_w[map] - a.T) {
-      int si, sj;
-      dihedral_fwd(a.g, a.T, i, j, si, sj);
-      const Tp* src = reinterpret_cast<const Tp*>(a.tiles) + a.tile_off[map] + ((size_t)(row + si) * a.tile_w[map] + (col + sj)) * a.C;
-      for (int c = 0; c < a.C; ++c) {
-        double e = (double)src[c];
-        if (c < 3) e = (e - a.mean[c]) / a.stdv[c];
-        v[c] = (float)e;
-      }
-    }
-  }
-  for (int c4 = 0; c4 < a.ld; c4 += 4) {
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = (c4 + k) < 8 ? v[(c4 + k) & 7] : 0.f;
-    *reinterpret_cast<f32x4*>(dst + c4) = o;
-  }
-}
-
 // the core of tile i (boxes as tile_place_kernel, checked the same way) gets the softmax of the logits the net computed for the
 // g-transformed tile, mapped back by sigma_g^-1, ADDED into acc; occur counts.  One thread per tile pixel in image order (coalesced
 // read-modify-write of acc); the cores of one plan are disjoint, so the plain read-modify-write is race-free and deterministic.
@@ -295,13 +258,8 @@ struct TilePlaceDihedralArgs {
 __global__ void tile_place_dihedral_kernel(const TilePlaceDihedralArgs a) {
   const int i = blockIdx.z, ty = blockIdx.y;
   const int tx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tx >= a.T || ty >= a.T) return;
-  const int* b = a.boxes + 6 * (size_t)i;
-  const int y0 = b[0], x0 = b[1], cy0 = b[2], cy1 = b[3], cx0 = b[4], cx1 = b[5];
-  if (y0 < 0 || x0 < 0 || y0 > a.h - a.T || x0 > a.w - a.T) return;
-  if (cy0 < y0 || cy1 > y0 + a.T || cy0 > cy1 || cx0 < x0 || cx1 > x0 + a.T || cx0 > cx1) return;
-  const int y = y0 + ty, x = x0 + tx;
-  if (y < cy0 || y >= cy1 || x < cx0 || x >= cx1) return;
+  int y, x;
+  if (!core_pixel(a.boxes, i, ty, tx, a.h, a.w, a.T, y, x)) return;
   int si, sj;
   dihedral_inv(a.g, a.T, ty, tx, si, sj);
   const float* lg = a.logits + (((size_t)i * a.T + si) * a.T + sj) * a.K;
@@ -328,22 +286,25 @@ __device__ __forceinline__ void resample_axis(int d, int n, int ns, int& i0, int
   l = src - (double)i0;
 }
 
-// conv1's haloed slab of the g-transformed T x T tile at (row, col) of map `map` resampled to hs x ws: the slab pixel's source on the
-// scaled grid is sigma_g as in crop_dihedral_kernel, its value the bilinear mix of four source pixels in fp64, then the normalisation
-// of crop_kernel (bands 0..2) and one rounding.  One fused gather: no resized image exists.  One thread per slab pixel in store order.
-struct CropResampledArgs {
+// conv1's haloed slab of the g-transformed T x T tile at (row, col) of map `map` (drs_crop_dihedral), or of that map bilinearly resampled
+// to hs x ws (RESAMPLE: drs_crop_resampled; row, col on that grid): the slab pixel's source is permuted by sigma_g; its value is the source
+// pixel's, or the bilinear mix of four source pixels in fp64 -- one fused gather: no resized image exists --; then the normalisation of
+// crop_kernel without augmentation (fp64 until the one rounding on the store, bands 0..2).  One thread per slab pixel, so the stores are
+// coalesced; a transposed code reads its source with a row stride (absorbed by L2 / the Infinity Cache).  inst is device data: a tile
+// outside its map or grid, or a map index out of range, leaves that patch's slab all zeros.
+struct CropTilesArgs {
   const void* tiles;
   const long long* tile_off;
   const int* tile_h; const int* tile_w;
   int n_maps, C;
-  const int* inst;              // [B][3]: map, row, col on the hs x ws grid
-  int hs, ws, g;
+  const int* inst;              // [B][3]: map, row, col (on the hs x ws grid with RESAMPLE)
+  int hs, ws, g;                // hs, ws: with RESAMPLE only
   double mean[3], stdv[3];
   float* out; int T, P, ld;     // [B][T+2P][T+2P][ld]
 };
 
-template <typename Tp>
-__global__ void crop_resampled_kernel(const CropResampledArgs a) {
+template <typename Tp, bool RESAMPLE>
+__global__ void crop_tiles_kernel(const CropTilesArgs a) {
   const int Tp2 = a.T + 2 * a.P;
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx >= Tp2) return;
@@ -353,22 +314,27 @@ __global__ void crop_resampled_kernel(const CropResampledArgs a) {
   float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (i >= 0 && i < a.T && j >= 0 && j < a.T) {
     const int map = a.inst[3 * b], row = a.inst[3 * b + 1], col = a.inst[3 * b + 2];
-    if (map >= 0 && map < a.n_maps && row >= 0 && col >= 0 && row <= a.hs - a.T && col <= a.ws - a.T) {
+    if (map >= 0 && map < a.n_maps && row >= 0 && col >= 0 &&
+        row <= (RESAMPLE ? a.hs : a.tile_h[map]) - a.T && col <= (RESAMPLE ? a.ws : a.tile_w[map]) - a.T) {
       int si, sj;
       dihedral_fwd(a.g, a.T, i, j, si, sj);
       const int h = a.tile_h[map], w = a.tile_w[map];
-      int y0, y1, x0, x1;
-      double ly, lx;
-      resample_axis(row + si, h, a.hs, y0, y1, ly);
-      resample_axis(col + sj, w, a.ws, x0, x1, lx);
       const Tp* base = reinterpret_cast<const Tp*>(a.tiles) + a.tile_off[map];
+      int y0 = row + si, y1 = y0, x0 = col + sj, x1 = x0;
+      double ly = 0.0, lx = 0.0;
+      if (RESAMPLE) {
+        resample_axis(row + si, h, a.hs, y0, y1, ly);
+        resample_axis(col + sj, w, a.ws, x0, x1, lx);
+      }
       const Tp* s00 = base + ((size_t)y0 * w + x0) * a.C;
       const Tp* s01 = base + ((size_t)y0 * w + x1) * a.C;
       const Tp* s10 = base + ((size_t)y1 * w + x0) * a.C;
       const Tp* s11 = base + ((size_t)y1 * w + x1) * a.C;
       for (int c = 0; c < a.C; ++c) {
-        double e = (1.0 - ly) * ((1.0 - lx) * (double)s00[c] + lx * (double)s01[c]) +
-                   ly * ((1.0 - lx) * (double)s10[c] + lx * (double)s11[c]);
+        double e = (double)s00[c];
+        if (RESAMPLE)
+          e = (1.0 - ly) * ((1.0 - lx) * (double)s00[c] + lx * (double)s01[c]) +
+              ly * ((1.0 - lx) * (double)s10[c] + lx * (double)s11[c]);
         if (c < 3) e = (e - a.mean[c]) / a.stdv[c];
         v[c] = (float)e;
       }
@@ -450,6 +416,47 @@ __device__ __forceinline__ unsigned char score_byte(float s) {
   return (unsigned char)(int)(255.f * s + 0.5f);
 }
 
+// The three blocks drs_stitch_finalize_scores' two kernels share.  score_label: the first maximum of the fp64 quotients s[k] / oc,
+// stitch_finalize_kernel's expression.
+template <int K>
+__device__ __forceinline__ int score_label(const float (&s)[K], unsigned oc) {
+  int am = 0;
+  double best = (double)s[0] / (double)oc;
+#pragma unroll
+  for (int k = 1; k < K; ++k) {
+    const double v = (double)s[k] / (double)oc;
+    if (v > best) { best = v; am = k; }
+  }
+  return am;
+}
+
+// no window or tile reached pixel i: nothing is known about it
+__device__ __forceinline__ void score_uncovered(size_t i, unsigned char* confidence, unsigned char* margin, unsigned char* entropy) {
+  if (confidence) confidence[i] = 0;
+  if (margin) margin[i] = 0;
+  if (entropy) entropy[i] = 255;
+}
+
+// the bytes of pixel i from its probability vector p, its label am and its normalised entropy hn (formed by the caller, and only where
+// that map is asked for): confidence p[am], margin p[am] - the largest other p, entropy hn
+template <int K>
+__device__ __forceinline__ void score_write(size_t i, const float (&p)[K], int am, float hn, unsigned char* confidence,
+                                            unsigned char* margin, unsigned char* entropy) {
+  float top = p[0], second = 0.f;
+#pragma unroll
+  for (int k = 1; k < K; ++k) top = k == am ? p[k] : top;
+  bool first = true;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (k == am) continue;
+    second = first ? p[k] : fmaxf(second, p[k]);
+    first = false;
+  }
+  if (confidence) confidence[i] = score_byte(top);
+  if (margin) margin[i] = score_byte(top - second);
+  if (entropy) entropy[i] = score_byte(hn);
+}
+
 // drs_stitch_finalize with the per-pixel score maps (include/drs.h: confidence, margin, normalised entropy) beside the label: one
 // thread per pixel, grid-stride, the pixel's K sums read once into registers (K is a template parameter: the loops unroll and
 // nothing spills).  The label is stitch_finalize_kernel's expression, the probability vector is prob_from_sums'.  Every output is one
@@ -465,53 +472,31 @@ __global__ void score_maps_kernel(const float* __restrict__ sums, const unsigned
     float s[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) s[k] = sums[i * K + k];
-    int am = 0;
-    double best = (double)s[0] / (double)oc;
-#pragma unroll
-    for (int k = 1; k < K; ++k) {
-      const double v = (double)s[k] / (double)oc;
-      if (v > best) { best = v; am = k; }
-    }
+    const int am = score_label<K>(s, oc);
     if (labels) labels[i] = (unsigned char)am;
     if (!want_scores) continue;
-    if (!o) {          // no window or tile reached this pixel: nothing is known about it
-      if (confidence) confidence[i] = 0;
-      if (margin) margin[i] = 0;
-      if (entropy) entropy[i] = 255;
+    if (!o) {
+      score_uncovered(i, confidence, margin, entropy);
       continue;
     }
     const float ocf = (float)oc;
     float p[K], mx = 0.f;
     const float se = prob_from_sums(s, ocf, K, sums_are_prob, p, mx);
-    float top = p[0], second = 0.f;
+    float hn = 0.f;          // one class: the entropy is 0, and so is its normalised form here
+    if (entropy && K > 1) {
+      float acc = 0.f;
+      if (sums_are_prob) {
 #pragma unroll
-    for (int k = 1; k < K; ++k) top = k == am ? p[k] : top;
-    bool first = true;
+        for (int k = 0; k < K; ++k) acc += p[k] > 0.f ? p[k] * logf(p[k]) : 0.f;      // 0 ln 0 = 0
+        hn = -acc / logf((float)K);
+      } else {
+        // -sum p ln p with ln p_k = (v_k - max) - ln se: no logarithm of an underflowed p_k is formed
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-      if (k == am) continue;
-      second = first ? p[k] : fmaxf(second, p[k]);
-      first = false;
-    }
-    if (confidence) confidence[i] = score_byte(top);
-    if (margin) margin[i] = score_byte(top - second);
-    if (entropy) {
-      float hn = 0.f;          // one class: the entropy is 0, and so is its normalised form here
-      if (K > 1) {
-        float acc = 0.f;
-        if (sums_are_prob) {
-#pragma unroll
-          for (int k = 0; k < K; ++k) acc += p[k] > 0.f ? p[k] * logf(p[k]) : 0.f;      // 0 ln 0 = 0
-          hn = -acc / logf((float)K);
-        } else {
-          // -sum p ln p with ln p_k = (v_k - max) - ln se: no logarithm of an underflowed p_k is formed
-#pragma unroll
-          for (int k = 0; k < K; ++k) acc += p[k] * (s[k] / ocf - mx);
-          hn = (logf(se) - acc) / logf((float)K);
-        }
+        for (int k = 0; k < K; ++k) acc += p[k] * (s[k] / ocf - mx);
+        hn = (logf(se) - acc) / logf((float)K);
       }
-      entropy[i] = score_byte(hn);
     }
+    score_write<K>(i, p, am, hn, confidence, margin, entropy);
   }
 }
 
@@ -531,19 +516,11 @@ __global__ void score_maps_t_kernel(const float* __restrict__ sums, const unsign
     float s[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) s[k] = sums[i * K + k];
-    int am = 0;
-    double best = (double)s[0] / (double)oc;
-#pragma unroll
-    for (int k = 1; k < K; ++k) {
-      const double v = (double)s[k] / (double)oc;
-      if (v > best) { best = v; am = k; }
-    }
+    const int am = score_label<K>(s, oc);
     if (labels) labels[i] = (unsigned char)am;
     if (!want_scores) continue;
-    if (!o) {          // no window or tile reached this pixel: nothing is known about it
-      if (confidence) confidence[i] = 0;
-      if (margin) margin[i] = 0;
-      if (entropy) entropy[i] = 255;
+    if (!o) {
+      score_uncovered(i, confidence, margin, entropy);
       continue;
     }
     const float ocf = (float)oc;
@@ -564,28 +541,14 @@ __global__ void score_maps_t_kernel(const float* __restrict__ sums, const unsign
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) p[k] = p[k] / se;
-    float top = p[0], second = 0.f;
+    float hn = 0.f;
+    if (entropy && K > 1) {
+      float acc = 0.f;
 #pragma unroll
-    for (int k = 1; k < K; ++k) top = k == am ? p[k] : top;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      if (k == am) continue;
-      second = first ? p[k] : fmaxf(second, p[k]);
-      first = false;
+      for (int k = 0; k < K; ++k) acc += p[k] * t[k];
+      hn = (logf(se) - acc) / logf((float)K);
     }
-    if (confidence) confidence[i] = score_byte(top);
-    if (margin) margin[i] = score_byte(top - second);
-    if (entropy) {
-      float hn = 0.f;          // one class: the entropy is 0, and so is its normalised form here
-      if (K > 1) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) acc += p[k] * t[k];
-        hn = (logf(se) - acc) / logf((float)K);
-      }
-      entropy[i] = score_byte(hn);
-    }
+    score_write<K>(i, p, am, hn, confidence, margin, entropy);
   }
 }
 
@@ -601,6 +564,55 @@ __global__ void softmax_accumulate_kernel(const float* __restrict__ prob, const 
     }
     for (int k = 0; k < K; ++k) acc[i * K + k] += e[k] / sum;
   }
+}
+
+// drs_crop_dihedral / drs_crop_resampled (RESAMPLE: on the hs x ws grid): the argument checks and the launch
+template <bool RESAMPLE>
+int launch_crop_tiles(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps, int C,
+                      const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
+                      float* out, void* stream) {
+  if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
+  if (RESAMPLE && (hs < 1 || ws < 1)) return DRS_ERR_ARG;
+  const int Tp2 = T + 2 * P;
+  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
+  CropTilesArgs a;
+  a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst;
+  a.hs = hs; a.ws = ws; a.g = g;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+  a.out = out; a.T = T; a.P = P; a.ld = ld;
+  dim3 grid((Tp2 + 63) / 64, B * Tp2);
+  if (tiles_are_f64) DRS_LAUNCH((crop_tiles_kernel<double, RESAMPLE>), grid, dim3(64), 0, (hipStream_t)stream, a);
+  else DRS_LAUNCH((crop_tiles_kernel<float, RESAMPLE>), grid, dim3(64), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+// drs_stitch_finalize_scores / drs_stitch_finalize_scores_t (TEMPERED: at the inverse temperature beta): the argument checks, the grid
+// and the instantiation for K
+template <bool TEMPERED>
+int launch_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta, unsigned char* labels,
+                  unsigned char* confidence, unsigned char* margin, unsigned char* entropy, void* stream) {
+  if (!sums || !occur || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
+  if (!labels && !confidence && !margin && !entropy) return DRS_ERR_ARG;
+  const size_t n = (size_t)h * w;
+  const size_t nb = (n + 255) / 256;
+  const dim3 grid(nb < 4096 ? (unsigned)nb : 4096u);
+  const int prob = sums_are_prob ? 1 : 0;
+#define DRS_SCORES_CASE(KK)                                                                                                        \
+  case KK:                                                                                                                         \
+    if (TEMPERED)                                                                                                                  \
+      DRS_LAUNCH(score_maps_t_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, beta, labels, confidence, \
+                 margin, entropy);                                                                                                 \
+    else                                                                                                                           \
+      DRS_LAUNCH(score_maps_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, labels, confidence, margin, \
+                 entropy);                                                                                                         \
+    break;
+  switch (K) {
+    DRS_SCORES_CASE(1) DRS_SCORES_CASE(2) DRS_SCORES_CASE(3) DRS_SCORES_CASE(4)
+    DRS_SCORES_CASE(5) DRS_SCORES_CASE(6) DRS_SCORES_CASE(7) DRS_SCORES_CASE(8)
+  }
+#undef DRS_SCORES_CASE
+  return DRS_LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -657,18 +669,8 @@ int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h,
 int drs_crop_dihedral(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
                       int C, const int* inst, int g, const double* mean3, const double* std3, int B, int T, int P, int ld, float* out,
                       void* stream) {
-  if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
-  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
-  const int Tp2 = T + 2 * P;
-  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
-  CropDihedralArgs a;
-  a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst; a.g = g;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
-  a.out = out; a.T = T; a.P = P; a.ld = ld;
-  dim3 grid((Tp2 + 63) / 64, B * Tp2);
-  if (tiles_are_f64) DRS_LAUNCH(crop_dihedral_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a);
-  else DRS_LAUNCH(crop_dihedral_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a);
-  return DRS_LAUNCH_CHECK();
+  return launch_crop_tiles<false>(tiles, tiles_are_f64, tile_off, tile_h, tile_w, n_maps, C, inst, 0, 0, g, mean3, std3, B, T, P, ld, out,
+                                  stream);
 }
 
 int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
@@ -685,20 +687,8 @@ int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits
 int drs_crop_resampled(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
                        int C, const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
                        float* out, void* stream) {
-  if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
-  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
-  if (hs < 1 || ws < 1) return DRS_ERR_ARG;
-  const int Tp2 = T + 2 * P;
-  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
-  CropResampledArgs a;
-  a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst;
-  a.hs = hs; a.ws = ws; a.g = g;
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
-  a.out = out; a.T = T; a.P = P; a.ld = ld;
-  dim3 grid((Tp2 + 63) / 64, B * Tp2);
-  if (tiles_are_f64) DRS_LAUNCH(crop_resampled_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a);
-  else DRS_LAUNCH(crop_resampled_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a);
-  return DRS_LAUNCH_CHECK();
+  return launch_crop_tiles<true>(tiles, tiles_are_f64, tile_off, tile_h, tile_w, n_maps, C, inst, hs, ws, g, mean3, std3, B, T, P, ld, out,
+                                 stream);
 }
 
 int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs, int ws, int K, int src_is_prob, int h, int w, float* acc,
@@ -721,23 +711,7 @@ int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int
 int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob,
                                unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
                                void* stream) {
-  if (!sums || !occur || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
-  if (!labels && !confidence && !margin && !entropy) return DRS_ERR_ARG;
-  const size_t n = (size_t)h * w;
-  const size_t nb = (n + 255) / 256;
-  const dim3 grid(nb < 4096 ? (unsigned)nb : 4096u);
-  const int prob = sums_are_prob ? 1 : 0;
-#define DRS_SCORES_CASE(KK)                                                                                                        \
-  case KK:                                                                                                                         \
-    DRS_LAUNCH(score_maps_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, labels, confidence, margin,   \
-               entropy);                                                                                                           \
-    break;
-  switch (K) {
-    DRS_SCORES_CASE(1) DRS_SCORES_CASE(2) DRS_SCORES_CASE(3) DRS_SCORES_CASE(4)
-    DRS_SCORES_CASE(5) DRS_SCORES_CASE(6) DRS_SCORES_CASE(7) DRS_SCORES_CASE(8)
-  }
-#undef DRS_SCORES_CASE
-  return DRS_LAUNCH_CHECK();
+  return launch_scores<false>(sums, occur, h, w, K, sums_are_prob, 1.0f, labels, confidence, margin, entropy, stream);
 }
 
 int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta,
@@ -745,23 +719,7 @@ int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, i
                                  void* stream) {
   if (!(beta >= 1.0f / 64.0f && beta <= 64.0f)) return DRS_ERR_ARG;          // (a NaN fails both comparisons)
   if (beta == 1.0f) return drs_stitch_finalize_scores(sums, occur, h, w, K, sums_are_prob, labels, confidence, margin, entropy, stream);
-  if (!sums || !occur || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
-  if (!labels && !confidence && !margin && !entropy) return DRS_ERR_ARG;
-  const size_t n = (size_t)h * w;
-  const size_t nb = (n + 255) / 256;
-  const dim3 grid(nb < 4096 ? (unsigned)nb : 4096u);
-  const int prob = sums_are_prob ? 1 : 0;
-#define DRS_SCORES_T_CASE(KK)                                                                                                      \
-  case KK:                                                                                                                         \
-    DRS_LAUNCH(score_maps_t_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, sums, occur, n, prob, beta, labels, confidence,   \
-               margin, entropy);                                                                                                   \
-    break;
-  switch (K) {
-    DRS_SCORES_T_CASE(1) DRS_SCORES_T_CASE(2) DRS_SCORES_T_CASE(3) DRS_SCORES_T_CASE(4)
-    DRS_SCORES_T_CASE(5) DRS_SCORES_T_CASE(6) DRS_SCORES_T_CASE(7) DRS_SCORES_T_CASE(8)
-  }
-#undef DRS_SCORES_T_CASE
-  return DRS_LAUNCH_CHECK();
+  return launch_scores<true>(sums, occur, h, w, K, sums_are_prob, beta, labels, confidence, margin, entropy, stream);
 }
 
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream) {

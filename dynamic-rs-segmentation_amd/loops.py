@@ -11,6 +11,7 @@ side files), with every per-pixel operation on the device.  Differences that are
   * the TensorFlow checkpoint becomes `model-<step>.npz` (same names, same `-<step>` resume convention, isprs:1708-1715);
   * under data parallelism every rank runs the same host code with the same RNG streams and takes its slice of the batch.
 """
+import collections
 import datetime
 import math
 import os
@@ -484,8 +485,83 @@ def _finalize(sums_ptr, occur_ptr, rows, w, K, sums_are_prob, out, smaps, pix0, 
               ptr[0], ptr[1], ptr[2], st)
 
 
-def _score_views(smaps, h, w):
-    return {k: v.view(h, w) for k, v in smaps.items()}
+def _labels_tail(net, sums, occur, top, row0, rows, h, w, sums_are_prob, scores, beta, comm=None):
+    """The tail of every inference path: labels -- and, with `scores` (_check_scores' kinds), score maps -- of image rows
+    [row0, row0 + rows) into zeroed [h*w] maps (_finalize), from accumulators whose first element belongs to image row `top`.  With a
+    `comm` of several ranks, each of which wrote only the rows it owns, the uint8 maps are gathered by one sum all-reduce each.
+    Returns (labels [h, w], {kind: map [h, w]} or None), device tensors."""
+    K = net.plan.K
+    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
+    smaps = _score_buffers(scores, h * w, net.dev)
+    if rows > 0:
+        d0 = row0 - top
+        _finalize(sums.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, rows, w, K, sums_are_prob, out, smaps, row0 * w,
+                  net._stream(), beta)
+    if comm is not None and comm.world > 1:
+        comm.all_reduce_sum(out)
+        for v in (smaps or {}).values():
+            comm.all_reduce_sum(v)
+    return out.view(h, w), None if smaps is None else {k: v.view(h, w) for k, v in smaps.items()}
+
+
+def _public(res, return_sums, scores, count=True):
+    """The argument-dependent arity of the public predict_* returns, over the fixed shapes their workers return: (sums, occur, count)
+    with return_sums, else (labels, count, score maps or None).  count=False leaves the count out (predict_tile_multiscale has none)."""
+    if return_sums:
+        return res if count else res[:2]
+    labels, n, smaps = res
+    out = ((labels, n) if count else (labels,)) + (() if scores is None else (smaps,))
+    return out if len(out) > 1 else out[0]
+
+
+DENSE_SE_MODES = ("global",)
+
+
+class InferencePath(collections.namedtuple("InferencePath", "crop_size crop_sizes flavour dense_tile dense_tta dense_scales dense_se",
+                                           defaults=(None, None, "isprs", None, None, None, None))):
+    """Which whole-map inference validate_test, generate_final_maps and fit_temperature run, from their keyword arguments: the sliding
+    windows at crop_size (bands of window rows per rank under data parallelism), the multi-size windows (crop_sizes), or overlap-tile
+    inference (dense_tile: an int, 0 = the default side) with its dihedral (dense_tta), multi-scale (dense_scales) and whole-image
+    squeeze-and-excitation (dense_se) options."""
+    __slots__ = ()
+
+    def check(self):
+        """ValueError for options that do not go together, or that are malformed; the net is not needed"""
+        if self.dense_tile is None:
+            if self.dense_tta is not None:
+                raise ValueError("test-time augmentation needs overlap-tile inference (dense_tile): the sliding-window map depends on the "
+                                 "patch size and has no exact dihedral form")
+            if self.dense_scales is not None:
+                raise ValueError("multi-scale test-time augmentation needs overlap-tile inference (dense_tile): the sliding windows take "
+                                 "their scales from the patch size (crop_sizes)")
+            if self.dense_se is not None:
+                raise ValueError("whole-image squeeze-and-excitation gates need overlap-tile inference (dense_tile): a sliding window is "
+                                 "gated by its own mean")
+            return
+        if self.dense_tta is not None:
+            P.tta_group(self.dense_tta)
+        if self.dense_scales is not None:
+            P.check_scales(self.dense_scales)
+        if self.dense_se is not None and self.dense_se not in DENSE_SE_MODES:
+            raise ValueError("dense_se must be one of %s, not %r" % (list(DENSE_SE_MODES), self.dense_se))
+        if self.crop_sizes:
+            raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
+
+    @property
+    def sums_are_prob(self):
+        """What the path accumulates per pixel (DESIGN.md 8a.4's table): sums of probability vectors (the multi-size windows; overlap
+        tiles with tta or scales) or of logits (the windows and their bands; plain overlap tiles).  The one place that decides it."""
+        if self.dense_tile is not None:
+            return self.dense_tta is not None or self.dense_scales is not None
+        return bool(self.crop_sizes)
+
+    def run(self, net, pool, map_index, batch_size, mean_full, std_full, comm, scores=None, beta=None, return_sums=False):
+        """One map through the path.  Returns (labels [h, w], window or tile count -- None for the multi-size windows --, {kind: score
+        map} or None); with return_sums (sums [h*w*K], occur [h*w], sums_are_prob), whole on every rank.  scores / beta: as
+        _check_scores / _check_temperature return them."""
+        worker = _dense if self.dense_tile is not None else _multisize if self.crop_sizes else _window
+        res = worker(self, net, pool, map_index, batch_size, mean_full, std_full, comm, scores, beta, return_sums)
+        return (res[0], res[1], self.sums_are_prob) if return_sums else res
 
 
 def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm=None, return_sums=False, flavour="isprs",
@@ -498,22 +574,24 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
     {kind: uint8 device tensor [h, w]} of per-pixel score maps of the averaged logits (drs_stitch_finalize_scores).
     temperature_beta (opt-in; with scores only): the maps are those of softmax(beta x averaged logits); the labels
     do not change."""
+    scores = _check_scores(scores, return_sums)
+    beta = _check_temperature(temperature_beta, scores)
+    return _public(_window(InferencePath(crop_size=crop_size, flavour=flavour), net, pool, map_index, batch_size, mean_full, std_full,
+                           comm or NoComm(), scores, beta, return_sums), return_sums, scores)
+
+
+def _window(path, net, pool, map_index, batch_size, mean_full, std_full, comm, scores, beta, return_sums):
+    """predict_tile's worker: (labels, window count, score maps or None), or (prob, occur, window count) with return_sums"""
     from . import _lib
-    comm = comm or NoComm()
+    crop_size, flavour = path.crop_size, path.flavour
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     stride = int(math.floor(crop_size / 2.0))
     n_h, n_w = P.window_counts(h, w, crop_size, stride)
     total = n_h * n_w
-    scores = _check_scores(scores, return_sums)
-    beta = _check_temperature(temperature_beta, scores)
     if comm.world > 1 and not return_sums and flavour == "isprs" and n_h >= comm.world:
-        if scores is not None:
-            out, sm = _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=scores,
-                                          temperature_beta=beta)
-            return out, total, sm
-        return _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm), total
-    smaps = _score_buffers(scores, h * w, net.dev)
+        labels, smaps = _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores, beta)
+        return labels, total, smaps
     prob = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
     occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
     # batches are the REFERENCE's: batch i starts where its `batch_size` puts it (for flavour="contest" that start depends on the
@@ -532,16 +610,13 @@ def predict_tile(net, pool, map_index, crop_size, batch_size, mean_full, std_ful
             P.crop_to_net(net, pool, inst, crop_size, mean_full, std_full)
             _, logits = net.forward(len(pos), crop_size, want_logits=True)
             _lib.call("drs_stitch_accumulate", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, crop_size, stride, f0 + c0, len(pos), st)
-    if comm.world > 1:          # (the multi-scale caller needs the whole sums; the plain path below exchanges bands instead)
+    if comm.world > 1:          # (the multi-scale caller needs the whole sums; the plain path above exchanges bands instead)
         comm.all_reduce_sum(prob)
         comm.all_reduce_sum(occur)
     if return_sums:
         return prob, occur, total
-    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(prob.data_ptr(), occur.data_ptr(), h, w, K, False, out, smaps, 0, st, beta)
-    if smaps is not None:
-        return out.view(h, w), total, _score_views(smaps, h, w)
-    return out.view(h, w), total
+    labels, smaps = _labels_tail(net, prob, occur, 0, 0, h, h, w, path.sums_are_prob, scores, beta)
+    return labels, total, smaps
 
 
 def band_plan(h, crop_size, stride, n_h, world):
@@ -557,21 +632,19 @@ def band_plan(h, crop_size, stride, n_h, world):
     return a, top, bot, own
 
 
-def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=None, temperature_beta=None):
+def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, std_full, comm, scores=None, beta=None):
     """Sliding-window inference of one tile on several ranks: the window rows are cut into one contiguous band per
     rank, every rank overlap-adds its windows into a band-sized accumulator ([rows of the band][w][K] instead of the whole
     [h][w][K]), only the rows a band shares with the next ranks' territory are exchanged (one sum all-reduce of a buffer in which
     every rank fills its own segment: (world-1) x (S - stride) rows instead of the whole map), each rank divides and arg-maxes the
     rows it owns, and the uint8 label bands are gathered.  Sums are formed as (own windows in window order) + (lower ranks'
     contributions in rank order): deterministic, and equal to the single-rank result up to the association of those float sums.
-    scores, temperature_beta (predict_tile's): every rank also writes the score maps of the rows it owns, gathered like the labels;
-    returns (labels, {kind: map})."""
+    scores, beta (_window's): every rank also writes the score maps of the rows it owns, gathered like the labels.
+    Returns (labels, {kind: map} or None)."""
     from . import _lib
-    beta = _check_temperature(temperature_beta, scores)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
     S = crop_size
-    smaps = _score_buffers(scores, h * w, net.dev)
     stride = int(math.floor(S / 2.0))
     n_h, n_w = P.window_counts(h, w, S, stride)
     W, r = comm.world, comm.rank
@@ -608,16 +681,8 @@ def _predict_tile_bands(net, pool, map_index, crop_size, batch_size, mean_full, 
             src, dst = off[q] + (lo - own[q + 1]), lo - top[r]
             prob[dst * w * K:(dst + hi - lo) * w * K] += xp[src * w * K:(src + hi - lo) * w * K]
             occur[dst * w:(dst + hi - lo) * w] += xo[src * w:(src + hi - lo) * w]
-    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    n_own, d0 = own[r + 1] - own[r], own[r] - top[r]
-    _finalize(prob.data_ptr() + d0 * w * K * 4, occur.data_ptr() + d0 * w * 4, n_own, w, K, False, out, smaps, own[r] * w, st,
-              beta)
-    comm.all_reduce_sum(out)    # every rank wrote only the rows it owns: the sum is the gather of the uint8 label bands
-    if smaps is not None:
-        for v in smaps.values():
-            comm.all_reduce_sum(v)
-        return out.view(h, w), _score_views(smaps, h, w)
-    return out.view(h, w)
+    # every rank finalizes only the rows it owns: the sum all-reduce is the gather of the uint8 bands
+    return _labels_tail(net, prob, occur, top[r], own[r], own[r + 1] - own[r], h, w, False, scores, beta, comm)
 
 
 def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_full, std_full, comm=None, scores=None,
@@ -627,24 +692,27 @@ def predict_tile_multiscale(net, pool, map_index, crop_sizes, batch_size, mean_f
     the number of scales, which leaves the arg-max where it is).  temperature_beta (with scores only): the maps are of
     softmax(beta x log of that mean).  return_sums (not with scores): returns (the summed softmax vectors [h*w*K],
     occur = the number of scales everywhere) instead, on every rank."""
+    scores = _check_scores(scores, return_sums)
+    beta = _check_temperature(temperature_beta, scores)
+    return _public(_multisize(InferencePath(crop_sizes=crop_sizes), net, pool, map_index, batch_size, mean_full, std_full,
+                              comm or NoComm(), scores, beta, return_sums), return_sums, scores, count=False)
+
+
+def _multisize(path, net, pool, map_index, batch_size, mean_full, std_full, comm, scores, beta, return_sums):
+    """predict_tile_multiscale's worker: (labels, None, score maps or None), or (acc, occur, None) with return_sums"""
     from . import _lib
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
-    scores = _check_scores(scores, return_sums)
-    beta = _check_temperature(temperature_beta, scores)
-    smaps = _score_buffers(scores, h * w, net.dev)
     acc = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
-    for s_ in crop_sizes:
-        prob, occur, _ = predict_tile(net, pool, map_index, int(s_), batch_size, mean_full, std_full, comm, return_sums=True)
+    for s_ in path.crop_sizes:
+        prob, occur, _ = _window(path._replace(crop_size=int(s_), crop_sizes=None), net, pool, map_index, batch_size, mean_full, std_full,
+                                 comm, None, None, True)
         _lib.call("drs_softmax_accumulate", prob.data_ptr(), occur.data_ptr(), h, w, K, acc.data_ptr(), net._stream())
-    ones = torch.full((h * w,), 1 if smaps is None and not return_sums else len(crop_sizes), dtype=torch.int32, device=net.dev)
+    ones = torch.full((h * w,), 1 if scores is None and not return_sums else len(path.crop_sizes), dtype=torch.int32, device=net.dev)
     if return_sums:
-        return acc, ones
-    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(acc.data_ptr(), ones.data_ptr(), h, w, K, True, out, smaps, 0, net._stream(), beta)
-    if smaps is not None:
-        return out.view(h, w), _score_views(smaps, h, w)
-    return out.view(h, w)
+        return acc, ones, None
+    labels, smaps = _labels_tail(net, acc, ones, 0, 0, h, h, w, path.sums_are_prob, scores, beta)
+    return labels, None, smaps
 
 
 # ------------------------------------------------------------------------------------------------- whole tiles, overlap-tile
@@ -681,12 +749,9 @@ def dense_twin(net, T, batch_size):
     return twin
 
 
-DENSE_SE_MODES = ("global",)
-
-
-def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g=0):
+def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g):
     """The gate sweeps of predict_tile_dense(se="global") for the image transformed by the dihedral code g: for SE
-    block j = 0, 1, ... every tile of this rank (`mine`, indices into the plan `boxes`) is cropped transformed by g (crop(inst)) and
+    block j = 0, 1, ... every tile of this rank (`mine`, indices into the plan `boxes`) is cropped transformed by g (crop(inst, g)) and
     forwarded up to the block SE j follows with the gates before it (forward_staged), its activated output summed per channel over the
     tile's core -- as it lies in the transformed tile, patches.dihedral_core_boxes -- into the twin's fp64 se_sum[j], which is zeroed
     on the stream when the sweep begins and summed over the ranks when it ends; se_gate[j] is made of the mean over `count` pixels."""
@@ -695,12 +760,50 @@ def _se_global_gates(twin, crop, T, boxes, mine, map_index, count, comm, g=0):
         twin.se_sum[j].zero_()
         for c0 in range(0, len(mine), twin.b_max):
             sel = mine[c0:c0 + twin.b_max]
-            crop(np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1))
+            crop(np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1), g)
             twin.forward_staged(len(sel), T, j, local.data_ptr() + int(sel[0]) * 6 * 4)
         if comm.world > 1:
             comm.all_reduce_sum(twin.se_sum[j])
         twin.se_gate_finish(j, count)
     twin._keep_boxes = local             # alive until the stream has consumed it
+
+
+def _tile_pass(twin, T, boxes, n_rows, hg, wg, G, se, prob, occur, comm, crop, map_index):
+    """One dense plan over one hg x wg grid (the map, or the map at one scale): this rank's tiles -- a contiguous run of the plan's n_rows
+    tile rows, as even as possible over the ranks -- are cropped (crop(inst, g) fills the twin's input slab with the tiles at `inst`
+    rows (map, row, col) transformed by the code g: crop_to_net on the plain path, which has no g, crop_dihedral_to_net with tta,
+    crop_resampled_to_net with scales), forwarded, and their cores placed into prob / occur [hg][wg]: the logits copied
+    (drs_tile_place) without tta (G None), else the softmax mapped back by g^-1 ADDED (drs_tile_place_dihedral).  Without se a batch of
+    tiles runs every code of G, ascending (the per-pixel order of the sum); with se every code is a pass of its own over the tiles, after
+    its gate sweeps (_se_global_gates).  No collective on prob / occur: that is the caller's.  Returns the split a: rank q took tile
+    rows [a[q], a[q+1])."""
+    from . import _lib
+    K = twin.plan.K
+    n_w = len(boxes) // n_rows
+    a = [q * n_rows // comm.world for q in range(comm.world + 1)]
+    mine = np.arange(a[comm.rank] * n_w, a[comm.rank + 1] * n_w)
+    st = twin._stream()
+    boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(twin.dev)
+    forward = twin.forward
+    if se is not None:
+        forward = lambda nb, T_, want_logits: twin.forward_staged(nb, T_, len(twin.plan.se), want_logits=want_logits)   # noqa: E731
+    codes = (0,) if G is None else G
+    for Gp in ([codes] if se is None else [(g,) for g in codes]):
+        if se is not None:
+            _se_global_gates(twin, crop, T, boxes, mine, map_index, hg * wg, comm, Gp[0])
+        for c0 in range(0, len(mine), twin.b_max):
+            sel = mine[c0:c0 + twin.b_max]
+            inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
+            box0 = boxes_dev.data_ptr() + int(sel[0]) * 6 * 4
+            for g in Gp:
+                crop(inst, g)
+                _, logits = forward(len(sel), T, want_logits=True)
+                if G is None:
+                    _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hg, wg, K, T, box0, len(sel), st)
+                else:
+                    _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hg, wg, K, T, box0,
+                              len(sel), int(g), st)
+    return a
 
 
 def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, comm=None, tile=None, return_sums=False, tta=None,
@@ -720,7 +823,14 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     grid, occur = |G|; labels the arg-max of that mean.  A flip swaps `before` and `after` on its axis and a transpose swaps the axes,
     so with any g != 0 the plan keeps the symmetric margin max(before, after) on both sides.
     scales (a list of distinct factors in [0.25, 4]; patches.check_scales): multi-scale test-time augmentation, with or
-    without tta -- see _predict_tile_dense_scales.
+    without tta.  For each scale s, in the order given: the map resampled to hs x ws (patches.scaled_size; bilinear, half-pixel centres)
+    is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) -- each tile cropped from the source map by one fused
+    gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its logits (drs_tile_place) or its per-g softmax
+    (drs_tile_place_dihedral) summed into a zeroed hs x ws map; under data parallelism that map is summed over the ranks (the same split
+    of tile rows as one scale); then its class probabilities are resampled back onto h x w and ADDED into acc (drs_resample_accumulate)
+    on every rank, and the scale's buffers go.  Labels: drs_stitch_finalize(acc, occur = len(scales)) on every rank, which holds the
+    whole acc: score maps are made beside them and nothing is gathered.  The tile count is the total over the scales.  One inference
+    twin, sized once for max T_s, runs every scale's tiles.
     se ("global"; nets with squeeze-and-excitation blocks only, which raise without it): every SE block scales by the
     sigmoid gate of the mean over ALL h x w pixels of the image -- the function the net computes when the whole image is one patch --
     instead of a patch's own mean (what the window path does, and what training saw: a different function, hence opt-in).  With n
@@ -728,16 +838,24 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
     sums its activated output over the cores in fp64 (_se_global_gates); the last sweep is the full forward with every gate.  The
     margin is the field with the SE layers as constants (Plan.gated_receptive_field).  The net is not equivariant (asymmetric SAME
     pads, unsymmetric filters), so the activation means of a flipped or rotated image are not those of the image: with tta every
-    code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale.
+    code g has gates of its own, from sweeps over the g-transformed tiles, before its full forwards; so has every scale, an image of
+    its own on its hs x ws grid.
     scores (opt-in; a tuple of kinds from patches.SCORE_KINDS; not with return_sums): the return value is followed by a dict
     {kind: uint8 device tensor [h, w]} of per-pixel score maps (drs_stitch_finalize_scores): of the logits on the plain
     path, of the mean probability vector with tta or scales.  Under data parallelism they are gathered as the labels are.
     temperature_beta (opt-in; with scores only): the maps are of softmax(beta u), u the averaged logits on the plain path and the log of
     the mean probability vector with tta or scales (drs_stitch_finalize_scores_t); the labels do not change."""
-    from . import _lib
-    comm = comm or NoComm()
     scores = _check_scores(scores, return_sums)
     beta = _check_temperature(temperature_beta, scores)
+    path = InferencePath(dense_tile=tile or 0, dense_tta=tta, dense_scales=scales, dense_se=se)
+    return _public(_dense(path, net, pool, map_index, batch_size, mean_full, std_full, comm or NoComm(), scores, beta, return_sums),
+                   return_sums, scores)
+
+
+def _dense(path, net, pool, map_index, batch_size, mean_full, std_full, comm, scores, beta, return_sums):
+    """predict_tile_dense's worker: (labels, tile count, score maps or None), or (sums, occur, tile count) with return_sums"""
+    from . import _lib
+    tile, se = path.dense_tile, path.dense_se
     if se is not None and se not in DENSE_SE_MODES:
         raise ValueError("se must be None or one of %s, not %r" % (list(DENSE_SE_MODES), se))
     if se is not None and not net.plan.se:
@@ -748,92 +866,37 @@ def predict_tile_dense(net, pool, map_index, batch_size, mean_full, std_full, co
                          "so there is no single-pass exact whole-tile inference; use predict_tile, or se=\"global\" for gates from the "
                          "whole image's mean" % net.plan.net_type)
     before, after = net.plan.receptive_field if se is None else net.plan.gated_receptive_field
-    G = None if tta is None else P.tta_group(tta)
+    G = None if path.dense_tta is None else P.tta_group(path.dense_tta)
     if G is not None and any(G):
         before = after = max(before, after)
-    if scales is not None:
-        return _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G,
-                                          P.check_scales(scales), before, after, se, scores, beta)
     h, w = pool.h[map_index], pool.w[map_index]
     K = net.plan.K
-    smaps = _score_buffers(scores, h * w, net.dev)
-    T = int(tile) if tile else min(h, w, DENSE_TILE)
-    oy, ys, ye = P.dense_axis(h, T, before, after)
-    boxes = P.dense_tiles(h, w, T, before, after)
-    n_w = len(boxes) // len(oy)
-    twin = dense_twin(net, T, batch_size)
     W, r = comm.world, comm.rank
-    a = [q * len(oy) // W for q in range(W + 1)]          # tile rows per rank: contiguous, as even as possible
-    mine = np.arange(a[r] * n_w, a[r + 1] * n_w)
-    prob = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
-    occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
-    st = twin._stream()
-    boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
-    forward = twin.forward
-    if se is not None:
-        forward = lambda nb, T_, want_logits: twin.forward_staged(nb, T_, len(twin.plan.se), want_logits=want_logits)   # noqa: E731
-    # one pass over the tiles runs every code of its group per batch; with se every code is a pass of its own, after its gate sweeps
-    for Gp in ([G] if se is None or G is None else [(g,) for g in G]):
-        if se is not None and Gp is None:
-            _se_global_gates(twin, lambda inst: P.crop_to_net(twin, pool, inst, T, mean_full, std_full), T, boxes, mine, map_index,
-                             h * w, comm)
-        elif se is not None:
-            _se_global_gates(twin, lambda inst: P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, Gp[0]), T, boxes, mine,
-                             map_index, h * w, comm, Gp[0])
-        for c0 in range(0, len(mine), twin.b_max):
-            sel = mine[c0:c0 + twin.b_max]
-            inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
-            if Gp is None:
-                P.crop_to_net(twin, pool, inst, T, mean_full, std_full)
-                _, logits = forward(len(sel), T, want_logits=True)
-                _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
-                          boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
-                continue
-            for g in Gp:        # ascending: the per-pixel order of the sum
-                P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, g)
-                _, logits = forward(len(sel), T, want_logits=True)
-                _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), h, w, K, T,
-                          boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
-    if return_sums:
-        if W > 1:
-            comm.all_reduce_sum(prob)
-            comm.all_reduce_sum(occur)
-        return prob, occur, len(boxes)
-    out = torch.zeros(h * w, dtype=torch.uint8, device=net.dev)
-    own0 = ys[a[r]] if a[r] < len(oy) else h
-    own1 = ys[a[r + 1]] if a[r + 1] < len(oy) else h
-    if own1 > own0:
-        _finalize(prob.data_ptr() + own0 * w * K * 4, occur.data_ptr() + own0 * w * 4, own1 - own0, w, K, G is not None, out, smaps,
-                  own0 * w, st, beta)
-    if W > 1:
-        comm.all_reduce_sum(out)    # every rank wrote only the rows its cores own: the sum is the gather of the label bands
-        for v in (smaps or {}).values():
-            comm.all_reduce_sum(v)
-    if smaps is not None:
-        return out.view(h, w), len(boxes), _score_views(smaps, h, w)
-    return out.view(h, w), len(boxes)
-
-
-def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_full, comm, tile, return_sums, G, scales, before, after,
-                               se=None, scores=None, temperature_beta=None):
-    """predict_tile_dense with scales.  For each scale s, in the order given: the map resampled to hs x ws
-    (patches.scaled_size; bilinear, half-pixel centres) is run through the dense plan of side T_s = min(hs, ws, tile or DENSE_TILE) --
-    each tile cropped from the source map by one fused gather (drs_crop_resampled, dihedral code g, 0 without tta), forwarded, and its
-    logits (drs_tile_place) or its per-g softmax (drs_tile_place_dihedral) summed into a zeroed hs x ws map; under data parallelism
-    that map is summed over the ranks (the same split of tile rows as one scale); then its class probabilities are resampled back onto
-    h x w and ADDED into acc (drs_resample_accumulate) on every rank, and the scale's buffers go.  Labels: drs_stitch_finalize(acc,
-    occur = len(scales)) on every rank.  Returns (labels, total tile count), or (acc, occur, total tile count) with return_sums.
-    One inference twin, sized once for max T_s, runs every scale's tiles.  With se (predict_tile_dense's) every scale is
-    an image of its own, and so is every code of tta: gates from sweeps over the scale's hs x ws grid (tiles transformed by the code),
-    before that code's full forwards.  scores, temperature_beta (predict_tile_dense's): every rank holds the whole acc, so every rank
-    makes the whole score maps beside the labels; nothing is gathered."""
-    from . import _lib
-    beta = _check_temperature(temperature_beta, scores)
-    h, w = pool.h[map_index], pool.w[map_index]
-    K = net.plan.K
-    smaps = _score_buffers(scores, h * w, net.dev)
+    if path.dense_scales is None:
+        T = int(tile) if tile else min(h, w, DENSE_TILE)
+        oy, ys, ye = P.dense_axis(h, T, before, after)
+        boxes = P.dense_tiles(h, w, T, before, after)
+        twin = dense_twin(net, T, batch_size)
+        prob = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
+        occur = torch.zeros(h * w, dtype=torch.int32, device=net.dev)
+        if G is None:
+            crop = lambda inst, g: P.crop_to_net(twin, pool, inst, T, mean_full, std_full)                      # noqa: E731
+        else:
+            crop = lambda inst, g: P.crop_dihedral_to_net(twin, pool, inst, T, mean_full, std_full, g)          # noqa: E731
+        a = _tile_pass(twin, T, boxes, len(oy), h, w, G, se, prob, occur, comm, crop, map_index)
+        if return_sums:
+            if W > 1:
+                comm.all_reduce_sum(prob)
+                comm.all_reduce_sum(occur)
+            return prob, occur, len(boxes)
+        # every rank finalizes only the rows its cores own: the sum all-reduce is the gather of the uint8 bands
+        own0 = ys[a[r]] if a[r] < len(oy) else h
+        own1 = ys[a[r + 1]] if a[r + 1] < len(oy) else h
+        labels, smaps = _labels_tail(net, prob, occur, 0, own0, own1 - own0, h, w, path.sums_are_prob, scores, beta, comm)
+        return labels, len(boxes), smaps
+    one_scale = path._replace(dense_scales=None)         # what a scale's own hs x ws map accumulates
     plans = []
-    for s in scales:
+    for s in P.check_scales(path.dense_scales):
         hs, ws = P.scaled_size(h, s), P.scaled_size(w, s)
         T = min(hs, ws, int(tile) if tile else DENSE_TILE)
         if T < max(hs, ws) and T <= before + after:
@@ -842,53 +905,25 @@ def _predict_tile_dense_scales(net, pool, map_index, batch_size, mean_full, std_
         n_rows = len(P.dense_axis(hs, T, before, after)[0])
         plans.append((hs, ws, T, n_rows, P.dense_tiles(hs, ws, T, before, after)))
     twin = dense_twin(net, max(p[2] for p in plans), batch_size)
-    W, r = comm.world, comm.rank
     st = twin._stream()
     acc = torch.zeros(h * w * K, dtype=torch.float32, device=net.dev)
-    n_tiles = 0
     for hs, ws, T, n_rows, boxes in plans:
-        n_w = len(boxes) // n_rows
-        a = [q * n_rows // W for q in range(W + 1)]          # tile rows per rank, as with one scale
-        mine = np.arange(a[r] * n_w, a[r + 1] * n_w)
         prob = torch.zeros(hs * ws * K, dtype=torch.float32, device=net.dev)
         occur = torch.zeros(hs * ws, dtype=torch.int32, device=net.dev)
-        boxes_dev = torch.from_numpy(boxes.astype(np.int32)).to(net.dev)
-        forward = twin.forward
-        if se is not None:
-            forward = lambda nb, T_, want_logits: twin.forward_staged(nb, T_, len(twin.plan.se), want_logits=want_logits)   # noqa: E731
-        codes = (0,) if G is None else G
-        # one pass runs every code per batch of tiles; with se every code is a pass of its own, after its gate sweeps
-        for Gp in ([codes] if se is None else [(g,) for g in codes]):
-            if se is not None:
-                _se_global_gates(twin, lambda inst: P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, Gp[0]), T,
-                                 boxes, mine, map_index, hs * ws, comm, Gp[0])
-            for c0 in range(0, len(mine), twin.b_max):
-                sel = mine[c0:c0 + twin.b_max]
-                inst = np.concatenate([np.full((len(sel), 1), map_index), boxes[sel, :2]], axis=1)
-                for g in Gp:        # ascending: the per-pixel order of the sum
-                    P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, g)
-                    _, logits = forward(len(sel), T, want_logits=True)
-                    if G is None:
-                        _lib.call("drs_tile_place", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
-                                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), st)
-                    else:
-                        _lib.call("drs_tile_place_dihedral", prob.data_ptr(), occur.data_ptr(), logits.data_ptr(), hs, ws, K, T,
-                                  boxes_dev.data_ptr() + int(sel[0]) * 6 * 4, len(sel), int(g), st)
+        crop = lambda inst, g, T=T, hs=hs, ws=ws: P.crop_resampled_to_net(twin, pool, inst, T, hs, ws, mean_full, std_full, g)  # noqa: E731
+        _tile_pass(twin, T, boxes, n_rows, hs, ws, G, se, prob, occur, comm, crop, map_index)
         if W > 1:
             comm.all_reduce_sum(prob)
             comm.all_reduce_sum(occur)
-        _lib.call("drs_resample_accumulate", prob.data_ptr(), occur.data_ptr(), hs, ws, K, 0 if G is None else 1, h, w, acc.data_ptr(),
-                  st)
-        del prob, occur, boxes_dev          # (stream-ordered: the next scale's buffers may reuse them)
-        n_tiles += len(boxes)
-    occur = torch.full((h * w,), len(scales), dtype=torch.int32, device=net.dev)
+        _lib.call("drs_resample_accumulate", prob.data_ptr(), occur.data_ptr(), hs, ws, K, 1 if one_scale.sums_are_prob else 0, h, w,
+                  acc.data_ptr(), st)
+        del prob, occur          # (stream-ordered: the next scale's buffers may reuse them)
+    n_tiles = sum(len(p[4]) for p in plans)
+    occur = torch.full((h * w,), len(plans), dtype=torch.int32, device=net.dev)
     if return_sums:
         return acc, occur, n_tiles
-    out = torch.empty(h * w, dtype=torch.uint8, device=net.dev)
-    _finalize(acc.data_ptr(), occur.data_ptr(), h, w, K, True, out, smaps, 0, st, beta)
-    if smaps is not None:
-        return out.view(h, w), n_tiles, _score_views(smaps, h, w)
-    return out.view(h, w), n_tiles
+    labels, smaps = _labels_tail(net, acc, occur, 0, 0, h, h, w, path.sums_are_prob, scores, beta)
+    return labels, n_tiles, smaps
 
 
 def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_type, num_scales):
@@ -905,34 +940,6 @@ def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_ty
         ind = np.where(values == crop)
         values, acc, occ = np.delete(values, ind), np.delete(acc, ind), np.delete(occ, ind)
     return chosen
-
-
-def _check_dense_tta(dense_tile, dense_tta):
-    if dense_tta is None:
-        return
-    if dense_tile is None:
-        raise ValueError("test-time augmentation needs overlap-tile inference (dense_tile): the sliding-window map depends on the "
-                         "patch size and has no exact dihedral form")
-    P.tta_group(dense_tta)
-
-
-def _check_dense_scales(dense_tile, dense_scales):
-    if dense_scales is None:
-        return
-    if dense_tile is None:
-        raise ValueError("multi-scale test-time augmentation needs overlap-tile inference (dense_tile): the sliding windows take "
-                         "their scales from the patch size (crop_sizes)")
-    P.check_scales(dense_scales)
-
-
-def _check_dense_se(dense_tile, dense_se):
-    if dense_se is None:
-        return
-    if dense_tile is None:
-        raise ValueError("whole-image squeeze-and-excitation gates need overlap-tile inference (dense_tile): a sliding window is "
-                         "gated by its own mean")
-    if dense_se not in DENSE_SE_MODES:
-        raise ValueError("dense_se must be one of %s, not %r" % (list(DENSE_SE_MODES), dense_se))
 
 
 def _calibration_str(cal):
@@ -956,11 +963,8 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
     float32 the kernels take."""
     from . import _lib
     comm = comm or NoComm()
-    _check_dense_tta(dense_tile, dense_tta)
-    _check_dense_scales(dense_tile, dense_scales)
-    _check_dense_se(dense_tile, dense_se)
-    if dense_tile is not None and crop_sizes:
-        raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
+    path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
+    path.check()
     if testing_labels is None and pool is None:
         raise ValueError("fit_temperature needs labelled maps")
     K = net.plan.K
@@ -971,16 +975,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
                          "exceed max_resident_bytes = %d" % (need, max_resident_bytes))
     kept = []
     for k in range(len(testing_data)):
-        if dense_tile is not None:
-            sums, occur, _ = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                                scales=dense_scales, se=dense_se, return_sums=True)
-            is_prob = dense_tta is not None or dense_scales is not None
-        elif crop_sizes:
-            sums, occur = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, return_sums=True)
-            is_prob = True
-        else:
-            sums, occur, _ = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, return_sums=True, flavour=flavour)
-            is_prob = False
+        sums, occur, is_prob = path.run(net, pool, k, batch_size, mean_full, std_full, comm, return_sums=True)
         n = pool.h[k] * pool.w[k]
         off = int(pool.lab_off[k].item())
         kept.append((sums, occur, pool.labels[off:off + n], n, 1 if is_prob else 0))
@@ -1020,9 +1015,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     (T = 1 / beta) and extra carries "temperature_beta".  Labels and reference-format lines do not change."""
     from . import _lib
     comm = comm or NoComm()
-    _check_dense_tta(dense_tile, dense_tta)
-    _check_dense_scales(dense_tile, dense_scales)
-    _check_dense_se(dense_tile, dense_se)
+    path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
+    path.check()
     beta = _check_temperature(temperature_beta, score_maps)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
@@ -1038,21 +1032,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     all_f1 = np.zeros(len(testing_data), dtype=np.float32)
     all_f1_per_class = np.zeros(K, dtype=np.float32)
     maps = []
-    if dense_tile is not None and crop_sizes:
-        raise ValueError("overlap-tile inference has one scale: its map does not depend on a patch size")
     for k in range(len(testing_data)):
-        if dense_tile is not None:
-            res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                     scales=dense_scales, se=dense_se, scores=kinds, temperature_beta=beta)
-            (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
-        elif crop_sizes:    # validate_test_multiscale (isprs:1347-1474): several sizes, softmax maps summed
-            res = predict_tile_multiscale(net, pool, k, crop_sizes, batch_size, mean_full, std_full, comm, scores=kinds,
-                                          temperature_beta=beta)
-            pred, smaps = (res, None) if kinds is None else res
-        else:
-            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, flavour=flavour, scores=kinds,
-                                temperature_beta=beta)
-            (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
+        pred, _, smaps = path.run(net, pool, k, batch_size, mean_full, std_full, comm, scores=kinds, beta=beta)
         h, w = pool.h[k], pool.w[k]
         conf = torch.zeros(K * K, dtype=torch.int32, device=net.dev)
         lab = pool.labels[int(pool.lab_off[k].item()):int(pool.lab_off[k].item()) + h * w]
@@ -1123,25 +1104,19 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     returns (label maps, [per map {kind: uint8 numpy [h, w]}]).  temperature_beta (opt-in; with score_maps only; an inverse
     temperature): the score files are of the calibrated probabilities; the label files do not change."""
     comm = comm or NoComm()
-    _check_dense_tta(dense_tile, dense_tta)
-    _check_dense_scales(dense_tile, dense_scales)
-    _check_dense_se(dense_tile, dense_se)
+    path = InferencePath(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+    path.check()
     beta = _check_temperature(temperature_beta, score_maps)
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
     score_list = []
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
-        crop_size = (select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=comm.rank == 0)
-                     if sized else int(values[0]))
+        path = path._replace(crop_size=(select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type,
+                                                               debug=comm.rank == 0) if sized else int(values[0])))
     pool = P.TilePool(testing_data, None, net.dev)
     maps = []
     for k in range(len(testing_data)):
-        if dense_tile is not None:
-            res = predict_tile_dense(net, pool, k, batch_size, mean_full, std_full, comm, tile=dense_tile, tta=dense_tta,
-                                     scales=dense_scales, se=dense_se, scores=kinds, temperature_beta=beta)
-        else:
-            res = predict_tile(net, pool, k, crop_size, batch_size, mean_full, std_full, comm, scores=kinds, temperature_beta=beta)
-        (pred, _), smaps = (res, None) if kinds is None else (res[:2], res[2])
+        pred, _, smaps = path.run(net, pool, k, batch_size, mean_full, std_full, comm, scores=kinds, beta=beta)
         maps.append(pred.cpu().numpy())
         if kinds is not None:
             score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})

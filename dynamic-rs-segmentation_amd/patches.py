@@ -521,6 +521,23 @@ class _Staging(object):
         return base + self.o_inst, base + self.o_rot, base + self.o_ron, base + self.o_non
 
 
+def _crop_setup(net, B, S, inst, mean, std, aug=None):
+    """What the three crop_*_to_net share: the size check, `inst` (int32 [B][3 or 4]) and the augmentation tables uploaded through the
+    net's pinned staging ring (_Staging.upload's four device addresses), and mean / std as three C doubles each (bands past the third are
+    not normalised; HOST pointers: copied into the kernel arguments).  Returns (addresses, mean3, std3, keep); keep holds the doubles
+    alive over the call."""
+    import ctypes as C
+    net._check(B, S)
+    stg = getattr(net, "_staging", None)
+    if stg is None:
+        stg = net._staging = _Staging(net.dev, net.b_max)
+    ptrs = stg.upload(inst, aug)
+    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
+    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
+    keep = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)
+    return ptrs, C.cast(keep[0], C.c_void_p), C.cast(keep[1], C.c_void_p), keep
+
+
 def crop_to_net(net, pool, instances, S, mean, std, aug=None, void_label=-1, quantize_f16=False):
     """dynamically_create_patches + normalize_images (isprs:1742-1745 / 1579-1583) fused on the device:
     fills net's conv1 slab, net.labels and net.acc_mask for `instances` rows (map, x, y[, rot]).
@@ -528,33 +545,41 @@ def crop_to_net(net, pool, instances, S, mean, std, aug=None, void_label=-1, qua
     array (coffee:1290): value, difference and quotient are each rounded to float16; NumPy >= 2 evaluates the difference and the
     quotient in the type of the mean / std scalars when that is wider: float32 for coffee's own statistics (np.mean / np.std of
     float32 patches, coffee:78-79), float64 when `mean` arrives as float64 (drs_crop_normalize modes 1 / 2)."""
-    import ctypes as C
     B = len(instances)
-    net._check(B, S)
     inst = np.zeros((B, 4), dtype=np.int32)
     inst[:, :3] = _shift_inside(instances, pool, S)
     if aug is not None:
         inst[:, 3] = aug.flip
-    stg = getattr(net, "_staging", None)
-    if stg is None:
-        stg = net._staging = _Staging(net.dev, net.b_max)
-    p_inst, p_rot, p_ron, p_non = stg.upload(inst, aug)
+    (p_inst, p_rot, p_ron, p_non), m3, s3, keep = _crop_setup(net, B, S, inst, mean, std, aug)
     noise = None
     if aug is not None and aug.noise is not None:
         noise = torch.from_numpy(aug.noise).to(net.dev)          # reference-exact host noise (tests / parity runs)
-    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
-    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
-    m3c, s3c = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)       # HOST pointers: copied into the kernel arguments
     slab, P, ld = net.input_slab()
     _lib.call("drs_crop_normalize", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.labels.data_ptr(),
               pool.tile_off.data_ptr(), pool.lab_off.data_ptr(), pool.tile_h.data_ptr(), pool.tile_w.data_ptr(), pool.C,
               p_inst, p_rot if aug is not None else None, p_ron if aug is not None else None,
               None if noise is None else noise.data_ptr(), p_non if aug is not None else None,
-              aug.seed if aug is not None else 0, aug.index0 if aug is not None else 0, C.cast(m3c, C.c_void_p), C.cast(s3c, C.c_void_p), B, S, P, ld,
+              aug.seed if aug is not None else 0, aug.index0 if aug is not None else 0, m3, s3, B, S, P, ld,
               slab.data_ptr(), net.labels.data_ptr(), net.acc_mask.data_ptr(), int(void_label),
               (2 if getattr(mean, "dtype", None) == np.float64 else 1) if quantize_f16 else 0, net._stream())
     net._keep = noise                                            # alive until the stream has consumed it
     return inst[:, 1:3]
+
+
+def _crop_tiles_to_net(net, pool, instances, T, mean, std, g, grid=None):
+    """crop_dihedral_to_net (grid None: drs_crop_dihedral) and crop_resampled_to_net (grid = (hs, ws): drs_crop_resampled), which differ
+    in that one call: the tiles' (map, row, col) rows as int32 through the staging ring, no shift-back, labels, mask or augmentation"""
+    B = len(instances)
+    inst = np.ascontiguousarray(np.asarray(instances, dtype=np.int64)[:, :3].astype(np.int32))
+    ptrs, m3, s3, keep = _crop_setup(net, B, T, inst, mean, std)
+    slab, P, ld = net.input_slab()
+    head = (pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(), pool.tile_w.data_ptr(),
+            len(pool.h), pool.C, ptrs[0])
+    tail = (int(g), m3, s3, B, T, P, ld, slab.data_ptr(), net._stream())
+    if grid is None:
+        _lib.call("drs_crop_dihedral", *head, *tail)
+    else:
+        _lib.call("drs_crop_resampled", *head, int(grid[0]), int(grid[1]), *tail)
 
 
 def crop_dihedral_to_net(net, pool, instances, T, mean, std, g):
@@ -562,21 +587,7 @@ def crop_dihedral_to_net(net, pool, instances, T, mean, std, g):
     tiles at `instances` rows (map, row, col), each transformed by the dihedral code g (dihedral_apply) and normalised as crop_to_net
     normalises (drs_crop_dihedral; no augmentation, labels or mask).  No shift-back: a tile that does not lie inside its map is caught
     on the device and leaves a zero slab."""
-    import ctypes as C
-    B = len(instances)
-    net._check(B, T)
-    inst = np.ascontiguousarray(np.asarray(instances, dtype=np.int64)[:, :3].astype(np.int32))
-    stg = getattr(net, "_staging", None)
-    if stg is None:
-        stg = net._staging = _Staging(net.dev, net.b_max)
-    p_inst = stg.upload(inst, None)[0]
-    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
-    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
-    m3c, s3c = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)       # HOST pointers: copied into the kernel arguments
-    slab, P, ld = net.input_slab()
-    _lib.call("drs_crop_dihedral", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(),
-              pool.tile_w.data_ptr(), len(pool.h), pool.C, p_inst, int(g), C.cast(m3c, C.c_void_p), C.cast(s3c, C.c_void_p), B, T, P,
-              ld, slab.data_ptr(), net._stream())
+    _crop_tiles_to_net(net, pool, instances, T, mean, std, g)
 
 
 def crop_resampled_to_net(net, pool, instances, T, hs, ws, mean, std, g):
@@ -584,21 +595,7 @@ def crop_resampled_to_net(net, pool, instances, T, hs, ws, mean, std, g):
     tiles at `instances` rows (map, row, col) of the map bilinearly resampled to hs x ws (row / col on that grid), each transformed by
     the dihedral code g and normalised as crop_to_net normalises (drs_crop_resampled; no resized image is made).  A tile that does not
     lie inside the hs x ws grid is caught on the device and leaves a zero slab."""
-    import ctypes as C
-    B = len(instances)
-    net._check(B, T)
-    inst = np.ascontiguousarray(np.asarray(instances, dtype=np.int64)[:, :3].astype(np.int32))
-    stg = getattr(net, "_staging", None)
-    if stg is None:
-        stg = net._staging = _Staging(net.dev, net.b_max)
-    p_inst = stg.upload(inst, None)[0]
-    m = list(np.asarray(mean, dtype=np.float64)[:3]) + [0.0] * max(0, 3 - len(mean))
-    sd = list(np.asarray(std, dtype=np.float64)[:3]) + [1.0] * max(0, 3 - len(std))
-    m3c, s3c = (C.c_double * 3)(*m), (C.c_double * 3)(*sd)       # HOST pointers: copied into the kernel arguments
-    slab, P, ld = net.input_slab()
-    _lib.call("drs_crop_resampled", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.tile_off.data_ptr(), pool.tile_h.data_ptr(),
-              pool.tile_w.data_ptr(), len(pool.h), pool.C, p_inst, int(hs), int(ws), int(g), C.cast(m3c, C.c_void_p),
-              C.cast(s3c, C.c_void_p), B, T, P, ld, slab.data_ptr(), net._stream())
+    _crop_tiles_to_net(net, pool, instances, T, mean, std, g, grid=(hs, ws))
 
 
 def pack_feed(net, batch_x, batch_y, crop_size, mask=None, acc_mask=None):

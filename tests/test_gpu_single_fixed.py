@@ -216,8 +216,8 @@ def test_single_fixed_through_the_isprs_command_line(tmp_path, monkeypatch, caps
     common = ["isprs_dilated_random.py", "synthetic:96x110x3/vaihingen/", out]
     tail = ["a", "c", "0.01", "0.005", "16", "4", "25", "10", "dilated_icpr_original", "single_fixed", "25", "acc"]
     sizes = []
-    real = loops.predict_tile
-    monkeypatch.setattr(loops, "predict_tile", lambda net, pool, k, crop, *a, **kw: (sizes.append(crop), real(net, pool, k, crop, *a, **kw))[1])
+    real = loops._window          # the window path's worker, which validate_test / generate_final_maps reach through InferencePath.run
+    monkeypatch.setattr(loops, "_window", lambda path, *a, **kw: (sizes.append(path.crop_size), real(path, *a, **kw))[1])
     random.seed(2)
     np.random.seed(2)
     net = cli.main(common + ["none"] + tail + ["training"], device=DEV)
