@@ -69,6 +69,8 @@ SIGNATURES = {
     "drs_confusion": (_i, [_p, _p, _p, _sz, _i, _i, _p, _p]),
     "drs_crop_normalize": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _u64, _i, _p, _p, _i, _i, _i, _i, _p, _p,
                                 _p, _i, _i, _p]),
+    "drs_crop_normalize_scaled": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _u64, _i, _p, _p, _i, _i, _i, _i,
+                                       _p, _p, _p, _i, _i, _p]),
     "drs_stitch_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "drs_stitch_finalize": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_stitch_finalize_scores": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),

@@ -24,6 +24,9 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
     of the focal loss, 0 or in (0, 8] (loops.train's focal_gamma)
+  + optionally, anywhere, in all three flavours, `--scale-jitter=lo,hi` (training): every training patch is resampled at a scale
+    drawn log-uniformly from [lo, hi], 0.25 <= lo <= hi <= 4 (loops.train's scale_jitter); validation and inference
+    stay at scale 1
 coffee / contest flavours (coffee_dilated_random.py:1106-1150, contest_dilated_random.py:1229-1271, 14 [+ operation]):
     path_train path_test output_path currentModelPath lr wd batch niter ref_crop ref_stride net_type distribution_type
     probValues update_type [operation]
@@ -200,6 +203,17 @@ def parse_focal_gamma(argv):
         P.parse_focal_gamma, a, v, "%s=G (one number, 0 or finite in (0, %g])" % (FOCAL_GAMMA_FLAG, P.MAX_FOCAL_GAMMA)))
 
 
+SCALE_JITTER_FLAG = "--scale-jitter"
+
+
+def parse_scale_jitter(argv):
+    """all flavours: the optional `--scale-jitter=lo,hi` (anywhere in argv; training).  Returns (argv without the flag, (lo, hi) as
+    floats), or (argv unchanged, None) without it.  A bare flag, a value that is not two finite numbers lo <= hi inside [0.25, 4], or
+    the flag given twice, raises ValueError."""
+    return _take_flag(argv, SCALE_JITTER_FLAG, lambda a, v: _or_expected(
+        P.parse_scale_jitter, a, v, "%s=lo,hi (two numbers, %g <= lo <= hi <= %g)" % (SCALE_JITTER_FLAG, P.SCALE_MIN, P.SCALE_MAX)))
+
+
 def print_params(list_params, argv):
     print("+" * 97)
     for i in range(1, len(argv)):
@@ -263,6 +277,7 @@ def main(argv=None, device=None, comm=None):
         argv, temperature = parse_temperature(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
     if dense_tta is not None and dense_tile is None:
@@ -291,6 +306,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the training process only")
+    if scale_jitter is not None and argv[16] != "training":
+        sys.exit(SCALE_JITTER_FLAG + " applies to the training process only")
     if comm.rank == 0:
         print_params(ISPRS_PARAMS, argv)
     (input_path, output_path, former_model_path, tr, te, lr, wd, bs, niter, ref_crop, ref_stride, net_type,
@@ -340,7 +357,7 @@ def main(argv=None, device=None, comm=None):
                            testing_instances, lr_initial, batch_size, niter, weight_decay, mean_full, std_full, update_type,
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
-                           class_weights=class_weights, focal_gamma=focal_gamma)
+                           class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -407,6 +424,7 @@ def main_coffee(argv=None, device=None, comm=None):
     try:
         argv, class_weights = parse_class_weights(argv, 2)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
     if len(argv) < len(COFFEE_PARAMS) + 1:
@@ -424,7 +442,8 @@ def main_coffee(argv=None, device=None, comm=None):
     return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
-                    quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma)     # coffee:293: training patches pass through float16
+                    quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma,     # coffee:293: training patches pass through float16
+                    scale_jitter=scale_jitter)
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -435,6 +454,7 @@ def main_contest(argv=None, device=None, comm=None):
     try:
         argv, class_weights = parse_class_weights(argv, 7)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
     if len(argv) < len(CONTEST_PARAMS) + 1:
@@ -444,6 +464,8 @@ def main_contest(argv=None, device=None, comm=None):
     path, output_path, current_model, lr, wd, bs, niter, crop, stride, net_type, dist, pv, update_type, operation = argv[1:15]
     if focal_gamma is not None and operation != "train":
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the train operation only")
+    if scale_jitter is not None and operation != "train":
+        sys.exit(SCALE_JITTER_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
     resolve(net_type)
     acc, occ, chosen, probs = init_size_scores(dist, values, occur_init=1)            # contest:1275
@@ -461,7 +483,7 @@ def main_contest(argv=None, device=None, comm=None):
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
                         void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
-                        focal_gamma=focal_gamma)
+                        focal_gamma=focal_gamma, scale_jitter=scale_jitter)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

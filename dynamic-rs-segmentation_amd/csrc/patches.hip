@@ -7,7 +7,7 @@
 //   overlap-add of logits      :1261-1284 / :1925-1949, arg-max of the average
 //   (and, beside the reference's windows, the opt-in overlap-tile inference: exact cores of whole-net tiles, drs_tile_place;
 //    its dihedral test-time augmentation: drs_crop_dihedral, drs_tile_place_dihedral; its multi-scale test-time augmentation:
-//    drs_crop_resampled, drs_resample_accumulate)
+//    drs_crop_resampled, drs_resample_accumulate; and, for training, the crop with scale jitter: drs_crop_normalize_scaled)
 //
 // The crop writes straight into the zero-haloed, channel-padded input slab of conv1, so no separate pad/normalise
 // pass exists.  Arithmetic on pixel values is fp64 (the reference normalises float64 patches, then feeds float32),
@@ -106,6 +106,135 @@ __global__ void crop_kernel(const CropArgs a) {
     const bool noisy = a.noise_on && a.noise_on[b];
     for (int c = 0; c < a.C; ++c) {
       double e = valid ? (double)src[c] : 0.0;      // fp64 until the single rounding on the store
+      if (noisy) {
+        const size_t ne = (((size_t)b * a.S + fi) * a.S + fj) * a.C + c;   // noise is indexed before the flip
+        const size_t ng = ne + (size_t)a.b0 * a.S * a.S * a.C;             // ... and by the patch's place in the GLOBAL batch on the device path
+        if (a.noise) e = e + a.noise[ne];
+        else {
+          unsigned r[4];
+          philox(a.seed, (unsigned long long)ng, r);
+          e = e + 0.01 * normal_from(r[0], r[1]);
+        }
+      }
+      if (a.quantize_f16) {
+        // coffee:293 casts the patches to float16, coffee:67-74 normalises in that array.  NumPy >= 2 (NEP 50) evaluates
+        // float16-array (op) numpy-scalar in the SCALAR's type when that is wider, and the assignment rounds to float16:
+        // 1 = float32 scalars (what coffee's own compute_image_mean gives: np.mean / np.std of float32 patches), 2 = float64 scalars
+        _Float16 q = (_Float16)(float)e;
+        if (c < 3) {
+          if (a.quantize_f16 == 2) {
+            q = (_Float16)((double)q - a.mean[c]);
+            q = (_Float16)((double)q / a.stdv[c]);
+          } else {
+            q = (_Float16)((float)q - (float)a.mean[c]);
+            q = (_Float16)((float)q / (float)a.stdv[c]);
+          }
+        }
+        v[c] = (float)q;
+        continue;
+      }
+      if (c < 3) e = (e - a.mean[c]) / a.stdv[c];
+      v[c] = (float)e;
+    }
+    if (a.out_lab) a.out_lab[opix] = lab;
+    if (a.out_mask) a.out_mask[opix] = (valid && (int)lab != a.void_label) ? 1 : 0;
+  }
+  // one pixel = ld floats: the real channels, then zero padding up to the conv1 K-step
+  for (int c4 = 0; c4 < a.ld; c4 += 4) {
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = (c4 + k) < 8 ? v[(c4 + k) & 7] : 0.f;
+    *reinterpret_cast<f32x4*>(dst + c4) = o;
+  }
+}
+
+// One axis of the scale-jitter crop (include/drs.h, drs_crop_normalize_scaled): patch pixel p of a side-S patch whose footprint has
+// the centre c (pixel-edge coordinates) and `step` source pixels per patch pixel, on a map axis of n pixels.  u is the pixel centre's
+// position; it is valid iff 0 <= u <= n (a NaN fails both); the bilinear neighbours are those of D (resample_axis), the label's
+// source pixel the one that contains u.  Every product and sum is rounded on its own (fp contract(off)).
+__device__ __forceinline__ bool jitter_axis(int p, int S, double c, double step, int n, int& i0, int& i1, double& l, int& il) {
+  const double t = ((double)p + 0.5) - 0.5 * (double)S;
+  const double u = c + t * step;
+  if (!(u >= 0.0 && u <= (double)n)) return false;
+  double src = u - 0.5;
+  if (src < 0.0) src = 0.0;
+  if (src > (double)(n - 1)) src = (double)(n - 1);
+  i0 = (int)src;
+  i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+  l = src - (double)i0;
+  il = (int)u;
+  if (il > n - 1) il = n - 1;
+  return true;
+}
+
+// drs_crop_normalize_scaled: crop_kernel for training with scale jitter.  A sibling with a body of its own, not a
+// template parameter of crop_kernel: crop_kernel is held to the code it compiled to before this kernel existed (a shared body, even
+// with the new branches compiled out, came out scheduled differently), so its text above is left alone and what the two share is
+// restated here line by line.  What differs: the patch pixel (si, sj) the rotation picked is resampled from the footprint
+// geo[b] = (step, cy, cx) instead of copied from (px + si, py + sj); geo and the map index are device data and are checked here: a bad
+// row leaves a zero patch (no noise) with label 0 and mask 0.  Same grid: one thread per slab pixel in store order; four gathered
+// source pixels per patch pixel.
+template <typename T>
+__global__ void crop_scaled_kernel(const CropArgs a, const double* __restrict__ geo, int n_maps) {
+  const int Sp = a.S + 2 * a.P;
+  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (xx >= Sp) return;
+  const int b = blockIdx.y / Sp, yy = blockIdx.y - b * Sp;
+  float* dst = a.out + ((size_t)(b * Sp + yy) * Sp + xx) * a.ld;
+  const int i = yy - a.P, j = xx - a.P;
+  const bool inside = i >= 0 && i < a.S && j >= 0 && j < a.S;
+  float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (inside) {
+    const int map = a.inst[4 * b], flip = a.inst[4 * b + 3];     // (row, col are not read: the centre is in geo)
+    // undo the flip (applied last by the reference), then the rotation (applied first)
+    const int fi = flip == 1 ? a.S - 1 - i : i, fj = flip == 2 ? a.S - 1 - j : j;
+    int si = fi, sj = fj;
+    bool valid = true;
+    if (a.rot_on && a.rot_on[b]) {
+      const double* m = a.rot + 6 * b;
+      // scipy.ndimage geometric transform, order 0: in = M . out + offset (no FMA contraction), nearest = floor(c + 0.5)
+      // (plain operators under this file's `fp contract(off)`: every product and every sum rounded on its own, as in ndimage's C)
+      const double p00 = (double)fi * m[0], p01 = (double)fj * m[1], p10 = (double)fi * m[2], p11 = (double)fj * m[3];
+      double c0 = 0.0 + p00;
+      c0 = c0 + p01;
+      c0 = c0 + m[4];
+      double c1 = 0.0 + p10;
+      c1 = c1 + p11;
+      c1 = c1 + m[5];
+      valid = !(c0 < 0.0 || c0 > (double)(a.S - 1) || c1 < 0.0 || c1 > (double)(a.S - 1));
+      si = (int)floor(c0 + 0.5);
+      sj = (int)floor(c1 + 0.5);
+    }
+    const size_t opix = ((size_t)b * a.S + i) * a.S + j;
+    unsigned char lab = 0;
+    const T* src = nullptr;
+    const T* s01 = nullptr; const T* s10 = nullptr; const T* s11 = nullptr;      // the other three neighbours (src is v00)
+    double ly = 0.0, lx = 0.0;
+    const double step = geo[3 * b], cy = geo[3 * b + 1], cx = geo[3 * b + 2];
+    // the device-side check of geo and the map index (a NaN fails every comparison)
+    const bool bad = !(step > 0.0 && step <= DBL_MAX && fabs(cy) <= DBL_MAX && fabs(cx) <= DBL_MAX) || map < 0 || map >= n_maps;
+    if (bad) valid = false;
+    if (valid) {
+      const int H = a.tile_h[map], W = a.tile_w[map];
+      int y0, y1, x0, x1, yl, xl;
+      valid = jitter_axis(si, a.S, cy, step, H, y0, y1, ly, yl);
+      valid = jitter_axis(sj, a.S, cx, step, W, x0, x1, lx, xl) && valid;
+      if (valid) {
+        const T* base = reinterpret_cast<const T*>(a.tiles) + a.tile_off[map];
+        src = base + ((size_t)y0 * W + x0) * a.C;
+        s01 = base + ((size_t)y0 * W + x1) * a.C;
+        s10 = base + ((size_t)y1 * W + x0) * a.C;
+        s11 = base + ((size_t)y1 * W + x1) * a.C;
+        lab = a.labels[a.lab_off[map] + (size_t)yl * W + xl];
+      }
+    }
+    // rotated-in fill and the footprint's overhang are value 0 (+ noise), label 0, mask 0; a bad row is 0 without noise
+    const bool noisy = a.noise_on && a.noise_on[b];
+    for (int c = 0; c < a.C && !bad; ++c) {
+      double e = 0.0;                               // fp64 until the single rounding on the store
+      if (valid)                                    // D's expression (crop_tiles_kernel), in its order
+        e = (1.0 - ly) * ((1.0 - lx) * (double)src[c] + lx * (double)s01[c]) +
+            ly * ((1.0 - lx) * (double)s10[c] + lx * (double)s11[c]);
       if (noisy) {
         const size_t ne = (((size_t)b * a.S + fi) * a.S + fj) * a.C + c;   // noise is indexed before the flip
         const size_t ng = ne + (size_t)a.b0 * a.S * a.S * a.C;             // ... and by the patch's place in the GLOBAL batch on the device path
@@ -636,6 +765,27 @@ int drs_crop_normalize(const void* tiles, int tiles_are_f64, const unsigned char
   dim3 grid((Sp + 63) / 64, B * Sp);
   if (tiles_are_f64) DRS_LAUNCH(crop_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a);
   else DRS_LAUNCH(crop_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_crop_normalize_scaled(const void* tiles, int tiles_are_f64, const unsigned char* labels, const long long* tile_off,
+                              const long long* lab_off, const int* tile_h, const int* tile_w, int n_maps, int C, const int* inst,
+                              const double* geo, const double* rot, const unsigned char* rot_on, const double* noise,
+                              const unsigned char* noise_on, unsigned long long seed, int noise_index0, const double* mean3,
+                              const double* std3, int B, int S, int P, int ld, float* out, unsigned char* out_lab,
+                              unsigned char* out_mask, int void_label, int quantize_f16, void* stream) {
+  if (!tiles || !labels || !tile_off || !lab_off || !tile_h || !tile_w || !inst || !geo || !out || !mean3 || !std3) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || B < 1 || S < 1 || P < 0) return DRS_ERR_ARG;
+  const int Sp = S + 2 * P;
+  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
+  CropArgs a;
+  a.tiles = tiles; a.labels = labels; a.tile_off = tile_off; a.lab_off = lab_off; a.tile_h = tile_h; a.tile_w = tile_w; a.C = C;
+  a.inst = inst; a.rot = rot; a.rot_on = rot ? rot_on : nullptr; a.noise = noise; a.noise_on = noise_on; a.seed = seed; a.b0 = noise_index0; a.void_label = void_label; a.quantize_f16 = quantize_f16;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+  a.out = out; a.S = S; a.P = P; a.ld = ld; a.out_lab = out_lab; a.out_mask = out_mask;
+  dim3 grid((Sp + 63) / 64, B * Sp);
+  if (tiles_are_f64) DRS_LAUNCH(crop_scaled_kernel<double>, grid, dim3(64), 0, (hipStream_t)stream, a, geo, n_maps);
+  else DRS_LAUNCH(crop_scaled_kernel<float>, grid, dim3(64), 0, (hipStream_t)stream, a, geo, n_maps);
   return DRS_LAUNCH_CHECK();
 }
 

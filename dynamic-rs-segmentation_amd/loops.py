@@ -227,12 +227,33 @@ def sync_rng(comm):
     draw, batch indices, augmentation).  Nothing guarantees that by itself -- the reference never seeds, and a rank that loads
     a cache file skips the draws the rank that built it made -- so at every point where the ranks may have drifted (start of a
     loop, after a cache was built or loaded) rank 0 draws two seeds from ITS streams and every rank re-seeds from them.
-    A single process is untouched (the reference's stream order)."""
+    A single process is untouched (the reference's stream order).
+    Returns the pair of seeds: the run seed of whatever keeps a generator of its own (the scale jitter of the training crop,
+    patches.draw_scales).  A single process returns the pair rank 0 would have drawn, taken from COPIES of the two streams, so that the
+    streams themselves stay where they are."""
     if not getattr(comm, "sync_rng", False):
-        return
+        r = random.Random()
+        r.setstate(random.getstate())
+        n = np.random.RandomState()
+        n.set_state(np.random.get_state())
+        return r.getrandbits(31), int(n.randint(0, 2 ** 31 - 1))
     seeds = comm.broadcast_object((random.getrandbits(31), int(np.random.randint(0, 2 ** 31 - 1))))
     random.seed(seeds[0])
     np.random.seed(seeds[1])
+    return int(seeds[0]), int(seeds[1])
+
+
+def setup_scale_jitter(scale_jitter, seeds, comm, say):
+    """The scale jitter of a training run (train's `scale_jitter`; patches.check_scale_jitter) and the run seed of its draws
+    (patches.jitter_run_seed of sync_rng's pair): every rank must hold the same ones, asserted once over the ranks.  One log line names
+    the range.  Returns ((lo, hi), run seed)."""
+    lo, hi = P.check_scale_jitter(scale_jitter)
+    run_seed = P.jitter_run_seed(seeds)
+    comm.agree([int(np.asarray(lo, dtype=np.float64).view(np.uint64)), int(np.asarray(hi, dtype=np.float64).view(np.uint64)), run_seed],
+               "scale jitter")
+    say("Scale jitter: every training patch resampled at a scale drawn log-uniformly from [" + "{:.6g}".format(lo) + ", " +
+        "{:.6g}".format(hi) + "] (validation and inference at scale 1)")
+    return (lo, hi), run_seed
 
 
 def rank0_call(comm, fn, what):
@@ -292,7 +313,8 @@ def train(training_data, training_labels, training_class_distribution, training_
           mean_full, std_full, update_type, distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values,
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
-          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None):
+          loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
+          scale_jitter=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -302,7 +324,11 @@ def train(training_data, training_labels, training_class_distribution, training_
     (setup_focal_gamma, DilatedNet.set_focal_gamma; with or without class_weights).  The loss this loop prints, and that feeds the
     size scores with update_type="loss", is then the MODULATED one (inv_n * sum wc[y] (1 - p_t)^gamma CE + the L2 term); accuracies,
     confusion matrices and validation are not modulated.  Given here, it replaces a gamma restored from a checkpoint's side file;
-    None keeps that."""
+    None keeps that.
+    scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
+    log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
+    their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
+    validation never jitters.  It is not net state: a resumed run is given it again."""
     comm = comm or NoComm()
     say = (lambda *a: print(*a)) if comm.rank == 0 else (lambda *a: None)
     say(BatchColors.OKGREEN + "TRAINING" + BatchColors.ENDC)
@@ -311,7 +337,8 @@ def train(training_data, training_labels, training_class_distribution, training_
 
     if batch_size % comm.world:
         raise ValueError("batch_size must be divisible by the number of ranks")
-    sync_rng(comm)
+    seeds = sync_rng(comm)       # (the pair from the loop's START is the run seed of the scale jitter: a resumed run, seeded alike, gets
+    #                              the same one whether or not the cache below exists by then)
     selected_training_instances = SP.select_super_batch_instances(training_class_distribution, training_rotation_distribution,
                                                                   batch_size, super_batch=SUPER_BATCH)
     total_length = len(selected_training_instances)
@@ -345,6 +372,9 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_class_weights(net, train_pool, num_classes, class_weights, comm, say)
     if focal_gamma is not None:
         setup_focal_gamma(net, focal_gamma, comm, say)
+    run_seed = None
+    if scale_jitter is not None:
+        scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)
 
     it = 0
     epoch_mean = 0.0
@@ -379,11 +409,11 @@ def train(training_data, training_labels, training_class_distribution, training_
         if step - current_iter < 3:                  # the ranks must move in lock step: same size, same instances
             comm.agree((cur_patch_size, batch[0], batch[-1], it), "patch size / batch indices at step %d" % step)
         rows = selected_training_instances[batch]
-        aug = P.draw_augmentation(rows, cur_patch_size, channels, noise=noise)
-        mine = P.Augmentation(b_local)
-        mine.rot_on, mine.rot, mine.noise_on, mine.flip = aug.rot_on[sl], aug.rot[sl], aug.noise_on[sl], aug.flip[sl]
-        mine.noise = aug.noise[sl] if aug.noise is not None else None
-        mine.seed, mine.index0 = aug.seed, sl.start      # device noise is keyed by the patch's place in the global batch
+        aug = P.draw_augmentation(rows, cur_patch_size, channels, noise=noise, scale_jitter=scale_jitter,
+                                  jitter_key=None if scale_jitter is None else (run_seed, step))
+        mine = aug.shard(sl)                             # device noise is keyed by the patch's place in the global batch
+        if mine.scale is not None:
+            mine.geo = P.scale_geometry(rows[sl], train_pool, cur_patch_size, mine.scale)
         P.crop_to_net(net, train_pool, rows[sl], cur_patch_size, mean_full, std_full, mine)
         out = net.train_step(b_local, cur_patch_size, lr_initial)
         pending.append(_Pending(net, out, cur_size_int, step, epoch_counter))

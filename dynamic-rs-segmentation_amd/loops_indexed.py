@@ -85,15 +85,18 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
           current_model, lr_initial, weight_decay, batch_size, niter, net_type, distribution_type, update_type, patch_acc_loss,
           patch_occur, patch_chosen_values, probs, values, *, num_classes, void_label=-1, side_names=None, device="cuda:0",
           comm=None, display_step=50, quiet_sizes=False, quantize_f16=False, flavour="isprs", class_weights=None,
-          focal_gamma=None):
+          focal_gamma=None, scale_jitter=None):
     """class_weights (opt-in; None = the reference's loss): "balanced" | "median" | K numbers, as loops.train takes them; the counts of
     the recipes leave the void label out.  The printed loss and the loss-based size scores are then the weighted ones.
     focal_gamma (opt-in; None or 0 = today's run): the focusing parameter of the focal loss, as loops.train takes it; the printed loss
-    and the loss-based size scores are then the modulated ones."""
+    and the loss-based size scores are then the modulated ones.
+    scale_jitter (opt-in; None = today's run): (lo, hi), as loops.train takes it -- every training patch resampled at a scale drawn
+    log-uniformly from [lo, hi] by a generator of its own (patches.draw_scales), before the flip by index, coffee's float16 pass and
+    contest's void mask; the test pass never jitters."""
     comm = comm or NoComm()
     if batch_size % comm.world:
         raise ValueError("batch_size must be divisible by the number of ranks")
-    loops.sync_rng(comm)                 # every rank walks the same permutation and draws the same sizes
+    seeds = loops.sync_rng(comm)         # every rank walks the same permutation and draws the same sizes
     say = (lambda *a: print(*a)) if comm.rank == 0 else (lambda *a: None)
     side = side_names or ("patch_acc_loss_step_", "patch_occur_step_", "patch_chosen_values_step_")
     channels = training_data[0].shape[-1]
@@ -124,6 +127,9 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
         loops.setup_class_weights(net, train_pool, num_classes, class_weights, comm, say, void_label if void_label >= 0 else None)
     if focal_gamma is not None:
         loops.setup_focal_gamma(net, focal_gamma, comm, say)
+    run_seed = None
+    if scale_jitter is not None:
+        scale_jitter, run_seed = loops.setup_scale_jitter(scale_jitter, seeds, comm, say)
 
     def save(step):
         if comm.rank == 0:
@@ -155,6 +161,9 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
         rows = dist_arr[batch % N]
         aug = P.Augmentation(b_local)
         aug.flip = flip[sl].astype(np.int32)
+        if scale_jitter is not None:             # one scale per patch of the GLOBAL batch, this rank's slice of them
+            aug.scale = P.draw_scales(batch_size, scale_jitter, (run_seed, step))[sl]
+            aug.geo = P.scale_geometry(rows[sl], train_pool, cur_size, aug.scale)
         P.crop_to_net(net, train_pool, rows[sl], cur_size, mean_full, std_full, aug, void_label=void_label, quantize_f16=quantize_f16)
         M = b_local * cur_size * cur_size
         if void_label >= 0:                      # masked mean: the loss averages over the unmasked pixels of the global batch

@@ -8,10 +8,12 @@ stays on the host (it is scalar work); every per-pixel operation -- crop,
 rotation, noise, flip, normalisation of bands 0..2, zero halo and band padding for conv1 -- happens
 in one HIP kernel (drs_crop_normalize) that writes the conv1 input slab directly (and, for the test-time
 augmentation of overlap-tile inference, the dihedral symmetries of whole tiles: drs_crop_dihedral, and tiles of
-the bilinearly resampled image: drs_crop_resampled).
+the bilinearly resampled image: drs_crop_resampled; and, for training with scale jitter, the crop that resamples every patch
+at a scale of its own: drs_crop_normalize_scaled).
 
 RNG: like the reference, draws come from the global `random` / `numpy.random` streams in the
-reference's call order, so seeding both reproduces the reference's sequence.
+reference's call order, so seeding both reproduces the reference's sequence.  The one exception is the opt-in scale jitter, whose
+draws come from a generator of their own (draw_scales) so that they leave that sequence alone.
 """
 import math
 import random
@@ -220,6 +222,53 @@ def check_scales(scales):
     return out
 
 
+# ------------------------------------------------------------------- scale jitter of the training crop
+def check_scale_jitter(jitter):
+    """The range of the training crop's scale jitter as a pair of floats (lo, hi): two finite numbers lo <= hi inside
+    [SCALE_MIN, SCALE_MAX] (a list or tuple; (1, 1) is allowed: every patch at scale 1).  Anything else raises ValueError."""
+    form = "expected two numbers lo,hi with %g <= lo <= hi <= %g" % (SCALE_MIN, SCALE_MAX)
+    if not isinstance(jitter, (tuple, list)) or len(jitter) != 2:
+        raise ValueError("scale jitter %r: %s" % (jitter, form))
+    if not all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in jitter):
+        raise ValueError("scale jitter %r: %s" % (jitter, form))
+    lo, hi = float(jitter[0]), float(jitter[1])
+    if not (math.isfinite(lo) and math.isfinite(hi) and SCALE_MIN <= lo <= hi <= SCALE_MAX):
+        raise ValueError("scale jitter %r: %s" % (jitter, form))
+    return lo, hi
+
+
+def parse_scale_jitter(text):
+    """The value of the command lines' --scale-jitter option: "lo,hi" as check_scale_jitter takes it.  Anything else raises
+    ValueError."""
+    try:
+        vals = [float(t) for t in text.split(",")] if isinstance(text, str) and text and text == text.strip() and " " not in text else None
+    except ValueError:
+        vals = None
+    if vals is None or len(vals) != 2:
+        raise ValueError("scale jitter %r: expected lo,hi with %g <= lo <= hi <= %g" % (text, SCALE_MIN, SCALE_MAX))
+    return check_scale_jitter(vals)
+
+
+def jitter_run_seed(seeds):
+    """The run seed of the scale draws from the pair loops.sync_rng returns (two 31-bit seeds): one integer below 2^64."""
+    return (int(seeds[0]) << 32) | int(seeds[1])
+
+
+def draw_scales(B, scale_jitter, jitter_key):
+    """The scales s_b of the B patches of a GLOBAL batch (float64 [B]), log-uniform on [lo, hi] = scale_jitter: s = exp(ln lo +
+    v (ln hi - ln lo)), v uniform in [0, 1), clamped to [lo, hi]; lo == hi gives lo exactly.  The draw comes from a generator of its own,
+    np.random.Generator(np.random.Philox(key=jitter_key)) with jitter_key = (run seed, step), two integers in [0, 2^64): it never
+    touches `random` or `numpy.random`, so every other draw of a run is what it is without the jitter, and a resumed run (same run
+    seed, same step) draws what the uninterrupted run drew."""
+    lo, hi = check_scale_jitter(scale_jitter)
+    if jitter_key is None or len(jitter_key) != 2 or not all(0 <= int(k) < 2 ** 64 for k in jitter_key):
+        raise ValueError("scale jitter: jitter_key %r must be (run seed, step), two integers in [0, 2^64)" % (jitter_key,))
+    gen = np.random.Generator(np.random.Philox(key=np.array([int(jitter_key[0]), int(jitter_key[1])], dtype=np.uint64)))
+    v = gen.random(int(B))
+    llo, lhi = math.log(lo), math.log(hi)
+    return np.minimum(np.maximum(np.exp(llo + v * (lhi - llo)), lo), hi)
+
+
 # ------------------------------------------------------------------- class weights of the training loss
 CLASS_WEIGHT_RECIPES = ("balanced", "median")
 MAX_CLASSES = 8          # the classifier kernels carry at most eight classes (include/drs.h)
@@ -410,11 +459,25 @@ class Augmentation(object):
         self.noise = None          # [B, S, S, C] float64 when host noise is used
         self.seed = 0
         self.index0 = 0            # place of the first patch in the global batch (device noise is keyed by the global index)
+        self.scale = None          # [B] float64: the scale of every patch when the crop jitters the scale (draw_scales)
+        self.geo = None            # [B, 3] float64 (step, cy, cx): the footprints of those patches (scale_geometry); set = the scaled crop
+
+    def shard(self, sl):
+        """this rank's slice `sl` of a global batch's draws (every per-patch table; the noise seed stays, index0 = sl.start: device
+        noise is keyed by the patch's place in the global batch)"""
+        mine = Augmentation(len(self.flip[sl]))
+        mine.rot_on, mine.rot, mine.noise_on, mine.flip = self.rot_on[sl], self.rot[sl], self.noise_on[sl], self.flip[sl]
+        mine.noise = self.noise[sl] if self.noise is not None else None
+        mine.scale = self.scale[sl] if self.scale is not None else None
+        mine.seed, mine.index0 = self.seed, sl.start
+        return mine
 
 
-def draw_augmentation(instances, S, C, noise="device"):
+def draw_augmentation(instances, S, C, noise="device", scale_jitter=None, jitter_key=None):
     """For every instance, in order: randint(0,2) rotate?; randint(0,2) noise? [+ normal(0, .01, (S,S,C))
-    when noise == 'host': bit-exact with the reference]; randint(0,3) flip."""
+    when noise == 'host': bit-exact with the reference]; randint(0,3) flip.
+    scale_jitter = (lo, hi) (opt-in) adds aug.scale, one scale per patch of this -- the global -- batch, from draw_scales' own generator
+    keyed by jitter_key = (run seed, step): the draws above, and the global streams after them, are what they are without it."""
     B = len(instances)
     aug = Augmentation(B)
     if noise == "host":
@@ -430,6 +493,8 @@ def draw_augmentation(instances, S, C, noise="device"):
         aug.flip[b] = np.random.randint(0, 3)
     if noise != "host":
         aug.seed = int(np.random.randint(0, 2 ** 31 - 1))
+    if scale_jitter is not None:
+        aug.scale = draw_scales(B, scale_jitter, jitter_key)
     return aug
 
 
@@ -485,17 +550,45 @@ def _shift_inside(inst_xy, pool, S):
     return inst
 
 
+def jitter_centre(r, S, s, n):
+    """One axis of the centre rule of the scale-jitter crop (include/drs.h): the patch starts at pixel r (after the shift-back) on a map
+    axis of n pixels; c = r + S / 2, clamped to [a, n - a] with a = S / (2 s) when the footprint fits (2 a <= n), else n / 2."""
+    c = float(r) + float(S) / 2.0
+    a = float(S) / (2.0 * float(s))
+    if 2.0 * a <= float(n):
+        return min(max(c, a), float(n) - a)
+    return float(n) / 2.0
+
+
+def scale_geometry(inst_xy, pool, S, scale):
+    """The footprints geo [B][3] = (step, cy, cx) (float64) of the patches `inst_xy` rows (map, x, y[, ...]) of side S at the scales
+    `scale` [B]: step = 1 / s in fp64, the centre from today's shift-back (_shift_inside) and jitter_centre per axis."""
+    inst = _shift_inside(inst_xy, pool, S)
+    scale = np.asarray(scale, dtype=np.float64).reshape(-1)
+    if len(scale) != len(inst):
+        raise ValueError("scale jitter: %d scales for %d patches" % (len(scale), len(inst)))
+    geo = np.zeros((len(inst), 3), dtype=np.float64)
+    for b, (m, x, y) in enumerate(inst):
+        s = float(scale[b])
+        if not (math.isfinite(s) and s > 0.0):
+            raise ValueError("scale jitter: scale %r of patch %d" % (s, b))
+        geo[b] = (1.0 / s, jitter_centre(x, S, s, pool.h[m]), jitter_centre(y, S, s, pool.w[m]))
+    return geo
+
+
 class _Staging(object):
     """Per-step index / augmentation tables go to the device in ONE asynchronous copy from a pinned ring buffer
     (pageable uploads would block the host every step and keep it from running ahead of the GPU).
-    Layout per slot, 8-byte aligned: rot f64 [B][6] | inst i32 [B][4] | rot_on u8 [B] | noise_on u8 [B]."""
+    Layout per slot, 8-byte aligned: rot f64 [B][6] | inst i32 [B][4] | rot_on u8 [B] | noise_on u8 [B] | pad to 8 | geo f64 [B][3]
+    (geo: the footprints of the scale-jitter crop, 24 bytes per patch, written only when the batch has them)."""
     SLOTS = 4
 
     def __init__(self, dev, b_max):
         self.b_max = b_max
         self.o_rot, self.o_inst = 0, 48 * b_max
         self.o_ron, self.o_non = 64 * b_max, 65 * b_max
-        self.nbytes = (66 * b_max + 7) // 8 * 8
+        self.o_geo = (66 * b_max + 7) // 8 * 8
+        self.nbytes = self.o_geo + 24 * b_max
         self.host = [torch.empty(self.nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available()) for _ in range(self.SLOTS)]
         self.dev = [torch.empty(self.nbytes, dtype=torch.uint8, device=dev) for _ in range(self.SLOTS)]
         self.events = [None] * self.SLOTS
@@ -513,17 +606,19 @@ class _Staging(object):
             h[self.o_rot:self.o_rot + 48 * B].view(np.float64)[:] = aug.rot.reshape(-1)
             h[self.o_ron:self.o_ron + B] = aug.rot_on
             h[self.o_non:self.o_non + B] = aug.noise_on
+            if aug.geo is not None:
+                h[self.o_geo:self.o_geo + 24 * B].view(np.float64)[:] = np.asarray(aug.geo, dtype=np.float64).reshape(-1)
         self.dev[k].copy_(self.host[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self.events[k] = ev
         base = self.dev[k].data_ptr()
-        return base + self.o_inst, base + self.o_rot, base + self.o_ron, base + self.o_non
+        return base + self.o_inst, base + self.o_rot, base + self.o_ron, base + self.o_non, base + self.o_geo
 
 
 def _crop_setup(net, B, S, inst, mean, std, aug=None):
     """What the three crop_*_to_net share: the size check, `inst` (int32 [B][3 or 4]) and the augmentation tables uploaded through the
-    net's pinned staging ring (_Staging.upload's four device addresses), and mean / std as three C doubles each (bands past the third are
+    net's pinned staging ring (_Staging.upload's five device addresses), and mean / std as three C doubles each (bands past the third are
     not normalised; HOST pointers: copied into the kernel arguments).  Returns (addresses, mean3, std3, keep); keep holds the doubles
     alive over the call."""
     import ctypes as C
@@ -544,24 +639,33 @@ def crop_to_net(net, pool, instances, S, mean, std, aug=None, void_label=-1, qua
     quantize_f16: the coffee script's training patches pass through float16 (coffee:293) and are normalised in place in that
     array (coffee:1290): value, difference and quotient are each rounded to float16; NumPy >= 2 evaluates the difference and the
     quotient in the type of the mean / std scalars when that is wider: float32 for coffee's own statistics (np.mean / np.std of
-    float32 patches, coffee:78-79), float64 when `mean` arrives as float64 (drs_crop_normalize modes 1 / 2)."""
+    float32 patches, coffee:78-79), float64 when `mean` arrives as float64 (drs_crop_normalize modes 1 / 2).
+    aug.geo set (scale_geometry of aug.scale; opt-in, training only): every patch is resampled from its footprint
+    (drs_crop_normalize_scaled, include/drs.h); not set: the plain crop, as ever."""
     B = len(instances)
     inst = np.zeros((B, 4), dtype=np.int32)
     inst[:, :3] = _shift_inside(instances, pool, S)
     if aug is not None:
         inst[:, 3] = aug.flip
-    (p_inst, p_rot, p_ron, p_non), m3, s3, keep = _crop_setup(net, B, S, inst, mean, std, aug)
+    scaled = aug is not None and aug.geo is not None
+    if scaled and np.asarray(aug.geo).shape != (B, 3):
+        raise ValueError("scale jitter: geo %r for %d patches" % (np.asarray(aug.geo).shape, B))
+    (p_inst, p_rot, p_ron, p_non, p_geo), m3, s3, keep = _crop_setup(net, B, S, inst, mean, std, aug)
     noise = None
     if aug is not None and aug.noise is not None:
         noise = torch.from_numpy(aug.noise).to(net.dev)          # reference-exact host noise (tests / parity runs)
     slab, P, ld = net.input_slab()
-    _lib.call("drs_crop_normalize", pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.labels.data_ptr(),
-              pool.tile_off.data_ptr(), pool.lab_off.data_ptr(), pool.tile_h.data_ptr(), pool.tile_w.data_ptr(), pool.C,
-              p_inst, p_rot if aug is not None else None, p_ron if aug is not None else None,
-              None if noise is None else noise.data_ptr(), p_non if aug is not None else None,
-              aug.seed if aug is not None else 0, aug.index0 if aug is not None else 0, m3, s3, B, S, P, ld,
-              slab.data_ptr(), net.labels.data_ptr(), net.acc_mask.data_ptr(), int(void_label),
-              (2 if getattr(mean, "dtype", None) == np.float64 else 1) if quantize_f16 else 0, net._stream())
+    head = (pool.tiles.data_ptr(), 1 if pool.f64 else 0, pool.labels.data_ptr(),
+            pool.tile_off.data_ptr(), pool.lab_off.data_ptr(), pool.tile_h.data_ptr(), pool.tile_w.data_ptr())
+    tail = (p_rot if aug is not None else None, p_ron if aug is not None else None,
+            None if noise is None else noise.data_ptr(), p_non if aug is not None else None,
+            aug.seed if aug is not None else 0, aug.index0 if aug is not None else 0, m3, s3, B, S, P, ld,
+            slab.data_ptr(), net.labels.data_ptr(), net.acc_mask.data_ptr(), int(void_label),
+            (2 if getattr(mean, "dtype", None) == np.float64 else 1) if quantize_f16 else 0, net._stream())
+    if scaled:                                                   # training with scale jitter: the resampling sibling of the crop
+        _lib.call("drs_crop_normalize_scaled", *head, len(pool.h), pool.C, p_inst, p_geo, *tail)
+    else:
+        _lib.call("drs_crop_normalize", *head, pool.C, p_inst, *tail)
     net._keep = noise                                            # alive until the stream has consumed it
     return inst[:, 1:3]
 

@@ -326,6 +326,39 @@ int drs_crop_normalize(const void* tiles, int tiles_are_f64, const unsigned char
                        const double* std3,
                        int B, int S, int P, int ld, float* out, unsigned char* out_lab, unsigned char* out_mask,
                        int void_label, int quantize_f16, void* stream);
+/* scale-jitter augmentation of training, fused into the crop (opt-in).  NORMATIVE: this text, the numpy statement
+ * tests/scale_jitter_ref.py and the kernel say the same thing in the same operation order.
+ * Patch b of side S has a scale s_b: it is the S x S image whose pixel centres sample the source map X (h x w) over a footprint of
+ * side S / s_b around a centre (cy, cx) given in continuous pixel-edge coordinates (pixel i covers [i, i + 1], its centre is
+ * i + 0.5).  geo [B][3] (fp64, device data) = (step, cy, cx) with step = 1 / s_b computed by the host in fp64.  Per axis -- map
+ * length n, centre c, patch pixel index p in [0, S) -- every product and sum rounded on its own, in fp64:
+ *     t = (p + 0.5) - 0.5 S,   u = c + t step                        the position of the pixel's centre
+ *     valid on the axis iff 0 <= u <= n;  a pixel is valid iff both axes are
+ *     src = min(max(u - 0.5, 0), n - 1),  i0 = floor(src),  i1 = min(i0 + 1, n - 1),  l = src - i0
+ * and the value is D's expression (drs_crop_resampled below), (1-ly)((1-lx) v00 + lx v01) + ly((1-lx) v10 + lx v11), in fp64 on
+ * every channel.  The label is that of the source pixel that contains the centre, X_lab[min(floor(u_y), h-1)][min(floor(u_x), w-1)].
+ * An invalid pixel is filled as the rotation fills: value 0, label 0, mask 0.
+ * The centre is the host's (patches.scale_geometry): with r the patch's row (column) after the border shift-back for side S
+ * (isprs:260-269), c = r + S / 2; then, with a = S / (2 s_b): c = min(max(c, a), n - a) if 2 a <= n (a footprint that fits in the map
+ * lies inside it), else c = n / 2 (the map is smaller than the footprint: the overhang is invalid and masked).
+ * Everything else acts on this resampled patch as it acts on drs_crop_normalize's plain crop, in that order: the order-0 rotation
+ * picks a patch pixel (si, sj), and it is that pixel that is resampled (p = si on the row axis, sj on the column axis); a rotated-in
+ * pixel is invalid; the noise is added after the interpolation and indexed before the flip, from the host array or from Philox keyed
+ * by the global patch index; quantize_f16 (the fp64 value rounded to float32, as coffee's patches are float32, then to float16) and
+ * the normalisation of bands 0..2 follow; one rounding to fp32 on the store; out_mask = valid && label != void_label.
+ * At s_b = 1 the weights are exactly (1, 0) and slab, labels and mask are drs_crop_normalize's bit for bit (values other than -0.0).
+ *
+ * drs_crop_normalize_scaled: drs_crop_normalize's arguments plus geo, and n_maps (the number of maps in the pool), which the
+ * device-side check of geo needs.  inst [B][4] = (map, row, col, flip): row / col are not read (the centre is in geo).  geo and inst are
+ * checked on the device, as drs_crop_resampled checks inst: a step that is not finite and positive, a centre that is not finite, or a
+ * map index outside [0, n_maps), leaves that patch's slab all zeros (no noise), its labels 0 and its mask 0.  Every source index is
+ * clamped into its map, so no finite geo reads outside the pool. */
+int drs_crop_normalize_scaled(const void* tiles, int tiles_are_f64, const unsigned char* labels, const long long* tile_off,
+                              const long long* lab_off, const int* tile_h, const int* tile_w, int n_maps, int C, const int* inst,
+                              const double* geo, const double* rot, const unsigned char* rot_on, const double* noise,
+                              const unsigned char* noise_on, unsigned long long seed, int noise_index0, const double* mean3,
+                              const double* std3, int B, int S, int P, int ld, float* out, unsigned char* out_lab,
+                              unsigned char* out_mask, int void_label, int quantize_f16, void* stream);
 
 /* ---- overlap-add of window logits and arg-max of the average  (isprs:1261-1284, 1925-1949) ---------------
  * windows [first_window, first_window + n_windows) of the row-major window grid at `stride` (last row/col
