@@ -80,6 +80,8 @@ SIGNATURES = {
     "drs_tile_place_dihedral": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "drs_crop_resampled": (_i, [_p, _i, _p, _p, _p, _i, _i, _p, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "drs_resample_accumulate": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "drs_crf_unary": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "drs_crf_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p]),
     "drs_softmax_accumulate": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
     # ---- step level (csrc/engine.hip)

@@ -20,6 +20,10 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     `<output_path>temperature_step_<N>.npy` (one float32, beta = 1 / T), and validate_test then reports with it
   + optionally, anywhere, with --score-maps only, `--temperature=auto|<T>` (validate_test / generate_final_maps): the score maps are
     of the probabilities at temperature T > 0; `auto` loads the file --calibrate-temperature wrote for the step being evaluated
+  + optionally, anywhere, `--crf[=ITERS]` (validate_test / generate_final_maps; any inference path): every map is the posterior
+    refined by a local dense CRF against the image (loops.refine_crf; DESIGN.md 8a.6), ITERS mean-field iterations (1..10, default 5);
+    `--crf-params=R,step,w_app,theta_xy,theta_rgb,w_smooth,theta_s` sets its window and kernels (default 5,2,4,8,0.08,2,2) and alone
+    implies --crf.  With --crf a --temperature is accepted without --score-maps: it scales the unary and can change labels
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -174,6 +178,27 @@ def temperature_file(output_path, step):
     return output_path + "temperature_step_" + str(step) + ".npy"
 
 
+CRF_FLAG = "--crf"
+CRF_PARAMS_FLAG = "--crf-params"
+
+
+def parse_crf(argv):
+    """isprs flavour: the optional `--crf[=ITERS]` and `--crf-params=R,step,w_app,theta_xy,theta_rgb,w_smooth,theta_s` (anywhere in
+    argv; validate_test / generate_final_maps, which main checks).  Returns (argv without the flags, the patches.CrfParams of
+    patches.check_crf), or (argv unchanged, None) without either; --crf-params alone implies --crf.  A malformed or out-of-range
+    value, or a flag given twice, raises ValueError."""
+    argv, iters = _take_flag(argv, CRF_FLAG, lambda a, v: _or_expected(
+        P.parse_crf_iters, a, v, "%s or %s=ITERS (iterations, 1..%d)" % (CRF_FLAG, CRF_FLAG, P.CRF_MAX_ITERS)), bare=P.CRF_DEFAULTS.iters)
+    argv, params = _take_flag(argv, CRF_PARAMS_FLAG, lambda a, v: _or_expected(
+        P.parse_crf_params, a, v, "%s=%s (%s)" % (CRF_PARAMS_FLAG, ",".join(P.CrfParams._fields[1:]), P.CRF_FORM)))
+    if iters is None and params is None:
+        return argv, None
+    spec = dict(params or {})
+    if iters is not None:
+        spec["iters"] = iters
+    return argv, P.check_crf(spec)
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -275,6 +300,7 @@ def main(argv=None, device=None, comm=None):
         argv, score_maps = parse_score_maps(argv)
         argv, calibrate = parse_calibrate_temperature(argv)
         argv, temperature = parse_temperature(argv)
+        argv, crf = parse_crf(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
@@ -288,7 +314,7 @@ def main(argv=None, device=None, comm=None):
         sys.exit(DENSE_SE_FLAG + " applies to overlap-tile inference only: give --dense-tile as well")
     if calibrate is not None and score_maps is None:
         sys.exit(CALIBRATE_FLAG + " applies to the score maps only: give --score-maps as well")
-    if temperature is not None and score_maps is None:
+    if temperature is not None and score_maps is None and crf is None:
         sys.exit(TEMPERATURE_FLAG + " applies to the score maps only: give --score-maps as well")
     if calibrate is not None and temperature is not None:
         sys.exit(CALIBRATE_FLAG + " fits the temperature it reports with: " + TEMPERATURE_FLAG + " cannot be given as well")
@@ -302,6 +328,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(CALIBRATE_FLAG + " applies to the validate_test process only")
     if temperature is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(TEMPERATURE_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if crf is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(CRF_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -376,6 +404,7 @@ def main(argv=None, device=None, comm=None):
         except (ValueError, IndexError) as e:
             sys.exit(TEMPERATURE_FLAG + "=auto: " + temperature_file(output_path, step) + ": " + str(e))
     path_kw = dict(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
+    crf_kw = {} if crf is None else dict(crf=crf)          # without the flag the loops are called as they always were
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
@@ -389,11 +418,11 @@ def main(argv=None, device=None, comm=None):
                       " Iterations= " + str(fit["iterations"]))
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw)
+                                   step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         score_maps=score_maps, temperature_beta=temperature, **path_kw)
+                                         score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -487,12 +487,13 @@ def _score_buffers(scores, n, dev):
     return {k: torch.zeros(n, dtype=torch.uint8, device=dev) for k in P.check_score_kinds(scores)}
 
 
-def _check_temperature(temperature_beta, scores):
+def _check_temperature(temperature_beta, scores, crf=None):
     """The `temperature_beta` argument of an inference path as the float the kernel takes (patches.check_temperature_beta), None without
-    it.  A temperature changes the score maps and nothing else, so it needs `scores`."""
+    it.  A temperature changes the score maps and nothing else, so it needs `scores` -- unless a CRF refines the map (`crf`, DESIGN.md
+    8a.6): there it scales the unary, and can change labels."""
     if temperature_beta is None:
         return None
-    if scores is None:
+    if scores is None and crf is None:
         raise ValueError("temperature_beta needs score maps (scores / score_maps): a temperature never changes a label")
     return P.check_temperature_beta(temperature_beta)
 
@@ -972,6 +973,44 @@ def best_sizes(distribution_type, values, patch_acc_loss, patch_occur, update_ty
     return chosen
 
 
+def refine_crf(net, pool, map_index, sums, occur, sums_are_prob, crf, scores=None, temperature_beta=None):
+    """Local dense-CRF refinement of one map's posterior (opt-in; include/drs.h drs_crf_unary / drs_crf_step): from the
+    accumulators an inference path hands out with return_sums (sums [h*w*K], occur [h*w], whole on this rank) and the map's image in
+    `pool`, crf.iters mean-field iterations of a bilateral + smoothness Potts model over a (2 radius + 1)^2 window dilated by crf.step
+    (crf: what patches.check_crf accepts).  The unary is log softmax(beta u), u the path's score vector (8a.5) and beta =
+    temperature_beta (default 1): here a temperature enters the model and CAN change labels.  Two ping-pong Q buffers and the unary,
+    4 (3 K + 1) bytes per pixel beside the sums.  Returns (uint8 labels [h, w], {kind: uint8 map [h, w]} or None) as device tensors:
+    the first maximum of the refined Q and, with `scores` (kinds from patches.SCORE_KINDS), drs_stitch_finalize_scores' maps of it;
+    an uncovered pixel (occur 0) is never a neighbour, keeps label 0 and scores as uncovered."""
+    from . import _lib
+    crf = P.check_crf(crf)
+    kinds = None if scores is None else P.check_score_kinds(scores)
+    beta = 1.0 if temperature_beta is None else P.check_temperature_beta(temperature_beta)
+    h, w, K, C = pool.h[map_index], pool.w[map_index], net.plan.K, pool.C
+    n = h * w
+    st = net._stream()
+    logp = torch.empty(n * K, dtype=torch.float32, device=net.dev)
+    q = [torch.empty(n * K, dtype=torch.float32, device=net.dev) for _ in range(2)]
+    live = torch.empty(n, dtype=torch.int32, device=net.dev)
+    _lib.call("drs_crf_unary", sums.data_ptr(), occur.data_ptr(), h, w, K, 1 if sums_are_prob else 0, beta, logp.data_ptr(),
+              q[0].data_ptr(), live.data_ptr(), st)
+    tile = pool.tiles.data_ptr() + int(pool.tile_off[map_index].item()) * (8 if pool.f64 else 4)
+    for it in range(crf.iters):
+        _lib.call("drs_crf_step", q[it & 1].data_ptr(), logp.data_ptr(), live.data_ptr(), tile, 1 if pool.f64 else 0, C, h, w, K, 0, h,
+                  crf.radius, crf.step, crf.w_app, crf.theta_xy, crf.theta_rgb, crf.w_smooth, crf.theta_s, q[(it + 1) & 1].data_ptr(), st)
+    return _labels_tail(net, q[crf.iters & 1], live, 0, 0, h, h, w, True, kinds, None)
+
+
+def _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf):
+    """One map of validate_test / generate_final_maps: (labels, score maps or None) of the path, or, with `crf`, of the CRF that refines
+    the path's sums (whole on every rank, so under data parallelism every rank refines the whole map and gets the same bits)."""
+    if crf is None:
+        pred, _, smaps = path.run(net, pool, k, batch_size, mean_full, std_full, comm, scores=kinds, beta=beta)
+        return pred, smaps
+    sums, occur, is_prob = path.run(net, pool, k, batch_size, mean_full, std_full, comm, return_sums=True)
+    return refine_crf(net, pool, k, sums, occur, is_prob, crf, kinds, beta)
+
+
 def _calibration_str(cal):
     return ("Calibration ECE= " + "{:.6f}".format(cal["ece"]) + " MCE= " + "{:.6f}".format(cal["mce"]) +
             " Mean Confidence= " + "{:.6f}".format(cal["mean_confidence"]) + " Accuracy= " + "{:.6f}".format(cal["accuracy"]))
@@ -1027,7 +1066,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None):
+                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1042,12 +1081,17 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     [256][2] (drs_reliability_histogram), "calibration": metrics.calibration of it, plus "per_map": [the same per map]}.
     temperature_beta (opt-in; with score_maps only; an inverse temperature, e.g. fit_temperature's): the score maps, and so the
     calibration report, are of the calibrated probabilities; every Calibration line then ends in ` Temperature= T`
-    (T = 1 / beta) and extra carries "temperature_beta".  Labels and reference-format lines do not change."""
+    (T = 1 / beta) and extra carries "temperature_beta".  Labels and reference-format lines do not change.
+    crf (opt-in; any inference path; what patches.check_crf accepts): every map is the path's posterior refined by a local dense CRF
+    against the image (refine_crf): accuracy, kappa, confusion matrix, returned maps, score maps and calibration
+    lines are then those of the refined map.  With crf a temperature_beta is accepted without score_maps: it scales the unary, so
+    with a CRF it CAN change labels.  Without crf nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
     path.check()
-    beta = _check_temperature(temperature_beta, score_maps)
+    crf = None if crf is None else P.check_crf(crf)
+    beta = _check_temperature(temperature_beta, score_maps, crf)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
@@ -1063,7 +1107,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     all_f1_per_class = np.zeros(K, dtype=np.float32)
     maps = []
     for k in range(len(testing_data)):
-        pred, _, smaps = path.run(net, pool, k, batch_size, mean_full, std_full, comm, scores=kinds, beta=beta)
+        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
         conf = torch.zeros(K * K, dtype=torch.int32, device=net.dev)
         lab = pool.labels[int(pool.lab_off[k].item()):int(pool.lab_off[k].item()) + h * w]
@@ -1122,7 +1166,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
-                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None):
+                        dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None,
+                        crf=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
@@ -1132,11 +1177,15 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     score_maps (opt-in; a tuple of kinds from patches.SCORE_KINDS; any inference path): per-pixel score maps written
     beside each label file as `<stem>_<kind>.npy` (uint8 [h, w]) and an 8-bit grey `<stem>_<kind>.tif`, by rank 0 as the labels are;
     returns (label maps, [per map {kind: uint8 numpy [h, w]}]).  temperature_beta (opt-in; with score_maps only; an inverse
-    temperature): the score files are of the calibrated probabilities; the label files do not change."""
+    temperature): the score files are of the calibrated probabilities; the label files do not change.
+    crf (opt-in; any inference path; what patches.check_crf accepts): the written maps and score maps are those of the path's
+    posterior refined by a local dense CRF against the image (refine_crf).  With crf a temperature_beta is accepted
+    without score_maps: it scales the unary, so with a CRF it CAN change the label files."""
     comm = comm or NoComm()
     path = InferencePath(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     path.check()
-    beta = _check_temperature(temperature_beta, score_maps)
+    crf = None if crf is None else P.check_crf(crf)
+    beta = _check_temperature(temperature_beta, score_maps, crf)
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
     score_list = []
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -1146,7 +1195,7 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     pool = P.TilePool(testing_data, None, net.dev)
     maps = []
     for k in range(len(testing_data)):
-        pred, _, smaps = path.run(net, pool, k, batch_size, mean_full, std_full, comm, scores=kinds, beta=beta)
+        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         maps.append(pred.cpu().numpy())
         if kinds is not None:
             score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})

@@ -15,6 +15,7 @@ RNG: like the reference, draws come from the global `random` / `numpy.random` st
 reference's call order, so seeding both reproduces the reference's sequence.  The one exception is the opt-in scale jitter, whose
 draws come from a generator of their own (draw_scales) so that they leave that sequence alone.
 """
+import collections
 import math
 import random
 
@@ -424,6 +425,71 @@ def parse_temperature(text):
         return check_temperature_beta(1.0 / T)
     except ValueError:
         raise ValueError("temperature %r: expected auto or a temperature T > 0 with 1/64 <= 1/T <= 64" % (text,)) from None
+
+
+# ------------------------------------------------------------------- local dense-CRF refinement of whole maps
+CrfParams = collections.namedtuple("CrfParams", "iters radius step w_app theta_xy theta_rgb w_smooth theta_s")
+CRF_DEFAULTS = CrfParams(5, 5, 2, 4.0, 8.0, 0.08, 2.0, 2.0)
+CRF_MAX_ITERS, CRF_MAX_RADIUS, CRF_MAX_STEP, CRF_MAX_REACH = 10, 6, 4, 12     # the ranges include/drs.h accepts (iterations: the host's)
+CRF_FORM = ("iters in 1..%d, radius in 1..%d, step in 1..%d with radius * step <= %d, w_app >= 0, theta_xy > 0, theta_rgb > 0, "
+            "w_smooth >= 0, theta_s > 0" % (CRF_MAX_ITERS, CRF_MAX_RADIUS, CRF_MAX_STEP, CRF_MAX_REACH))
+
+
+def check_crf(spec):
+    """The `crf` option of validate_test / generate_final_maps as a CrfParams: True or "crf" (the defaults), an int (the iterations,
+    everything else at its default), a dict of some of CrfParams' fields, or all eight as a tuple / list in CrfParams' order.  The
+    thetas of position are in pixels, theta_rgb in the units of the tiles' values.  Anything else, or a value outside its range,
+    raises ValueError naming the ranges."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    def is_num(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and math.isfinite(float(v))
+    if spec is True or (isinstance(spec, str) and spec == "crf"):
+        p = CRF_DEFAULTS
+    elif is_int(spec):
+        p = CRF_DEFAULTS._replace(iters=int(spec))
+    elif isinstance(spec, dict):
+        unknown = [k for k in spec if k not in CrfParams._fields]
+        if unknown:
+            raise ValueError("crf %r: unknown parameter %r; expected some of %s" % (spec, unknown[0], ", ".join(CrfParams._fields)))
+        p = CRF_DEFAULTS._replace(**spec)
+    elif isinstance(spec, (tuple, list)) and len(spec) == len(CrfParams._fields):
+        p = CrfParams(*spec)
+    else:
+        raise ValueError("crf %r: expected True, \"crf\", the iterations, a dict or the 8 values (%s): %s"
+                         % (spec, ", ".join(CrfParams._fields), CRF_FORM))
+    if not all(is_int(v) for v in p[:3]) or not all(is_num(v) for v in p[3:]):
+        raise ValueError("crf %r: iters, radius and step are integers, the rest finite numbers: %s" % (spec, CRF_FORM))
+    p = CrfParams(int(p.iters), int(p.radius), int(p.step), *[float(v) for v in p[3:]])
+    ok = (1 <= p.iters <= CRF_MAX_ITERS and 1 <= p.radius <= CRF_MAX_RADIUS and 1 <= p.step <= CRF_MAX_STEP
+          and p.radius * p.step <= CRF_MAX_REACH and p.w_app >= 0 and p.w_smooth >= 0
+          and all(np.float32(t) > 0 for t in (p.theta_xy, p.theta_rgb, p.theta_s)))
+    if not ok:
+        raise ValueError("crf %r: out of range: %s" % (spec, CRF_FORM))
+    return p
+
+
+def parse_crf_iters(text):
+    """The value of the command line's --crf=ITERS: the iterations as an int in 1..10.  Anything else raises ValueError."""
+    if not (isinstance(text, str) and text.isascii() and text.isdigit()) or not 1 <= int(text) <= CRF_MAX_ITERS:
+        raise ValueError("crf iterations %r: expected an integer in 1..%d" % (text, CRF_MAX_ITERS))
+    return int(text)
+
+
+def parse_crf_params(text):
+    """The value of the command line's --crf-params: "R,step,w_app,theta_xy,theta_rgb,w_smooth,theta_s" as the dict check_crf takes
+    (the iterations are --crf's).  Anything else raises ValueError."""
+    names = CrfParams._fields[1:]
+    parts = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else []
+    try:
+        if len(parts) != len(names) or not all(t.isascii() and t.isdigit() for t in parts[:2]):
+            raise ValueError(text)
+        spec = dict(zip(names, [int(parts[0]), int(parts[1])] + [float(t) for t in parts[2:]]))
+        check_crf(spec)
+    except ValueError:
+        raise ValueError("crf parameters %r: expected %s with %s" % (text, ",".join(names), CRF_FORM)) from None
+    return spec
 
 
 # ---------------------------------------------------------------------------------------- augmentation draws

@@ -443,6 +443,30 @@ int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int
 int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta,
                                  unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
                                  void* stream);
+/* local dense-CRF refinement of a whole-map posterior (opt-in; csrc/refine.hip): mean-field iterations of a Potts model
+ * with a bilateral and a smoothness kernel (Kraehenbuehl & Koltun, Efficient inference in fully connected CRFs, 2011) over a window of
+ * (2R+1)^2 - 1 neighbours dilated by `step` (Teichmann & Cipolla, Convolutional CRFs, 2018).  NORMATIVE: this text and the fp64 numpy
+ * statement tests/crf_ref.py.  Inputs are the accumulators handed to drs_stitch_finalize* and the map's image [h][w][C] as the tile
+ * pool stores it (fp64 or fp32, each value read as fp32).
+ * drs_crf_unary: per pixel i, oc = occur[i] ? occur[i] : 1, in fp32: u_k = sums[i][k] / (float)oc (sums_are_prob == 0) or
+ *     logf(fmaxf(sums[i][k] / (float)oc, FLT_MIN)) (!= 0); t_k = beta u_k, rounded before the maximum is subtracted (beta finite,
+ *     1/64 <= beta <= 64, else DRS_ERR_ARG);  logp[i][k] = t_k - max t - ln sum_l exp(t_l - max t);  q0[i][k] = softmax_k(t);
+ *     live[i] = occur[i] != 0.  A pixel that is not live is dead: it is never a neighbour and no iteration moves its Q.
+ * drs_crf_step: one iteration for the image rows [row0, row0 + rows), reading the whole q_in [h*w][K] and writing those rows of q_out
+ *     (q_out != q_in).  For a live pixel p the neighbours are q = p + (i, j) step, |i|, |j| <= R, (i, j) != (0, 0), inside the map and live;
+ *         kappa(p, q) = w_app exp(-|d|^2 / (2 theta_xy^2) - |f_p - f_q|^2 / (2 theta_rgb^2)) + w_smooth exp(-|d|^2 / (2 theta_s^2)),
+ *     d = q - p in pixels, f the C image values;  m_p[k] = sum_q kappa(p, q) q_in[q][k], summed i ascending, then j ascending;
+ *         q_out[p] = softmax_k(logp[p][k] + m_p[k]), max-subtracted
+ *     (the Potts compatibility; no kernel normalisation).  A dead pixel's q_out is its q_in.  The spatial factors are made once per call
+ *     on the host in fp64, the appearance factor is one exp2 per neighbour.  No atomics: a pixel's bits depend neither on the
+ *     workgroup tiling nor on how the rows are cut into calls.  Ranges, else DRS_ERR_ARG: K 2..8, C 1..8, R 1..6, step 1..4,
+ *     R * step <= 12, w_app, w_smooth finite >= 0, theta_* finite > 0, 0 <= row0, 1 <= rows, row0 + rows <= h.
+ * Labels and score maps of the refined posterior: drs_stitch_finalize / drs_stitch_finalize_scores on (Q, live, sums_are_prob = 1). */
+int drs_crf_unary(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta, float* logp, float* q0,
+                  unsigned int* live, void* stream);
+int drs_crf_step(const float* q_in, const float* logp, const unsigned int* live, const void* tile, int tile_is_f64, int C, int h, int w,
+                 int K, int row0, int rows, int R, int step, float w_app, float theta_xy, float theta_rgb, float w_smooth, float theta_s,
+                 float* q_out, void* stream);
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);
