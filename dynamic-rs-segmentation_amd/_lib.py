@@ -83,6 +83,8 @@ SIGNATURES = {
     "drs_crf_unary": (_i, [_p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "drs_crf_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p]),
     "drs_softmax_accumulate": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "drs_boundary_distance": (_i, [_p, _i, _i, _i, _p, _p]),
+    "drs_boundary_histogram": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
     # ---- step level (csrc/engine.hip)
     "drs_net_create": (_i, [C.c_char_p, _i, _i, _f, _i, _i, _i, _f, C.POINTER(_p)]),

@@ -24,6 +24,9 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     refined by a local dense CRF against the image (loops.refine_crf; DESIGN.md 8a.6), ITERS mean-field iterations (1..10, default 5);
     `--crf-params=R,step,w_app,theta_xy,theta_rgb,w_smooth,theta_s` sets its window and kernels (default 5,2,4,8,0.08,2,2) and alone
     implies --crf.  With --crf a --temperature is accepted without --score-maps: it scales the unary and can change labels
+  + optionally, anywhere, `--boundary-scores[=d0,d1,...]` (validate_test; any inference path, with or without --crf): one more line per
+    map and for all maps with the trimap accuracy and the Boundary IoU at the distances given (pixels; 1 to 8 ascending integers in
+    1..16; the bare flag means 1,2,4,8) and the plain IoU (loops.validate_test's boundary_scores)
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -199,6 +202,18 @@ def parse_crf(argv):
     return argv, P.check_crf(spec)
 
 
+BOUNDARY_FLAG = "--boundary-scores"
+
+
+def parse_boundary_scores(argv):
+    """isprs flavour: the optional `--boundary-scores[=d0,d1,...]` (anywhere in argv; validate_test, which main checks).  Returns (argv
+    without the flag, tuple of distances; patches.parse_boundary_scores) -- patches.BOUNDARY_DEFAULT for the bare flag --, or (argv
+    unchanged, None) without it.  A malformed or invalid list, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, BOUNDARY_FLAG, lambda a, v: _or_expected(
+        P.parse_boundary_scores, a, v, "%s or %s=d0,d1,... (1 to %d ascending integers in 1..%d, such as 1,2,4,8)"
+        % (BOUNDARY_FLAG, BOUNDARY_FLAG, P.BOUNDARY_MAX_DISTANCES, P.BOUNDARY_MAX_REACH)), bare=P.BOUNDARY_DEFAULT)
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -301,6 +316,7 @@ def main(argv=None, device=None, comm=None):
         argv, calibrate = parse_calibrate_temperature(argv)
         argv, temperature = parse_temperature(argv)
         argv, crf = parse_crf(argv)
+        argv, boundary = parse_boundary_scores(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
@@ -330,6 +346,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(TEMPERATURE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if crf is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(CRF_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if boundary is not None and argv[16] != "validate_test":
+        sys.exit(BOUNDARY_FLAG + " applies to the validate_test process only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -405,6 +423,7 @@ def main(argv=None, device=None, comm=None):
             sys.exit(TEMPERATURE_FLAG + "=auto: " + temperature_file(output_path, step) + ": " + str(e))
     path_kw = dict(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     crf_kw = {} if crf is None else dict(crf=crf)          # without the flag the loops are called as they always were
+    boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
@@ -418,7 +437,8 @@ def main(argv=None, device=None, comm=None):
                       " Iterations= " + str(fit["iterations"]))
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
-                                   step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw)
+                                   step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
+                                   **boundary_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,

@@ -12,6 +12,7 @@ side files), with every per-pixel operation on the device.  Differences that are
   * under data parallelism every rank runs the same host code with the same RNG streams and takes its slice of the batch.
 """
 import collections
+import ctypes
 import datetime
 import math
 import os
@@ -1016,6 +1017,39 @@ def _calibration_str(cal):
             " Mean Confidence= " + "{:.6f}".format(cal["mean_confidence"]) + " Accuracy= " + "{:.6f}".format(cal["accuracy"]))
 
 
+def boundary_histogram(truth_dev, pred_dev, h, w, K, ignore_label, distances, hist=None, stream=None):
+    """The boundary table of one (truth, prediction) pair of uint8 device maps [h][w] (drs_boundary_histogram; include/drs.h; DESIGN.md
+    8a.7): int64 device tensor [(n+1)][(n+1)][K][K], hist[bin in truth][bin in pred][truth][pred], for the distances of
+    patches.check_boundary_distances.  `hist` (such a tensor) is ADDED to and returned; without it a zeroed one is made.  stream: a raw
+    stream handle (default: torch's current stream on the maps' device).  metrics.boundary_scores turns the table into scores."""
+    from . import _lib
+    distances = P.check_boundary_distances(distances)
+    n = len(distances)
+    if hist is None:
+        hist = torch.zeros((n + 1, n + 1, K, K), dtype=torch.int64, device=truth_dev.device)
+    elif hist.dtype != torch.int64 or tuple(hist.shape) != (n + 1, n + 1, K, K) or not hist.is_contiguous():
+        raise ValueError("boundary_histogram: hist must be a contiguous int64 tensor [%d][%d][%d][%d]" % (n + 1, n + 1, K, K))
+    if stream is None:
+        stream = torch.cuda.current_stream(truth_dev.device).cuda_stream
+    dist = (ctypes.c_int * n)(*distances)
+    _lib.call("drs_boundary_histogram", truth_dev.data_ptr(), pred_dev.data_ptr(), int(h), int(w), int(K),
+              -1 if ignore_label is None else int(ignore_label), ctypes.addressof(dist), n, hist.data_ptr(), stream)
+    return hist
+
+
+def _boundary_str(b):
+    """the Boundary line's text from metrics.boundary_scores' dict"""
+    bands = b["bands"]
+    return ("Boundary d= " + " ".join(str(d) for d in b["distances"]) +
+            " Band Pixels= " + " ".join(str(x["count"]) for x in bands) +
+            " Band Accuracy= " + " ".join("{:.6f}".format(x["accuracy"]) for x in bands) +
+            " Boundary IoU= " + " ".join("{:.6f}".format(x["boundary_iou"]) for x in bands) +
+            " Boundary IoU per class (d= " + str(bands[-1]["d"]) + ")= " +
+            "[" + " ".join("{:.6f}".format(v) for v in bands[-1]["boundary_iou_per_class"]) + "]" +
+            " IoU per class= " + "[" + " ".join("{:.6f}".format(v) for v in b["iou_per_class"]) + "]" +
+            " Mean IoU= " + "{:.6f}".format(b["mean_iou"]))
+
+
 FIT_RESIDENT_BYTES = 32 << 30       # default cap on the accumulators fit_temperature keeps on the device
 
 
@@ -1066,7 +1100,8 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
-                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None):
+                  dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None,
+                  boundary_scores=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1085,13 +1120,22 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     crf (opt-in; any inference path; what patches.check_crf accepts): every map is the path's posterior refined by a local dense CRF
     against the image (refine_crf): accuracy, kappa, confusion matrix, returned maps, score maps and calibration
     lines are then those of the refined map.  With crf a temperature_beta is accepted without score_maps: it scales the unary, so
-    with a CRF it CAN change labels.  Without crf nothing changes."""
+    with a CRF it CAN change labels.  Without crf nothing changes.
+    boundary_scores (opt-in; any inference path; a tuple of distances in pixels, patches.check_boundary_distances, e.g.
+    patches.BOUNDARY_DEFAULT): trimap accuracy, Boundary IoU and plain IoU of every map and of all maps: per map, one
+    drs_boundary_histogram call on the labels and the map that drs_confusion scored -- the refined map with crf.  One line
+    `---- Iter N -- Test Map M: Boundary d= ... Band Pixels= ... Band Accuracy= ... Boundary IoU= ... Boundary IoU per class (d= D)= ...
+    IoU per class= ... Mean IoU= ...` follows the reference-format line (and the Calibration line where there is one), per map and
+    for all maps from the summed table.  Returns (all-maps confusion matrix, label maps, extra) with extra["boundary"] =
+    metrics.boundary_scores of the all-maps table, plus "per_map": [the same per map] and "hist": the int64 numpy table; the score-map
+    keys are in extra only when score_maps is given too.  Without boundary_scores nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
     path.check()
     crf = None if crf is None else P.check_crf(crf)
     beta = _check_temperature(temperature_beta, score_maps, crf)
+    bdist = None if boundary_scores is None else P.check_boundary_distances(boundary_scores)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
@@ -1106,6 +1150,9 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     all_f1 = np.zeros(len(testing_data), dtype=np.float32)
     all_f1_per_class = np.zeros(K, dtype=np.float32)
     maps = []
+    if bdist is not None:
+        all_bhist = np.zeros((len(bdist) + 1, len(bdist) + 1, K, K), dtype=np.int64)
+        boundary_list = []
     for k in range(len(testing_data)):
         pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
@@ -1140,6 +1187,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             cal_list.append(MT.calibration(hist))
             if comm.rank == 0:
                 print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _calibration_str(cal_list[-1]) + cal_tail)
+        if bdist is not None:
+            bhist = boundary_histogram(lab, pred, h, w, K, ignore_label, bdist, stream=net._stream()).cpu().numpy()
+            all_bhist += bhist
+            boundary_list.append(MT.boundary_scores(bhist, bdist))
+            if comm.rank == 0:
+                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _boundary_str(boundary_list[-1]))
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -1160,6 +1213,14 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         extra = {"scores": score_list, "reliability": all_hist, "calibration": cal}
         if beta is not None:
             extra["temperature_beta"] = beta
+    if bdist is not None:
+        bnd = MT.boundary_scores(all_bhist, bdist)
+        bnd["per_map"] = boundary_list
+        bnd["hist"] = all_bhist
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _boundary_str(bnd))
+        extra = dict(extra if kinds is not None else {}, boundary=bnd)
+    if kinds is not None or bdist is not None:
         return all_cm, maps, extra
     return all_cm, maps
 

@@ -34,6 +34,64 @@ def f1_macro(cm):
     return float(f1.mean()) if len(f1) else 0.0
 
 
+def iou_per_class(cm):
+    """(intersection over union of the classes present in the labels or the predictions, the presence mask): tp / (tp + fp + fn), the
+    presence rule of f1_per_class."""
+    cm = np.asarray(cm, dtype=np.float64)
+    tp = np.diag(cm)
+    union = cm.sum(axis=0) + cm.sum(axis=1) - tp
+    present = union > 0
+    return tp[present] / union[present], present
+
+
+def mean_iou(cm):
+    iou, _ = iou_per_class(cm)
+    return float(iou.mean()) if len(iou) else 0.0
+
+
+def boundary_scores(hist, distances):
+    """Boundary-quality scores from the table of drs_boundary_histogram (include/drs.h): hist [(n+1)][(n+1)][K][K]
+    integers, hist[bg][bp][t][p] = the counted pixels of truth class t predicted p whose distance bin is bg in the truth map and bp
+    in the prediction (bin i: within distances[i] of a pixel that carries another byte and not within distances[i - 1]; bin n:
+    further than the last).  Everything below is a sum over the table:
+      CM = sum over bg, bp                                  the plain confusion matrix (what drs_confusion gives)
+      trimap of d_i (Kohli et al. 2009)    T_i = sum over bg <= i and every bp: its pixel count, overall_and_normalized(T_i)
+      Boundary IoU of d_i and class c (Cheng et al. 2021)   I / (G + P - I) with I = sum over bg <= i, bp <= i of hist[bg][bp][c][c],
+          G = sum over bg <= i, every bp, every j of hist[bg][bp][c][j],  P = sum over bp <= i, every bg, every j of hist[bg][bp][j][c];
+          a class with G + P - I = 0 is absent, the mean is over the present classes (0.0 without any), as f1_per_class
+    Returns {"distances", "confusion", "iou_per_class" (K values, 0 for an absent class), "mean_iou", "bands": [{"d", "count",
+    "accuracy", "normalized_accuracy", "confusion", "boundary_iou_per_class" (K values, 0 for an absent class),
+    "boundary_iou_present", "boundary_iou"} per distance]}.  A table of another shape, of a non-integer dtype or with a negative
+    entry raises ValueError."""
+    h = np.asarray(hist)
+    n = len(distances)
+    if (h.ndim != 4 or h.shape[0] != n + 1 or h.shape[1] != n + 1 or h.shape[2] != h.shape[3] or h.shape[2] < 1
+            or not np.issubdtype(h.dtype, np.integer) or np.any(h < 0)):
+        raise ValueError("boundary table: expected [%d][%d][K][K] non-negative integers for the distances %r, not %s of shape %r"
+                         % (n + 1, n + 1, tuple(distances), h.dtype, h.shape))
+    h = h.astype(np.int64)
+    K = h.shape[2]
+    cm = h.sum(axis=(0, 1))
+    iou_full = np.zeros(K, dtype=np.float64)
+    iou, present = iou_per_class(cm)
+    iou_full[present] = iou
+    bands = []
+    for i, d in enumerate(distances):
+        t = h[:i + 1].sum(axis=(0, 1))
+        _, oa, na = overall_and_normalized(t)
+        inter = np.diagonal(h[:i + 1, :i + 1].sum(axis=(0, 1))).astype(np.float64)
+        g = h[:i + 1].sum(axis=(0, 1, 3)).astype(np.float64)
+        p = h[:, :i + 1].sum(axis=(0, 1, 2)).astype(np.float64)
+        union = g + p - inter
+        there = union > 0
+        biou = np.where(there, inter / np.where(there, union, 1.0), 0.0)
+        bands.append({"d": int(d), "count": int(t.sum()), "accuracy": float(oa), "normalized_accuracy": float(na), "confusion": t,
+                      "boundary_iou_per_class": biou, "boundary_iou_present": there,
+                      "boundary_iou": float(biou[there].mean()) if there.any() else 0.0})
+    return {"distances": tuple(int(d) for d in distances), "confusion": cm, "iou_per_class": iou_full, "mean_iou": mean_iou(cm),
+            "bands": bands}
+
+
 def cohen_kappa(cm):
     """sklearn cohen_kappa_score(y_true, y_pred) from the confusion matrix."""
     cm = np.asarray(cm, dtype=np.float64)

@@ -492,6 +492,39 @@ def parse_crf_params(text):
     return spec
 
 
+# ------------------------------------------------------------------- boundary-quality scores of validation
+BOUNDARY_DEFAULT = (1, 2, 4, 8)
+BOUNDARY_MAX_DISTANCES, BOUNDARY_MAX_REACH = 8, 16     # the ranges include/drs.h accepts
+
+
+def check_boundary_distances(v):
+    """The band distances of the boundary scores, in pixels, as a tuple of ints: 1 to 8 integers in 1..16, strictly ascending
+    (drs_boundary_histogram's).  Anything else raises ValueError naming the offending value."""
+    form = "1 to %d integers in 1..%d, strictly ascending" % (BOUNDARY_MAX_DISTANCES, BOUNDARY_MAX_REACH)
+    if isinstance(v, (str, bytes)) or not isinstance(v, (tuple, list, np.ndarray)) or not 1 <= len(v) <= BOUNDARY_MAX_DISTANCES:
+        raise ValueError("boundary distances %r: expected %s" % (v, form))
+    out = []
+    for d in v:
+        if not isinstance(d, (int, np.integer)) or isinstance(d, bool) or not 1 <= int(d) <= BOUNDARY_MAX_REACH:
+            raise ValueError("boundary distance %r of %r: expected %s" % (d, tuple(v), form))
+        if out and int(d) <= out[-1]:
+            raise ValueError("boundary distance %r of %r does not exceed the one before it: expected %s" % (d, tuple(v), form))
+        out.append(int(d))
+    return tuple(out)
+
+
+def parse_boundary_scores(text):
+    """The value of the command line's --boundary-scores option: "1,2,4,8" as a tuple of ints (check_boundary_distances).  An empty
+    value, blanks, or anything that is not a plain decimal integer raise ValueError."""
+    parts = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else []
+    for t in parts:
+        if not (t.isascii() and t.isdigit()):
+            raise ValueError("boundary distance %r of %r: expected integers, comma-separated (e.g. 1,2,4,8)" % (t, text))
+    if not parts:
+        raise ValueError("boundary distances %r: expected integers, comma-separated (e.g. 1,2,4,8)" % (text,))
+    return check_boundary_distances([int(t) for t in parts])
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

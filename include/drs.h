@@ -470,6 +470,31 @@ int drs_crf_step(const float* q_in, const float* logp, const unsigned int* live,
 /* multi-scale evaluation (isprs:1347-1474, softmax isprs:38-43): acc[h][w][K] += softmax_k(prob / max(occur, 1));
  * the label map of the summed scales is drs_stitch_finalize(acc, ones, ...). */
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream);
+/* boundary-quality counts of a (truth, prediction) pair of label maps (opt-in; csrc/boundary.hip): what trimap
+ * accuracy (Kohli et al., Robust higher order potentials, 2009) and Boundary IoU (Cheng et al., CVPR 2021) are sums of.  NORMATIVE:
+ * this text and the numpy statement tests/boundary_ref.py.
+ * Inputs: truth and pred are uint8 [h][w] on the device; K is the class count, 2 <= K <= 8; ignore_label is -1 for none;
+ *     d_0 < d_1 < ... < d_(n-1) are integer distances in pixels, 1 <= n <= 8, 1 <= d_i <= 16; the reach is R = d_(n-1).
+ * Distance field: for a byte map m and a pixel p = (y, x),
+ *         D2_m(p) = min { dy^2 + dx^2 : |dy| <= R, |dx| <= R, q = p + (dy, dx) inside the map, m[q] != m[p] },
+ *     infinite if there is no such q.  Integer arithmetic; nothing is rounded anywhere.  THE EDGE OF THE MAP IS NOT A BOUNDARY:
+ *     positions outside the map are never "different" (a mosaic tile cuts objects arbitrarily; Cheng et al.'s implementation pads with
+ *     background instead).  A byte is just a byte: in truth a pixel carrying ignore_label differs from every class pixel beside it (in
+ *     the ISPRS noBoundary ground truth label 6 is the eroded contour zone, so the distance of a class pixel is measured from the edge
+ *     of that zone); in pred, bytes >= K are likewise just different bytes.
+ * Bins: bin_m(p) = the smallest i with D2_m(p) <= d_i^2, or n if there is none.  Every pixel has a bin.
+ * Table: a pixel is counted exactly when drs_confusion counts it (truth != ignore_label, truth < K, pred < K); for every counted pixel
+ *         hist[bin_truth(p)][bin_pred(p)][truth[p]][pred[p]] += 1.
+ *     hist = [(n+1)][(n+1)][K][K] 64-bit counters on the device, ADDED to (integer atomics: exact and order-independent), so the maps
+ *     of a split accumulate over several calls.  The sum of the table over both bins is drs_confusion's matrix.
+ * drs_boundary_distance: d2[y][x] = min(D2_map(p), 65535) as uint16 (infinite -> 65535), R 1..16: the same device function as the
+ *     table's, so that a wrong distance field and a wrong count can be told apart.
+ * drs_boundary_histogram: the table; distances = n HOST ints.
+ * DRS_ERR_ARG (nothing is launched): a null pointer, h or w < 1, h w >= 2^40, K outside 2..8, n outside 1..8, distances that are not
+ * strictly ascending or lie outside 1..16, R outside 1..16. */
+int drs_boundary_distance(const unsigned char* map, int h, int w, int R, unsigned short* d2, void* stream);
+int drs_boundary_histogram(const unsigned char* truth, const unsigned char* pred, int h, int w, int K, int ignore_label,
+                           const int* distances, int n, unsigned long long* hist, void* stream);
 
 /* ==================================================================================================================
  * Step level: the reference's three `sess.run` call shapes (isprs:1750-1752 train, :1274-1275 infer, :1588 validate) as entry
