@@ -676,7 +676,6 @@ struct WgradArgs {
   int skip_halo;             // the walk jumps over the dead chunks (0: it multiplies their zeros -- same sums, bitwise)
   int live_cut;              // the live ranges shape the cut (plan) whether or not the walk skips
   int prio;                  // waves lower their priority as they advance (set_prio_by_progress)
-  int ablate;                // timing experiments only (libdrs_hip_dev.so): 1 = every tap reads the un-shifted pixels (wrong sums)
   float rcpS, rcpSS;
   WgradPlan plan;
 #ifdef DRS_DEV
@@ -788,6 +787,132 @@ struct ChunkWalk {
   }
 };
 
+// The parts both filter-gradient kernels (wgrad_kernel, wgrad_dma_kernel) are built from.  What stays in each kernel is what makes
+// the forms different: how a chunk's bytes get into LDS (gload / lstore against issue / zero_tail / chunk_bases / Seg), whether the
+// wave index is a scalar, and the main loop that orders those steps around its barriers.  The multiply phase over a staged image
+// is also written out in each kernel, although the two differ only in pixel count, row pitch and group stride: as one function it
+// is simplified before it is inlined, its LDS addresses become base + constant chains, and the register form then hoists an address
+// per pixel pair out of the K loop -- wgrad_kernel<128,64,true> / <64,128,true> 96 -> 105 VGPRs, a wave of occupancy lost
+// (profiles/wgrad_refactor/vgpr_before_after.txt).
+
+// What a workgroup knows at entry: its split and chunk range and the tile's live pixels (wgrad_assign, the same code
+// drs_debug_wgrad_cut runs on the host), the tile's corner, the padded sides of the two slabs and the ragged last chunk
+struct WgradTile {
+  int split, cbeg, cend, live_lo, live_hi;
+  int R0, o0;                // first row of the [k*k*Cin] dimension (a tile may span several taps, and the last one may be ragged:
+  int rows_all;              //  rows beyond k*k*Cin are not stored) and first output channel
+  int Sxp, Sgp;
+  int clast;                 // the one chunk that holds pixels past the end, if any (else -1)
+};
+
+__device__ __forceinline__ void wgrad_tile_enter(const WgradArgs& a, int TR, int TO, WgradTile& T) {
+#ifdef DRS_DEV
+  if (a.trace && threadIdx.x == 0) {
+    a.trace[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+    a.trace[32768 + blockIdx.x] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);   // HW_ID, XCC_ID
+  }
+#endif
+  int tile;
+  wgrad_assign(a, TR, xcd_remap(blockIdx.x, gridDim.x), tile, T.split, T.cbeg, T.cend, T.live_lo, T.live_hi);
+  T.R0 = (tile / a.nto) * TR;
+  T.o0 = (tile % a.nto) * TO;
+  T.rows_all = a.k * a.k * a.Cin;
+  T.Sxp = a.S + 2 * a.Px; T.Sgp = a.S + 2 * a.Pg;
+  T.clast = (a.M & 31) ? (a.M + 31) / 32 - 1 : -1;
+}
+
+__device__ __forceinline__ void wgrad_tile_exit(const WgradArgs& a) {
+#ifdef DRS_DEV
+  if (a.trace && threadIdx.x == 0) a.trace[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+
+// A thread always stages the same 4 rows (tap, c..c+3) of the tile, `row4` rows below its top: its tap shift and channel are a
+// per-thread constant of its X addresses (returned in floats).  Rows past the end: any valid address will do.
+__device__ __forceinline__ int wgrad_staged_rows_offset(const WgradArgs& a, const WgradTile& T, int row4) {
+  const int myR = T.R0 + row4;
+  const int myRc = myR < T.rows_all ? myR : 0;
+  const int tap = myRc / a.Cin, c0 = myRc % a.Cin;
+  const int u = tap / a.k, v = tap % a.k;
+  return (u * a.rate * T.Sxp + v * a.rate) * a.ld_x + a.coff_x + c0;
+}
+
+// S % 32 != 0, the table forms: a chunk crosses image rows, so its 32 pixels get a table of byte offsets, written by the first 32
+// threads.  A thread follows ITS pixel (py, px) through the walk: +32 pixels is a couple of compares; only a jump over dead rows
+// (once per image and tile) or a pixel past the end pays for the divisions.
+// The thread carries the BYTE OFFSETS of its pixel in the two slabs along with (py, px): +32 pixels is three additions, a row
+// wrap adds the slab's row jump, an image wrap its image jump -- compares, selects and additions only; the integer multiplies of
+// the offset formula (quarter rate) are paid once per jump.  (r04: the fills cost 3.5-5 % of a launch at S % 32 != 0 -- one wave
+// of four does them and the workgroup moves at its pace.)
+struct PixelTrack {
+  int py, px;
+  uint32_t ox, og;
+  uint32_t stepx, stepg, rowjx, rowjg, imgjx, imgjg;
+  __device__ __forceinline__ void init(const WgradArgs& a, const WgradTile& T) {
+    py = 0; px = 0; ox = 0; og = 0;
+    stepx = (uint32_t)(32 * a.ld_x) * 4u; stepg = (uint32_t)(32 * a.ld_g) * 4u;
+    rowjx = (uint32_t)((T.Sxp - a.S) * a.ld_x) * 4u; rowjg = (uint32_t)((T.Sgp - a.S) * a.ld_g) * 4u;
+    imgjx = (uint32_t)(T.Sxp * (T.Sxp - a.S) * a.ld_x) * 4u; imgjg = (uint32_t)(T.Sgp * (T.Sgp - a.S) * a.ld_g) * 4u;
+  }
+  __device__ __forceinline__ void set(const WgradArgs& a, const WgradTile& T, int p) {
+    int pb, rem;
+    divmod24(p < a.M ? p : a.M - 1, a.S * a.S, a.rcpSS, pb, rem);
+    divmod24(rem, a.S, a.rcpS, py, px);
+    ox = (uint32_t)(((pb * T.Sxp + py + a.Px - a.pad) * T.Sxp + px + a.Px - a.pad) * a.ld_x) * 4u;
+    og = (uint32_t)(((pb * T.Sgp + py + a.Pg) * T.Sgp + px + a.Pg) * a.ld_g) * 4u;
+  }
+  __device__ __forceinline__ void step32(const WgradArgs& a) {
+    px += 32; ox += stepx; og += stepg;
+    if (a.S >= 32) {                           // (uniform) at most one row wrap per 32 pixels
+      if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
+    }
+    if (py >= a.S) { py -= a.S; ox += imgjx; og += imgjg; }
+  }
+};
+
+// the table entries of thread t < 32 for chunk w.c; `stepped` = chunks the walk advanced since this thread's pixel was set
+__device__ __forceinline__ void wgrad_fill_tables(const WgradArgs& a, const WgradTile& T, const ChunkWalk& w, PixelTrack& trk, int t,
+                                                  int stepped, uint32_t (*tabx)[32], uint32_t (*tabg)[32], int slot) {
+  if (t >= 32 || w.c >= T.cend) return;
+  const int p = w.c * 32 + t;
+  if (stepped == 1 && p < a.M && a.S >= 11) trk.step32(a);
+  else if (stepped != 0) trk.set(a, T, p);
+  tabx[slot][t] = trk.ox;
+  tabg[slot][t] = trk.og;
+}
+
+template <int TMr, int TNo>
+__device__ __forceinline__ void wgrad_acc_zero(f32x16 (&acc)[TMr][TNo]) {
+#pragma unroll
+  for (int mi = 0; mi < TMr; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TNo; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+}
+
+// the tile's sums into this split's slab: the wave's 32-row group mi starts at row0 + mi * rstep, lane li's column of group ni is
+// gc + ni * cstep -- the map its kernel's multiply phase reads the fragments by
+template <int TMr, int TNo>
+__device__ __forceinline__ void wgrad_store_slab(const WgradArgs& a, const WgradTile& T, const f32x16 (&acc)[TMr][TNo], int h,
+                                                 int row0, int rstep, int gc, int cstep) {
+  const size_t rows_total = (size_t)a.k * a.k * a.Cin;
+  float* dst = a.slab + ((size_t)T.split * rows_total + T.R0) * a.Cout + T.o0;
+#pragma unroll
+  for (int mi = 0; mi < TMr; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < TNo; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = row0 + mi * rstep + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int col = gc + ni * cstep;
+        if (T.R0 + row < T.rows_all) dst[(size_t)row * a.Cout + col] = acc[mi][ni][r];
+      }
+}
+
 // The filter-gradient tile with a K loop that issues no vector-ALU instruction besides its MFMAs: VALU instructions of ANY
 // wave on a SIMD take issue slots from that SIMD's matrix pipe (measured on wgrad_kernel: removing its ~200 address / select
 // instructions per chunk raises the MFMA rate by 10-15 %).  Every global load is (wave-uniform base in SGPRs) + (32-bit byte
@@ -818,25 +943,10 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   const int li = lane & 31, h = lane >> 5;
   const int wr = wave / WC, wc = wave % WC;
 
-  int tile, split, cbeg, cend, live_lo, live_hi;
-#ifdef DRS_DEV
-  if (a.trace && t == 0) {
-    a.trace[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    a.trace[32768 + blockIdx.x] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);   // HW_ID, XCC_ID
-  }
-#endif
-  wgrad_assign(a, TR, xcd_remap(blockIdx.x, gridDim.x), tile, split, cbeg, cend, live_lo, live_hi);
-  const int R0 = (tile / a.nto) * TR;         // first row of the [k*k*Cin] dimension; a tile may span several taps
-  const int o0 = (tile % a.nto) * TO;         // and the last one may be ragged (rows beyond k*k*Cin are not stored)
-  const int rows_all = a.k * a.k * a.Cin;
-  // this thread always stages the same 4 rows (tap, c..c+3) of the tile: its tap shift is a per-thread constant
-  const int myR = R0 + (t % XQ) * 4;
-  const int myRc = myR < rows_all ? myR : 0;                 // rows past the end: any valid address will do
-  const int tap = myRc / a.Cin, c0 = myRc % a.Cin;
-  const int u = tap / a.k, v = tap % a.k;
-  const int Sxp = a.S + 2 * a.Px, Sgp = a.S + 2 * a.Pg;
-  const uint32_t xconst = (uint32_t)((u * a.rate * Sxp + v * a.rate) * a.ld_x + a.coff_x + c0) * 4u;
-  const uint32_t gconst = (uint32_t)(a.coff_g + o0 + (t % GQ) * 4) * 4u;
+  WgradTile T;
+  wgrad_tile_enter(a, TR, TO, T);
+  const uint32_t xconst = (uint32_t)wgrad_staged_rows_offset(a, T, (t % XQ) * 4) * 4u;
+  const uint32_t gconst = (uint32_t)(a.coff_g + T.o0 + (t % GQ) * 4) * 4u;
   const int xpix = t / XQ, gpix = t / GQ;
   constexpr bool affine = AFF;
   uint32_t xoff[NX], goff[NG];                // S % 32 == 0: the whole per-thread part of the address
@@ -846,56 +956,14 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   for (int i = 0; i < NG; ++i) goff[i] = gconst + (affine ? (uint32_t)((gpix + GPS * i) * a.ld_g) * 4u : 0u);
 
   f32x16 acc[TMr][TNo];
-#pragma unroll
-  for (int mi = 0; mi < TMr; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TNo; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  wgrad_acc_zero(acc);
 
-  const int nchunks_total = (a.M + BP - 1) / BP;
-  const int clast = (a.M & 31) ? nchunks_total - 1 : -1;     // the one chunk that holds pixels past the end, if any
   ChunkWalk w;
-  w.init(cbeg, a.S, a.rcpS, a.rcpSS, live_lo, live_hi);
-
-  // S % 32 != 0: a chunk crosses image rows, so its 32 pixels get a table of byte offsets, written by the first 32 threads.
-  // A thread follows ITS pixel (pb, py, px) through the walk: +32 pixels is a couple of compares; only a jump over dead rows
-  // (once per image and tile) or a pixel past the end pays for the divisions.
-  // The thread carries the BYTE OFFSETS of its pixel in the two slabs along with (py, px): +32 pixels is three additions, a row
-  // wrap adds the slab's row jump, an image wrap its image jump -- compares, selects and additions only; the integer multiplies of
-  // the offset formula (quarter rate) are paid once per jump.  (r04: the fills cost 3.5-5 % of a launch at S % 32 != 0 -- one wave
-  // of four does them and the workgroup moves at its pace.)
-  int py = 0, px = 0;
-  uint32_t ox = 0, og = 0;
-  const uint32_t stepx = (uint32_t)(32 * a.ld_x) * 4u, stepg = (uint32_t)(32 * a.ld_g) * 4u;
-  const uint32_t rowjx = (uint32_t)((Sxp - a.S) * a.ld_x) * 4u, rowjg = (uint32_t)((Sgp - a.S) * a.ld_g) * 4u;
-  const uint32_t imgjx = (uint32_t)(Sxp * (Sxp - a.S) * a.ld_x) * 4u, imgjg = (uint32_t)(Sgp * (Sgp - a.S) * a.ld_g) * 4u;
-  auto pixel_from_index = [&](int p) {
-    int pb, rem;
-    divmod24(p < a.M ? p : a.M - 1, w.S2, a.rcpSS, pb, rem);
-    divmod24(rem, a.S, a.rcpS, py, px);
-    ox = (uint32_t)(((pb * Sxp + py + a.Px - a.pad) * Sxp + px + a.Px - a.pad) * a.ld_x) * 4u;
-    og = (uint32_t)(((pb * Sgp + py + a.Pg) * Sgp + px + a.Pg) * a.ld_g) * 4u;
-  };
-  if (!affine && t < BP) pixel_from_index(w.c * BP + t);
-  auto fill_tables = [&](int slot, int stepped) {      // for chunk w.c; `stepped` = chunks the walk advanced since this thread's pixel was set
-    if (affine || t >= BP || w.c >= cend) return;
-    const int p = w.c * BP + t;
-    if (stepped == 1 && p < a.M && a.S >= 11) {
-      px += 32; ox += stepx; og += stepg;
-      if (a.S >= 32) {                           // (uniform) at most one row wrap per 32 pixels
-        if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
-      }
-      if (py >= a.S) { py -= a.S; ox += imgjx; og += imgjg; }
-    } else if (stepped != 0) {
-      pixel_from_index(p);
-    }
-    tabx[slot][t] = ox;
-    tabg[slot][t] = og;
-  };
+  w.init(T.cbeg, a.S, a.rcpS, a.rcpSS, T.live_lo, T.live_hi);
+  PixelTrack trk;
+  trk.init(a, T);
+  if (!affine && t < BP) trk.set(a, T, w.c * BP + t);
+  auto fill_tables = [&](int slot, int stepped) { if (!affine) wgrad_fill_tables(a, T, w, trk, t, stepped, tabx, tabg, slot); };
 
   const char* xbase = reinterpret_cast<const char*>(a.x);
   const char* gbase = reinterpret_cast<const char*>(a.g);
@@ -917,8 +985,8 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   };
   auto gload = [&]() {
     if (affine) {
-      const char* xb = xbase + (size_t)(uint32_t)(((w.b * Sxp + w.y + a.Px - a.pad) * Sxp + w.x0 + a.Px - a.pad) * a.ld_x) * 4u;
-      const char* gb = gbase + (size_t)(uint32_t)(((w.b * Sgp + w.y + a.Pg) * Sgp + w.x0 + a.Pg) * a.ld_g) * 4u;
+      const char* xb = xbase + (size_t)(uint32_t)(((w.b * T.Sxp + w.y + a.Px - a.pad) * T.Sxp + w.x0 + a.Px - a.pad) * a.ld_x) * 4u;
+      const char* gb = gbase + (size_t)(uint32_t)(((w.b * T.Sgp + w.y + a.Pg) * T.Sgp + w.x0 + a.Pg) * a.ld_g) * 4u;
 #pragma unroll
       for (int i = 0; i < NX; ++i) { uint32_t o = xoff[i]; asm volatile("" : "+v"(o)); rx[i] = *reinterpret_cast<const f32x4*>(xb + o); }
 #pragma unroll
@@ -933,7 +1001,7 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   auto lstore = [&](int chunk) {
 #pragma unroll
     for (int i = 0; i < NX; ++i) *reinterpret_cast<f32x4*>(&Xs[(xpix + XPS * i) * LDX + (t % XQ) * 4]) = rx[i];
-    if (!AFF && chunk == clast) {               // pixels past the end were loaded from a clamped address: their G rows are zero (S % 32 == 0: no such chunk)
+    if (!AFF && chunk == T.clast) {             // pixels past the end were loaded from a clamped address: their G rows are zero (S % 32 == 0: no such chunk)
 #pragma unroll
       for (int i = 0; i < NG; ++i)
         *reinterpret_cast<f32x4*>(&Gs[(gpix + GPS * i) * LDG + (t % GQ) * 4]) =
@@ -945,7 +1013,7 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   };
 
   int cA = w.c;                                  // chunk in LDS / being multiplied
-  if (cA < cend) {
+  if (cA < T.cend) {
     fill_tables(0, 0);
     __syncthreads();
     fetch_offsets(0);
@@ -958,12 +1026,9 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
     fetch_offsets(1);
     const int xr = wr * WTR + li, gc = wc * WTO + li;
     int quart = -1;
-    for (int it = 0; cA < cend; ++it) {
-      if (a.prio) set_prio_by_progress(cA - cbeg, cend - cbeg, quart, a.prio);
-#ifdef DRS_DEV
-      if (a.ablate == 2) fetch_offsets((it + 1) & 1);      // A/B arm: the table reads right in front of the loads, as before r04
-#endif
-      if (cB < cend) gload();                     // B: its offsets were fetched after the last barrier
+    for (int it = 0; cA < T.cend; ++it) {
+      if (a.prio) set_prio_by_progress(cA - T.cbeg, T.cend - T.cbeg, quart, a.prio);
+      if (cB < T.cend) gload();                   // B: its offsets were fetched after the last barrier
       stepped = w.advance();                      // ... and on C, whose table goes into the slot read two barriers ago
       fill_tables(it & 1, stepped);
       {
@@ -992,26 +1057,13 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
       }
       __syncthreads();
       fetch_offsets(it & 1);                      // C's table is published; the reads land under the stores below
-      if (cB < cend) { lstore(cB); __syncthreads(); }
+      if (cB < T.cend) { lstore(cB); __syncthreads(); }
       cA = cB;
       cB = w.c;
     }
   }
-  const size_t rows_total = (size_t)a.k * a.k * a.Cin;
-  float* dst = a.slab + ((size_t)split * rows_total + R0) * a.Cout + o0;
-#pragma unroll
-  for (int mi = 0; mi < TMr; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TNo; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wr * WTR + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int col = wc * WTO + ni * 32 + li;
-        if (R0 + row < rows_all) dst[(size_t)row * a.Cout + col] = acc[mi][ni][r];
-      }
-#ifdef DRS_DEV
-  if (a.trace && t == 0) a.trace[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
+  wgrad_store_slab(a, T, acc, h, wr * WTR, 32, wc * WTO + li, 32);
+  wgrad_tile_exit(a);
 }
 
 // The same tile with its operands brought in by LDS-DMA (global_load_lds_dwordx4: global memory -> LDS without passing through
@@ -1052,31 +1104,16 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   const int li = lane & 31, h = lane >> 5;
   const int wr = wave / WC, wc = wave % WC;
 
-  int tile, split, cbeg, cend, live_lo, live_hi;
-#ifdef DRS_DEV
-  if (a.trace && t == 0) {
-    a.trace[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    a.trace[32768 + blockIdx.x] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) | ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);   // HW_ID, XCC_ID
-  }
-#endif
-  wgrad_assign(a, TR, xcd_remap(blockIdx.x, gridDim.x), tile, split, cbeg, cend, live_lo, live_hi);
-  const int R0 = (tile / a.nto) * TR;
-  const int o0 = (tile % a.nto) * TO;
-  const int rows_all = a.k * a.k * a.Cin;
-  const int Sxp = a.S + 2 * a.Px, Sgp = a.S + 2 * a.Pg;
+  WgradTile T;
+  wgrad_tile_enter(a, TR, TO, T);
   constexpr bool affine = AFF || SEG;         // wave-uniform chunk bases + loop-invariant lane offsets
   // DMA lane roles: instruction i of this wave moves pieces 64 (wave + NW i) + lane of the linear image: piece f belongs to pixel
   // f / XQ, 16-byte column f % XQ.  (TR is a power of two, so the X column -- and with it the filter tap of the rows this lane
   // stages -- is the same for all of a lane's instructions; TO = 192 gives every instruction its own (pixel, column) pair.)
-  const int xq = lane % XQ;
-  const int myR = R0 + xq * 4;
-  const int myRc = myR < rows_all ? myR : 0;
-  const int tap = myRc / a.Cin, c0 = myRc % a.Cin;
-  const int u = tap / a.k, v = tap % a.k;
   // SEG: every lane offset carries a bias of 32 pixels' worth of bytes that the chunk bases take off again, so that the NEGATIVE jump of
   // the ragged last chunk (below) never takes a 32-bit lane offset below zero
   const uint32_t biasx = SEG ? (uint32_t)(32 * a.ld_x) * 4u : 0u, biasg = SEG ? (uint32_t)(32 * a.ld_g) * 4u : 0u;
-  const uint32_t xconst = (uint32_t)((a.ablate == 1 ? 0 : (u * a.rate * Sxp + v * a.rate)) * a.ld_x + a.coff_x + c0) * 4u + biasx;
+  const uint32_t xconst = (uint32_t)wgrad_staged_rows_offset(a, T, (lane % XQ) * 4) * 4u + biasx;
   uint32_t xoff[IX], goff[IG];
   int xpix[IX], gpix[IG];
 #pragma unroll
@@ -1088,57 +1125,18 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   for (int i = 0; i < IG; ++i) {
     const int f = 64 * (wave + NW * i) + lane;
     gpix[i] = f / GQ;
-    goff[i] = (uint32_t)(a.coff_g + o0 + (f % GQ) * 4) * 4u + (affine ? (uint32_t)(gpix[i] * a.ld_g) * 4u : 0u) + biasg;
+    goff[i] = (uint32_t)(a.coff_g + T.o0 + (f % GQ) * 4) * 4u + (affine ? (uint32_t)(gpix[i] * a.ld_g) * 4u : 0u) + biasg;
   }
 
   f32x16 acc[TMr][TNo];
-#pragma unroll
-  for (int mi = 0; mi < TMr; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TNo; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  wgrad_acc_zero(acc);
 
-  const int nchunks_total = (a.M + BP - 1) / BP;
-  const int clast = (a.M & 31) ? nchunks_total - 1 : -1;
   ChunkWalk w;
-  w.init(cbeg, a.S, a.rcpS, a.rcpSS, live_lo, live_hi);
-
-  // The thread carries the BYTE OFFSETS of its pixel in the two slabs along with (py, px): +32 pixels is three additions, a row
-  // wrap adds the slab's row jump, an image wrap its image jump -- compares, selects and additions only; the integer multiplies of
-  // the offset formula (quarter rate) are paid once per jump.  (r04: the fills cost 3.5-5 % of a launch at S % 32 != 0 -- one wave
-  // of four does them and the workgroup moves at its pace.)
-  int py = 0, px = 0;
-  uint32_t ox = 0, og = 0;
-  const uint32_t stepx = (uint32_t)(32 * a.ld_x) * 4u, stepg = (uint32_t)(32 * a.ld_g) * 4u;
-  const uint32_t rowjx = (uint32_t)((Sxp - a.S) * a.ld_x) * 4u, rowjg = (uint32_t)((Sgp - a.S) * a.ld_g) * 4u;
-  const uint32_t imgjx = (uint32_t)(Sxp * (Sxp - a.S) * a.ld_x) * 4u, imgjg = (uint32_t)(Sgp * (Sgp - a.S) * a.ld_g) * 4u;
-  auto pixel_from_index = [&](int p) {
-    int pb, rem;
-    divmod24(p < a.M ? p : a.M - 1, w.S2, a.rcpSS, pb, rem);
-    divmod24(rem, a.S, a.rcpS, py, px);
-    ox = (uint32_t)(((pb * Sxp + py + a.Px - a.pad) * Sxp + px + a.Px - a.pad) * a.ld_x) * 4u;
-    og = (uint32_t)(((pb * Sgp + py + a.Pg) * Sgp + px + a.Pg) * a.ld_g) * 4u;
-  };
-  if (!affine && t < BP) pixel_from_index(w.c * BP + t);
-  auto fill_tables = [&](int slot, int stepped) {
-    if (affine || t >= BP || w.c >= cend) return;
-    const int p = w.c * BP + t;
-    if (stepped == 1 && p < a.M && a.S >= 11) {
-      px += 32; ox += stepx; og += stepg;
-      if (a.S >= 32) {                           // (uniform) at most one row wrap per 32 pixels
-        if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) if (px >= a.S) { px -= a.S; ++py; ox += rowjx; og += rowjg; }
-      }
-      if (py >= a.S) { py -= a.S; ox += imgjx; og += imgjg; }
-    } else if (stepped != 0) {
-      pixel_from_index(p);
-    }
-    tabx[slot][t] = ox;
-    tabg[slot][t] = og;
-  };
+  w.init(T.cbeg, a.S, a.rcpS, a.rcpSS, T.live_lo, T.live_hi);
+  PixelTrack trk;                                // (SEG takes the row and image jumps from it, and nothing else)
+  trk.init(a, T);
+  if (!affine && t < BP) trk.set(a, T, w.c * BP + t);
+  auto fill_tables = [&](int slot, int stepped) { if (!affine) wgrad_fill_tables(a, T, w, trk, t, stepped, tabx, tabg, slot); };
 
   const char* xbase = reinterpret_cast<const char*>(a.x);
   const char* gbase = reinterpret_cast<const char*>(a.g);
@@ -1151,14 +1149,14 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   // are zeroed, zero_tail) -- the same mechanism, one more value of the jump.
   struct Seg { int brk; int32_t jx, jg; };
   auto chunk_bases = [&](const char*& xb, const char*& gb, Seg& sg) {
-    xb = xbase + (size_t)(uint32_t)(((w.b * Sxp + w.y + a.Px - a.pad) * Sxp + w.x0 + a.Px - a.pad) * a.ld_x) * 4u;
-    gb = gbase + (size_t)(uint32_t)(((w.b * Sgp + w.y + a.Pg) * Sgp + w.x0 + a.Pg) * a.ld_g) * 4u;
+    xb = xbase + (size_t)(uint32_t)(((w.b * T.Sxp + w.y + a.Px - a.pad) * T.Sxp + w.x0 + a.Px - a.pad) * a.ld_x) * 4u;
+    gb = gbase + (size_t)(uint32_t)(((w.b * T.Sgp + w.y + a.Pg) * T.Sgp + w.x0 + a.Pg) * a.ld_g) * 4u;
     if (SEG) {
       xb -= biasx; gb -= biasg;
       sg.brk = a.S - w.x0;
-      const bool last = w.c == clast, img_end = w.y == a.S - 1;
-      sg.jx = last ? -(int32_t)biasx : (int32_t)(rowjx + (img_end ? imgjx : 0u));
-      sg.jg = last ? -(int32_t)biasg : (int32_t)(rowjg + (img_end ? imgjg : 0u));
+      const bool last = w.c == T.clast, img_end = w.y == a.S - 1;
+      sg.jx = last ? -(int32_t)biasx : (int32_t)(trk.rowjx + (img_end ? trk.imgjx : 0u));
+      sg.jg = last ? -(int32_t)biasg : (int32_t)(trk.rowjg + (img_end ? trk.imgjg : 0u));
     }
   };
   // S % 32 != 0: a lane's byte offsets for the two halves of a chunk, table entry + lane constant, fetched into registers a phase
@@ -1224,7 +1222,7 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   // the zeros -- harmless-looking alone, a run-to-run difference as soon as another kernel shared the chip: tools/soak.py), and a
   // second barrier publishes the zeros before anybody multiplies.  `chunk` is uniform over the workgroup, so are the barriers.
   auto zero_tail = [&](int chunk, int half, int stage) {
-    if (AFF || chunk != clast) return;          // (S % 32 == 0: the pixel count is a multiple of 32, there is no such chunk)
+    if (AFF || chunk != T.clast) return;        // (S % 32 == 0: the pixel count is a multiple of 32, there is no such chunk)
     float* sg = lds + stage * STAGE + XSTAGE;
     for (int e = t; e < HP * TO; e += NT)
       if (chunk * BP + half * HP + e / TO >= a.M) sg[e] = 0.f;
@@ -1263,7 +1261,7 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
   };
 
   int cA = w.c;
-  if (cA < cend) {
+  if (cA < T.cend) {
     const char *xbA, *gbA, *xbB = xbase, *gbB = gbase;
     LaneOffsets oA, oB;
 #pragma unroll
@@ -1287,49 +1285,29 @@ __global__ __launch_bounds__(64 * (TR >= 64 ? 2 : 1) * (TO >= 64 ? 2 : 1), 3) vo
     __syncthreads();
     zero_tail(cA, 0, 0);
     int quart = -1;
-    for (int it = 0; cA < cend; ++it) {
-      if (a.prio) set_prio_by_progress(cA - cbeg, cend - cbeg, quart, a.prio);
-#ifdef DRS_DEV
-      const bool late = a.ablate == 2;           // A/B arm: the table reads where they used to be, right in front of each issue
-      if (late) fetch_offsets(it & 1, oA); else
-#endif
+    for (int it = 0; cA < T.cend; ++it) {
+      if (a.prio) set_prio_by_progress(cA - T.cbeg, T.cend - T.cbeg, quart, a.prio);
       fetch_offsets((it + 1) & 1, oB);           // B's table was published by the last barrier; its entries are used after compute(0)
       issue(xbA, gbA, sgA, oA, 1, 1);            // second half of A -> stage 1, lands while stage 0 is multiplied
       compute(0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       zero_tail(cA, 1, 1);
-#ifdef DRS_DEV
-      if (late) fetch_offsets((it + 1) & 1, oB);
-#endif
-      if (cB < cend) issue(xbB, gbB, sgB, oB, 0, 0);  // first half of B -> stage 0 (every wave is done with it)
+      if (cB < T.cend) issue(xbB, gbB, sgB, oB, 0, 0);  // first half of B -> stage 0 (every wave is done with it)
       stepped = w.advance();                     // ... and on C, whose table goes into the slot A's table was in
       compute(1);
       fill_tables(it & 1, stepped);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if (cB < cend) zero_tail(cB, 0, 0);
+      if (cB < T.cend) zero_tail(cB, 0, 0);
       cA = cB; xbA = xbB; gbA = gbB; sgA = sgB;
       oA = oB;
       cB = w.c;
       chunk_bases(xbB, gbB, sgB);
     }
   }
-  const size_t rows_total = (size_t)a.k * a.k * a.Cin;
-  float* dst = a.slab + ((size_t)split * rows_total + R0) * a.Cout + o0;
-#pragma unroll
-  for (int mi = 0; mi < TMr; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TNo; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = mi * XG + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const int col = ni * GG + wc * 32 + li;
-        if (R0 + row < rows_all) dst[(size_t)row * a.Cout + col] = acc[mi][ni][r];
-      }
-#ifdef DRS_DEV
-  if (a.trace && t == 0) a.trace[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
+  wgrad_store_slab(a, T, acc, h, wr * 32, XG, gc, GG);
+  wgrad_tile_exit(a);
 #endif
 }
 
@@ -1651,8 +1629,8 @@ int launch_conv(ConvArgs& a, float* ws, size_t ws_floats, hipStream_t st) {
 
 int g_wgrad_variant = -1;    // development switch (drs_debug_wgrad_variant): 0 = register-staged tiles, 1 = LDS-DMA double-buffered halves, -1 = per tile
 
-// the S % 32 == 0 form of wgrad_dma_kernel (development build, ablate 5: at any S -- a timing experiment with WRONG sums)
-inline bool wgrad_affine(const WgradArgs& a) { return (a.S & 31) == 0 || a.ablate == 5; }
+// the S % 32 == 0 form of wgrad_dma_kernel
+inline bool wgrad_affine(const WgradArgs& a) { return (a.S & 31) == 0; }
 // the table-free form of wgrad_dma_kernel for the other sides (r05): a 32-pixel chunk of a side >= 32 is at most two row segments.  The
 // lane offsets of that form are 32-bit byte offsets with a bias of 32 pixels: both slabs must leave that much room below 4 GiB
 int g_wgrad_seg = 1;         // development switch (drs_debug_wgrad_seg): 0 = the table form for every side that is not a multiple of 32
@@ -1734,11 +1712,8 @@ int g_wgrad_len = 0;        // development switch (drs_debug_wgrad_len): chunks 
 //  2.67 -> 2.35 ms), 256 -> 14.68; B = 128 at S = 75 / 85 and B = 64 at S = 100: 192 -0.4 .. -0.7 %; B = 64: 96 = 128, 192 +1.5 %)
 inline int wgrad_len(int nchunks) { return g_wgrad_len ? g_wgrad_len : (nchunks >= (1 << 14) ? 192 : 96); }
 int g_wgrad_minchunks = 8;  // development switch (drs_debug_wgrad_minchunks): fewest 32-pixel chunks a split may have
-int g_wgrad_target_big = 0;  // development switch: workgroups aimed at on launches with many tiles and pixels under the live cut (0 = default)
 
 int g_wgrad_prio = -1;       // development switch (drs_debug_wgrad_prio): -1 = by the rule in wgrad_setup, 0 = never, 1 = levels 3..0, 2 = levels 2..0
-int g_wgrad_ablate = 0;      // development switch (drs_debug_wgrad_ablate): timing experiments with wrong sums
-int g_wgrad_model = 1;       // development switch (drs_debug_wgrad_model): 1 = per-CU cost model for launches below the `big` class, 0 = the r02 table
 
 // workgroups a filter-gradient launch of `work` chunk-tiles (32-pixel chunks x tiles) aims at; occ = workgroups of this tile
 // shape a CU holds (4; the 128 x 192 tile: 3)
@@ -1755,30 +1730,23 @@ int wgrad_target(long long work, int ntile, int nchunks, bool balanced, int occ,
   // equal-length workgroups: the chip holds occ x 256 of them, and one workgroup over a whole number of rounds costs a round
   // (measured: 513 workgroups instead of 507 +27 %, 2049 instead of 2030 +7 %), so aim AT a whole number of workgroups per CU
   // (one round) or of rounds, and never above it (wgrad_live_plan rounds the splits down)
-  if (big) return g_wgrad_target_big ? g_wgrad_target_big : 3 * 1024;
-  if (g_wgrad_model) {
-    // n workgroups per CU, all resident: a CU's time ~ (its chunks + n * o) / eff(n), o = what a workgroup costs besides its
-    // chunks (assignment, pipeline fill, the 64 KB slab tile: ~6 chunks' worth), eff(n) = share of the MFMA rate n co-resident
-    // workgroups reach (1: 0.75, 2: 0.88, 3: 0.93, 4: 0.95: the barrier bubbles of one are filled by the others).  Sweeps at
-    // B = 16, S = 25 .. 85: profiles/r03/ab_wgrad_small.log.  Longer than g_wgrad_len chunks per workgroup: whole further rounds.
-    static const double eff[5] = {1.0, 0.75, 0.88, 0.93, 0.95};
-    const double W0 = (double)work / (double)cu_count(), o = 6.0;
-    int n = 1;
-    double bt = 1e30;
-    for (int i = 1; i <= occ && i <= 4; ++i) {
-      const double t = (W0 + i * o) / eff[i];
-      if (t < bt) { bt = t; n = i; }
-    }
-    int r = (int)(W0 / n / (double)len + 0.5);
-    r = r < 1 ? 1 : r;
-    const long long t = (long long)cu_count() * n * r;
-    return (int)(t > 4096 ? 4096 : t);
+  if (big) return 3 * 1024;
+  // n workgroups per CU, all resident: a CU's time ~ (its chunks + n * o) / eff(n), o = what a workgroup costs besides its
+  // chunks (assignment, pipeline fill, the 64 KB slab tile: ~6 chunks' worth), eff(n) = share of the MFMA rate n co-resident
+  // workgroups reach (1: 0.75, 2: 0.88, 3: 0.93, 4: 0.95: the barrier bubbles of one are filled by the others).  Sweeps at
+  // B = 16, S = 25 .. 85: profiles/r03/ab_wgrad_small.log.  Longer than g_wgrad_len chunks per workgroup: whole further rounds.
+  static const double eff[5] = {1.0, 0.75, 0.88, 0.93, 0.95};
+  const double W0 = (double)work / (double)cu_count(), o = 6.0;
+  int n = 1;
+  double bt = 1e30;
+  for (int i = 1; i <= occ && i <= 4; ++i) {
+    const double t = (W0 + i * o) / eff[i];
+    if (t < bt) { bt = t; n = i; }
   }
-  static const int steps[] = {512, 768, 1024, 2048, 3072, 4096};
-  int best = steps[0];
-  for (int s : steps)
-    if (s <= g_wgrad_target && (double)(s > fit ? s : fit) / (s > fit ? fit : s) < (double)(best > fit ? best : fit) / (best > fit ? fit : best)) best = s;
-  return best;
+  int r = (int)(W0 / n / (double)len + 0.5);
+  r = r < 1 ? 1 : r;
+  const long long t = (long long)cu_count() * n * r;
+  return (int)(t > 4096 ? 4096 : t);
 }
 
 // equal chunk ranges: the number of splits.  Never less than g_wgrad_minchunks chunks per split.
@@ -1892,11 +1860,10 @@ int wgrad_setup(int B, int S, int k, int rate, int pad_before, int cin, int cout
   const int nchunks = (int)((M + 31) / 32);
   a.chunks_per_split = (nchunks + nsplit - 1) / nsplit;
   a.rcpS = 1.0f / (float)S; a.rcpSS = 1.0f / (float)(S * S);
-  a.ablate = g_wgrad_ablate;
   // priority by remaining work: only where the filter gradient has the chip to itself.  Below 2^18 pixels the step engine runs it on a
   // stream of its own BESIDE the batch-norm-backward -> input-gradient chain (engine.hip), and raised priorities there take the matrix
   // pipe from the chain that the step waits for (B = 16: 6.87 -> 6.94 ms with them on)
-  a.prio = g_wgrad_prio >= 0 ? g_wgrad_prio : ((g_wgrad_ablate != 3 && M >= (1LL << 18)) ? 1 : 0);
+  a.prio = g_wgrad_prio >= 0 ? g_wgrad_prio : (M >= (1LL << 18) ? 1 : 0);
 #ifdef DRS_DEV
   a.trace = g_conv_trace;
 #endif
@@ -1943,13 +1910,7 @@ int drs_debug_wgrad_len(int v) { const int old = g_wgrad_len; if (v >= 0) g_wgra
 
 int drs_debug_wgrad_minchunks(int v) { const int old = g_wgrad_minchunks; if (v > 0) g_wgrad_minchunks = v; return old; }
 
-int drs_debug_wgrad_model(int v) { const int old = g_wgrad_model; if (v >= 0) g_wgrad_model = v; return old; }
-
 int drs_debug_wgrad_prio(int v) { const int old = g_wgrad_prio; if (v >= -1) g_wgrad_prio = v; return old; }
-
-int drs_debug_wgrad_ablate(int v) { const int old = g_wgrad_ablate; if (v >= 0) g_wgrad_ablate = v; return old; }
-
-int drs_debug_wgrad_target_big(int v) { const int old = g_wgrad_target_big; if (v >= 0) g_wgrad_target_big = v; return old; }
 
 int drs_debug_conv_wide192(int v) { const int old = g_conv_wide192; if (v >= 0) g_conv_wide192 = v; return old; }
 

@@ -30,12 +30,9 @@ int drs_debug_wgrad_variant(int v);      /* filter gradient: 0 register-staged, 
 int drs_debug_wgrad_seg(int v);          /* filter gradient, LDS-DMA form, sides >= 32 that are not a multiple of 32: 1 row-segment addressing without tables (default), 0 the table form */
 int drs_debug_wgrad_balance(int v);      /* 1 cut the pixel dimension by live pixels (default), 0 equal chunk ranges */
 int drs_debug_wgrad_target(int v);       /* workgroups the pixel split aims at (default 2048) */
-int drs_debug_wgrad_target_big(int v);   /* the same on launches with many tiles and pixels (0 = default rule) */
 int drs_debug_wgrad_len(int v);          /* chunks per workgroup the launches below the `big` class aim at (0 = default: 96, from 2^14 chunks 192) */
 int drs_debug_wgrad_minchunks(int v);    /* fewest 32-pixel chunks a split of the pixel dimension may have (default 8) */
 int drs_debug_wgrad_prio(int v);         /* filter gradient, wave priority by remaining work: -1 by the rule (default), 0 never, 1 levels 3..0, 2 levels 2..0 */
-int drs_debug_wgrad_ablate(int v);       /* 1 = timing experiment (WRONG sums): every filter tap reads the un-shifted pixels (perfect X re-use); 2 = the S % 32 != 0 table reads of wgrad_dma_kernel right in front of each DMA issue, as before r04 (same sums); 3 = no wave priority by remaining work (same sums) */
-int drs_debug_wgrad_model(int v);        /* 1 per-CU cost model for the workgroup count of launches below the `big` class (default), 0 the r02 table */
 int drs_debug_slide_blocks(int v);       /* sliding elementwise kernels: workgroups the row-strip split aims at (default 5120) */
 int drs_debug_slide_minrows(int v);      /* ... and the fewest rows of a strip in that first split (default 8) */
 int drs_debug_jitter(unsigned long long seed);   /* schedule fuzzing of the two-stream training step: != 0 = sleeps of 0 .. 150 us (a generator seeded with it) on the step's streams where they hand work to each other; 0 = off */

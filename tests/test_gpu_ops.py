@@ -571,15 +571,31 @@ def test_register_staged_and_lds_dma_kernel_forms_are_bitwise_equal(lib, k, rate
     assert torch.equal(out, res[1][0]) and torch.equal(stats, res[1][1]) and torch.equal(gw, res[1][2])
 
 
-@pytest.mark.parametrize("S,B", [(5, 3), (8, 5), (10, 2), (11, 3), (12, 2), (16, 3), (31, 1), (32, 2), (33, 1), (48, 1), (63, 1), (96, 1),
-                                 (33, 3), (37, 3), (45, 2), (65, 2), (85, 1), (100, 1)])
-def test_filter_gradient_chunk_walk_over_patch_sides(lib, S, B):
+# (k, cin, cout) -> (tile rows, tile columns): one shape per tile drs_conv_wgrad dispatches besides the 128 x 128 of (3, 64, 128), each
+# at four sides: 9 (division path, ragged last chunk), 21 (incremental tables below 32, ragged), 32 (affine), 45 (segments and tables, ragged)
+WGRAD_TILE_SHAPES = {(3, 64, 192): (128, 192), (3, 64, 64): (128, 64), (3, 64, 96): (128, 32),
+                     (1, 64, 128): (64, 128), (1, 64, 64): (64, 64), (2, 16, 96): (64, 32),
+                     (1, 96, 128): (32, 128), (1, 32, 64): (32, 64), (1, 96, 96): (32, 32)}
+
+
+@pytest.mark.parametrize("S,B,shape", [pytest.param(S, B, (3, 64, 128), id="%d-%d" % (S, B)) for S, B in
+                                       [(5, 3), (8, 5), (10, 2), (11, 3), (12, 2), (16, 3), (31, 1), (32, 2), (33, 1), (48, 1), (63, 1), (96, 1),
+                                        (33, 3), (37, 3), (45, 2), (65, 2), (85, 1), (100, 1)]] +
+                         [pytest.param(S, B, kcc, id="%d-%d-k%d-%d-%d-tile%dx%d" % ((S, B) + kcc + tile)) for kcc, tile in WGRAD_TILE_SHAPES.items()
+                          for S, B in [(9, 3), (21, 2), (32, 2), (45, 1)]])
+def test_filter_gradient_chunk_walk_over_patch_sides(lib, S, B, shape):
     """The filter-gradient kernels walk 32-pixel chunks with a scalar state machine (ChunkWalk) and, when the patch side is not a
     multiple of 32, per-pixel offset tables that each thread advances incrementally (below 11 pixels a side: by division).  Every
     regime -- sides below 11, not / exactly a multiple of 32, chunks spanning several rows or images, a ragged last chunk -- against
     the fp64 oracle, in both kernel forms and with the all-halo chunks skipped or not, which must also agree bit for bit."""
     lib = lib.dev()          # libdrs_hip_dev.so: the same sources + the A/B switches of include/drs_dev.h
-    k, rate, cin, cout = 3, 2, 64, 128
+    (k, cin, cout), rate = shape, 2
+    if shape in WGRAD_TILE_SHAPES:      # the tile the row is there for, by the library's own cut
+        import ctypes
+        cap, tr = 1 << 16, ctypes.c_int(0)
+        cut = np.zeros(5 * cap, dtype=np.int32)
+        n = lib.drs_debug_wgrad_cut(B, S, k, rate, onets.same_pad(k, rate)[0], cin, cout, cut.ctypes.data, cap, None, ctypes.addressof(tr))
+        assert 0 < n <= cap and (tr.value, cout // (int(cut[1:5 * n:5].max()) + 1)) == WGRAD_TILE_SHAPES[shape]
     rng = np.random.default_rng(S * 31 + B)
     x = rng.normal(size=(B, S, S, cin)).astype(np.float32)
     g = rng.normal(size=(B, S, S, cout)).astype(np.float32)

@@ -1,13 +1,11 @@
 #!/usr/bin/env python3
 """In-process A/B of the filter-gradient launch policy on the Dilated8Pooling shapes (development aid): interleaved repetitions on
 one device, best-of per arm.  An arm is a string of development-switch settings: b<0|1> cut by live pixels off / on
-(drs_debug_wgrad_balance), t<N> workgroup target (drs_debug_wgrad_target), g<N> target of the many-tiles-and-pixels launches under
-the live cut (drs_debug_wgrad_target_big), v<0|1> kernel form (drs_debug_wgrad_variant; default per tile), l<N> chunks per workgroup that small launches aim at,
-m<N> fewest chunks a split may have (drs_debug_wgrad_minchunks), o<0|1> workgroup count by the r02 table / the per-CU cost model,
-a<0|1> timing experiment with WRONG sums: every tap reads the un-shifted pixels (what perfect re-use of X across tap rows would buy),
+(drs_debug_wgrad_balance), t<N> workgroup target (drs_debug_wgrad_target), v<0|1> kernel form (drs_debug_wgrad_variant; default per tile), l<N> chunks per workgroup that small launches aim at,
+m<N> fewest chunks a split may have (drs_debug_wgrad_minchunks),
 s<0|1> sides >= 32 that are not a multiple of 32 in the LDS-DMA form: the r04 offset tables / row-segment addressing (drs_debug_wgrad_seg).
 S may be a list (S=63,64,65): one table per side with ms per 10^6 pixels, for comparing sides at equal pixels.
-    python tools/ab_wgrad.py [B=128] [S=64] [arms=b0,b1,b1g2048] [layers=1,2,...] [rounds=4]"""
+    python tools/ab_wgrad.py [B=128] [S=64] [arms=b0,b1,b1t1024] [layers=1,2,...] [rounds=4]"""
 import os, re, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,15 +16,12 @@ DEV = "cuda:0"
 
 
 def apply(lib, arm):
-    kv = dict((m.group(1), int(m.group(2))) for m in re.finditer(r"([btgvlmoasp])(\d+)", arm))
+    kv = dict((m.group(1), int(m.group(2))) for m in re.finditer(r"([btvlmsp])(\d+)", arm))
     lib.drs_debug_wgrad_balance(kv.get("b", 1))
     lib.drs_debug_wgrad_target(kv.get("t", 2048))
-    lib.drs_debug_wgrad_target_big(kv.get("g", 0))
     lib.drs_debug_wgrad_variant(kv.get("v", -1))
     lib.drs_debug_wgrad_len(kv.get("l", 0))
     lib.drs_debug_wgrad_minchunks(kv.get("m", 8))
-    lib.drs_debug_wgrad_model(kv.get("o", 1))
-    lib.drs_debug_wgrad_ablate(kv.get("a", 0))
     lib.drs_debug_wgrad_seg(kv.get("s", 1))
     lib.drs_debug_wgrad_prio(kv.get("p", -1))      # p<0|1|2>: wave priority by remaining work never / levels 3..0 / levels 2..0 (default: by the rule)
 
