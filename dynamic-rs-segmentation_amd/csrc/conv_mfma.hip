@@ -1998,7 +1998,7 @@ int drs_conv_halo_skip(int B, int S, int k, int rate, int pad_before, int cin, i
 // (drs_conv_halo_skip), tap rows and columns of image tiles.  Follows the library's own rules; 0 on success.
 int drs_conv_executed_ksteps(int B, int S, int k, int rate, int pad_before, int cin, int cout, long long* executed, long long* total) {
   const long long M = (long long)B * S * S;
-  if (M <= 0 || M >= (1 << 24) || cout % 32 || cin < 1 || k < 1 || rate < 1 || !executed || !total) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || M >= (1 << 24) || cout < 32 || cout % 32 || cin < 1 || k < 1 || rate < 1 || !executed || !total) return DRS_ERR_ARG;
   const int bn = pick_conv_tile(cout, cin), bm = bn >= 64 ? 128 : 256;
   const int mt = (int)((M + bm - 1) / bm), nt = cout / bn;
   const long long cpt = cin < 32 ? 1 : cin / 32;
@@ -2030,9 +2030,11 @@ int drs_conv_forward_ws(const float* in, int B, int S, int P, int ld_in, int cof
                         int accumulate, float* stats_partial, float* workspace, size_t workspace_floats, void* stream) {
   // cin: a multiple of 32, or 8 / 16 (few-band input: several taps share a K-step; w then has round_up(k*k*cin, 32) rows)
   if (!in || !w || !out || (cin % 32 && cin != 8 && cin != 16) || cout % 32 || k < 1 || rate < 1 || P < pad_before) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || cin < 8 || cout < 32 || pad_before < 0 || !drs_prod_below(1LL << 31, {k, k, cin, cout})) return DRS_ERR_ARG;
+  if (coff_in < 0 || ld_in < coff_in + cin || coff_out < 0 || ld_out < coff_out + cout) return DRS_ERR_ARG;     // the slices lie inside their rows
   if (cin < 32 && (ld_in % 4 || coff_in % 4)) return DRS_ERR_ARG;
   if (accumulate && stats_partial) return DRS_ERR_ARG;              // the tile statistics are those of this call's own sums
-  if (P < (k - 1) * rate - pad_before) return DRS_ERR_ARG;          // halo must cover pad_after too
+  if (P < (long long)(k - 1) * rate - pad_before) return DRS_ERR_ARG;          // halo must cover pad_after too
   const long long M = (long long)B * S * S;
   if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
   if ((long long)B * (S + 2 * P) * (S + 2 * P) * ld_in >= (1LL << 30)) return DRS_ERR_ARG;      // 32-bit BYTE offsets (slab < 4 GiB)
@@ -2093,7 +2095,13 @@ int drs_debug_wgrad_cut(int B, int S, int k, int rate, int pad_before, int cin, 
 int drs_conv_wgrad(const float* x, int B, int S, int Px, int ld_x, int coff_x, const float* g, int Pg, int ld_g,
                    int coff_g, int k, int rate, int pad_before, int cin, int cin_real, int cout, float* slab,
                    float* grad, void* stream) {
-  if (!x || !g || !slab || !grad || cin_real > cin) return DRS_ERR_ARG;
+  if (!x || !g || !slab || !grad || cin_real < 1 || cin_real > cin) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || k < 1 || rate < 1 || cin < 8 || cout < 32 || pad_before < 0 || Pg < 0) return DRS_ERR_ARG;
+  if (!drs_prod_below(1LL << 31, {k, k, cin, cout})) return DRS_ERR_ARG;
+  // the halo of x covers both pads, as in drs_conv_forward: the pixel address (.. + Px - pad) * ld_x is formed in 32 bits and a short halo wraps it
+  if (Px < pad_before || Px < (long long)(k - 1) * rate - pad_before) return DRS_ERR_ARG;
+  if (coff_x < 0 || ld_x < coff_x + cin || coff_g < 0 || ld_g < coff_g + cout) return DRS_ERR_ARG;
+  if (cin < 32 && (ld_x % 4 || coff_x % 4)) return DRS_ERR_ARG;
   if ((long long)B * (S + 2 * Px) * (S + 2 * Px) * ld_x >= (1LL << 30)) return DRS_ERR_ARG;     // 32-bit BYTE offsets (slabs < 4 GiB)
   if ((long long)B * (S + 2 * Pg) * (S + 2 * Pg) * ld_g >= (1LL << 30)) return DRS_ERR_ARG;
   WgradArgs a;
@@ -2121,7 +2129,7 @@ int drs_conv_wgrad(const float* x, int B, int S, int Px, int ld_x, int coff_x, c
 }
 
 int drs_filter_flip_transpose(const float* w, float* wt, int k, int cin, int cout, void* stream) {
-  if (!w || !wt) return DRS_ERR_ARG;
+  if (!w || !wt || k < 1 || cin < 1 || cout < 1 || !drs_prod_below(1LL << 31, {k, k, cin, cout})) return DRS_ERR_ARG;
   const int n = k * k * cin * cout;
   DRS_LAUNCH(flip_transpose_kernel, dim3((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048), dim3(256), 0,
                      (hipStream_t)stream, w, wt, k, cin, cout);
@@ -2129,7 +2137,7 @@ int drs_filter_flip_transpose(const float* w, float* wt, int k, int cin, int cou
 }
 
 int drs_filter_pad_cin(const float* w, float* wp, int k, int cin, int cin_pad, int cout, void* stream) {
-  if (!w || !wp || cin_pad < cin) return DRS_ERR_ARG;
+  if (!w || !wp || k < 1 || cin < 1 || cout < 1 || cin_pad < cin || !drs_prod_below(1LL << 31, {k, k, cin_pad, cout})) return DRS_ERR_ARG;
   const int n = k * k * cin_pad * cout;
   DRS_LAUNCH(pad_cin_kernel, dim3((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048), dim3(256), 0,
                      (hipStream_t)stream, w, wp, k * k, cin, cin_pad, cout);

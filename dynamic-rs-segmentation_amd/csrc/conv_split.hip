@@ -1313,6 +1313,7 @@ int drs_split_terms(const float* src, size_t n, int nterms, unsigned short* term
 int drs_filter_split(const float* w, int k, int cin, int cin_pad, int cout, int nsplit, unsigned short* wf,
                      unsigned short* wd, void* stream) {
   if (!w || !wf || cin_pad < cin || cin_pad % 32 || cout % 32 || (nsplit != 2 && nsplit != 3)) return DRS_ERR_ARG;
+  if (k < 1 || cin < 1 || cout < 32 || !drs_prod_below(1LL << 31, {k, k, cin_pad, cout, nsplit})) return DRS_ERR_ARG;
   if (wd && cin % 32) return DRS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)k * k * cout * (cin_pad + (wd ? cin : 0));
@@ -1327,6 +1328,9 @@ int drs_conv_forward_split(const unsigned short* in, int B, int S, int P, int ld
   if (!in || !w || !out || cin % 32 || cout % 64 || k < 1 || rate < 1 || P < pad_before) return DRS_ERR_ARG;
   if (P < (k - 1) * rate - pad_before || (ld_in & 31) || (coff_in & 31) || (nsplit != 2 && nsplit != 3)) return DRS_ERR_ARG;
   if (accumulate && stats_partial) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || cin < 32 || cout < 64 || pad_before < 0 || P < (long long)(k - 1) * rate - pad_before) return DRS_ERR_ARG;
+  if (!drs_slice_ok(ld_in, coff_in, cin, 32) || coff_out < 0 || (long long)coff_out + cout > ld_out) return DRS_ERR_ARG;
+  if (!drs_prod_below(1LL << 31, {k, k, cin, cout, nsplit})) return DRS_ERR_ARG;
   const long long M = (long long)B * S * S;
   if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
   // the kernels address with 32-bit element offsets: the whole term image of the input slab and the filter must stay below 2^32
@@ -1373,6 +1377,11 @@ int drs_conv_wgrad_split(const unsigned short* x, int B, int S, int Px, int ld_x
                          float* slab, float* grad, int nsplit_terms, void* stream) {
   if (!x || !g || !slab || !grad || cin % 32 || cout % 64 || cin_real > cin) return DRS_ERR_ARG;
   if ((ld_x & 31) || (coff_x & 31) || (ld_g & 31) || (coff_g & 31) || (nsplit_terms != 2 && nsplit_terms != 3)) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || k < 1 || rate < 1 || cin < 32 || cout < 64 || cin_real < 1 || pad_before < 0 || Pg < 0) return DRS_ERR_ARG;
+  // the halo of x covers both pads, as in drs_conv_forward_split: a short one wraps the 32-bit pixel address
+  if (Px < pad_before || Px < (long long)(k - 1) * rate - pad_before) return DRS_ERR_ARG;
+  if (!drs_slice_ok(ld_x, coff_x, cin, 32) || !drs_slice_ok(ld_g, coff_g, cout, 32)) return DRS_ERR_ARG;
+  if (!drs_prod_below(1LL << 31, {k, k, cin, cout})) return DRS_ERR_ARG;
   const long long M = (long long)B * S * S;
   if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
   if ((long long)B * (S + 2 * Px) * (S + 2 * Px) * ld_x * nsplit_terms >= (1LL << 32)) return DRS_ERR_ARG;   // 32-bit element offsets

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 #define DRS_OK 0
 #define DRS_ERR_ARG 1
@@ -222,6 +223,28 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
   const int xcd = bid & 7, q = nblk >> 3, r = nblk & 7;
   const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   return start + (bid >> 3);
+}
+
+// Host-side argument checks of the entry points (include/drs.h states each domain; a wrapper rejects everything outside it with
+// DRS_ERR_ARG before its first HIP call).
+// every factor is >= 1 and the product stays below lim (no overflow on the way)
+static inline bool drs_prod_below(long long lim, std::initializer_list<long long> f) {
+  long long p = 1;
+  for (long long v : f) {
+    if (v < 1 || v >= lim) return false;
+    p *= v;                       // p, v < lim <= 2^31 where this is used: below 2^62
+    if (p >= lim) return false;
+  }
+  return true;
+}
+// the channel slice [coff, coff + C) lies inside a pixel row of ld floats; align: the kernel moves that many floats at a time
+// (4 = 16-byte vector accesses, 32 = the granularity of the split-bf16 term layout), so ld and coff are multiples of it
+static inline bool drs_slice_ok(int ld, int coff, int C, int align) {
+  return C >= 1 && coff >= 0 && (long long)coff + C <= ld && ld % align == 0 && coff % align == 0;
+}
+// a patch batch whose haloed rows index the y dimension of a grid: B, S >= 1, P >= 0, B * (S + 2P) <= 65535
+static inline bool drs_rows_ok(int B, int S, int P) {
+  return B >= 1 && S >= 1 && P >= 0 && (long long)B * ((long long)S + 2LL * P) <= 65535;
 }
 
 static inline int drs_check(hipError_t e) { return e == hipSuccess ? DRS_OK : DRS_ERR_HIP; }

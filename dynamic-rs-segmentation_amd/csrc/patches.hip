@@ -701,10 +701,9 @@ int launch_crop_tiles(const void* tiles, int tiles_are_f64, const long long* til
                       const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
                       float* out, void* stream) {
   if (!tiles || !tile_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
-  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || B < 1 || T < 1 || P < 0) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || g < 0 || g > 7 || !drs_rows_ok(B, T, P)) return DRS_ERR_ARG;
   if (RESAMPLE && (hs < 1 || ws < 1)) return DRS_ERR_ARG;
   const int Tp2 = T + 2 * P;
-  if ((long long)B * Tp2 > 65535) return DRS_ERR_ARG;
   CropTilesArgs a;
   a.tiles = tiles; a.tile_off = tile_off; a.tile_h = tile_h; a.tile_w = tile_w; a.n_maps = n_maps; a.C = C; a.inst = inst;
   a.hs = hs; a.ws = ws; a.g = g;
@@ -754,9 +753,9 @@ int drs_crop_normalize(const void* tiles, int tiles_are_f64, const unsigned char
                        unsigned long long seed, int noise_index0, const double* mean3, const double* std3, int B, int S, int P, int ld,
                        float* out, unsigned char* out_lab, unsigned char* out_mask, int void_label, int quantize_f16, void* stream) {
   if (!tiles || !labels || !tile_off || !lab_off || !tile_h || !tile_w || !inst || !out || !mean3 || !std3) return DRS_ERR_ARG;
-  if (C < 1 || C > 8 || ld < C || ld % 4) return DRS_ERR_ARG;
+  if (C < 1 || C > 8 || ld < C || ld % 4 || !drs_rows_ok(B, S, P) || noise_index0 < 0) return DRS_ERR_ARG;
+  if (quantize_f16 < 0 || quantize_f16 > 2) return DRS_ERR_ARG;
   const int Sp = S + 2 * P;
-  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
   CropArgs a;
   a.tiles = tiles; a.labels = labels; a.tile_off = tile_off; a.lab_off = lab_off; a.tile_h = tile_h; a.tile_w = tile_w; a.C = C;
   a.inst = inst; a.rot = rot; a.rot_on = rot ? rot_on : nullptr; a.noise = noise; a.noise_on = noise_on; a.seed = seed; a.b0 = noise_index0; a.void_label = void_label; a.quantize_f16 = quantize_f16;
@@ -775,9 +774,9 @@ int drs_crop_normalize_scaled(const void* tiles, int tiles_are_f64, const unsign
                               const double* std3, int B, int S, int P, int ld, float* out, unsigned char* out_lab,
                               unsigned char* out_mask, int void_label, int quantize_f16, void* stream) {
   if (!tiles || !labels || !tile_off || !lab_off || !tile_h || !tile_w || !inst || !geo || !out || !mean3 || !std3) return DRS_ERR_ARG;
-  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || B < 1 || S < 1 || P < 0) return DRS_ERR_ARG;
+  if (n_maps < 1 || C < 1 || C > 8 || ld < C || ld % 4 || !drs_rows_ok(B, S, P) || noise_index0 < 0) return DRS_ERR_ARG;
+  if (quantize_f16 < 0 || quantize_f16 > 2) return DRS_ERR_ARG;
   const int Sp = S + 2 * P;
-  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
   CropArgs a;
   a.tiles = tiles; a.labels = labels; a.tile_off = tile_off; a.lab_off = lab_off; a.tile_h = tile_h; a.tile_w = tile_w; a.C = C;
   a.inst = inst; a.rot = rot; a.rot_on = rot ? rot_on : nullptr; a.noise = noise; a.noise_on = noise_on; a.seed = seed; a.b0 = noise_index0; a.void_label = void_label; a.quantize_f16 = quantize_f16;
@@ -791,7 +790,10 @@ int drs_crop_normalize_scaled(const void* tiles, int tiles_are_f64, const unsign
 
 int drs_stitch_accumulate(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int S, int stride,
                           int first_window, int n_windows, void* stream) {
-  if (!prob || !occur || !logits || K < 1 || K > 8 || S > h || S > w || stride < 1) return DRS_ERR_ARG;
+  if (!prob || !occur || !logits || K < 1 || K > 8 || S < 1 || h < 1 || w < 1 || S > h || S > w || stride < 1) return DRS_ERR_ARG;
+  // covering() lists at most 5 regular windows per axis over a coordinate, plus the one shifted back to the border
+  if (((long long)S + stride - 1) / stride > 5) return DRS_ERR_ARG;
+  if (!drs_prod_below(1LL << 31, {(h - S) / stride + 2, (w - S) / stride + 2})) return DRS_ERR_ARG;        // the flat window index is an int
   StitchArgs a;
   a.prob = prob; a.occur = occur; a.logits = logits; a.h = h; a.w = w; a.K = K; a.S = S; a.stride = stride;
   a.n_h = (h - S) % stride == 0 ? (h - S) / stride + 1 : (h - S) / stride + 2;
@@ -802,6 +804,7 @@ int drs_stitch_accumulate(float* prob, unsigned int* occur, const float* logits,
   const int y0 = r_first * stride < h - S ? r_first * stride : h - S;
   const int y1 = (r_last * stride < h - S ? r_last * stride : h - S) + S;
   a.row0 = y0; a.nrows = y1 - y0;
+  if (a.nrows > 65535) return DRS_ERR_ARG;       // the touched rows index grid.y
   dim3 grid((w + 255) / 256, a.nrows);
   DRS_LAUNCH(stitch_accumulate_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
   return DRS_LAUNCH_CHECK();
@@ -850,7 +853,7 @@ int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs,
 }
 
 int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int w, int K, unsigned char* out, void* stream) {
-  if (!prob || !occur || !out || K < 1 || K > 8) return DRS_ERR_ARG;
+  if (!prob || !occur || !out || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
   const size_t n = (size_t)h * w;
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(stitch_finalize_kernel, dim3(nb < 4096 ? (unsigned)nb : 4096u), dim3(256), 0, (hipStream_t)stream, prob, occur,
@@ -873,7 +876,7 @@ int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, i
 }
 
 int drs_softmax_accumulate(const float* prob, const unsigned int* occur, int h, int w, int K, float* acc, void* stream) {
-  if (!prob || !occur || !acc || K < 1 || K > 8) return DRS_ERR_ARG;
+  if (!prob || !occur || !acc || K < 1 || K > 8 || h < 1 || w < 1) return DRS_ERR_ARG;
   const size_t n = (size_t)h * w;
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(softmax_accumulate_kernel, dim3(nb < 4096 ? (unsigned)nb : 4096u), dim3(256), 0, (hipStream_t)stream, prob, occur, n, K, acc);

@@ -1805,6 +1805,12 @@ temperature_stats_l2_kernel(const double* __restrict__ scratch, int rows, double
   if (threadIdx.x == 0) out[j] += sh[0];
 }
 
+// argument domains (include/drs.h): a batch of patches whose haloed rows index grid.y and whose pixels the kernels count in 24 bits
+inline bool batch_ok(int B, int S, int P) { return drs_rows_ok(B, S, P) && (long long)B * S * S < (1 << 24); }
+inline bool count_ok(double c) { return std::isfinite(c) && c >= 1.0; }                  // a pixel count
+inline bool unit_ok(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }       // alpha of max(alpha x, x); a decay
+constexpr int SE_MAX_CR = 16384;      // se_excite_kernel keeps C + R floats in dynamic LDS (64 KiB without an opt-in)
+
 inline int chain_hp() { return drs_chain_level(drs_tl_chain, drs_g_chain_mode) >= 2 ? 1 : 0; }
 
 inline ActView mkview(float* base, int S, int P, int ld, int coff) {
@@ -1826,7 +1832,7 @@ int drs_stats_reduce(const float* partial, int nrows, int C, double* sums, doubl
 }
 
 int drs_stats_reduce_means(const float* partial, int nrows, int C, double count, double* sums, float* means, void* stream) {
-  if (!partial || !means || nrows < 1 || C < 1 || count < 1.0) return DRS_ERR_ARG;
+  if (!partial || !means || nrows < 1 || C < 1 || !count_ok(count)) return DRS_ERR_ARG;
   DRS_LAUNCH(bn_stats_kernel<false>, dim3((C + STAT_CH - 1) / STAT_CH), dim3(256), 0, (hipStream_t)stream, partial, nrows, C, 0, 1, sums,
              count, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0, means, chain_hp());
   return DRS_LAUNCH_CHECK();
@@ -1842,7 +1848,8 @@ int drs_conv_stats_reduce(const float* partial, int M, int mtile, int C, double*
 
 int drs_conv_stats_finish(const float* partial, int M, int mtile, int C, double count, float* mean_rstd, float* moving_mean,
                           float* moving_var, double decay, int bessel, double* sums, void* stream) {
-  if (!partial || !mean_rstd || M < 1 || mtile < 1 || C < 1 || count < 1.0) return DRS_ERR_ARG;
+  if (!partial || !mean_rstd || M < 1 || mtile < 1 || C < 1 || !count_ok(count) || !unit_ok(decay)) return DRS_ERR_ARG;
+  if ((moving_mean == nullptr) != (moving_var == nullptr)) return DRS_ERR_ARG;
   DRS_LAUNCH(bn_stats_kernel<true>, dim3((C + STAT_CH - 1) / STAT_CH), dim3(256), 0, (hipStream_t)stream, partial, (M + mtile - 1) / mtile, C,
              M, mtile, sums, count, mean_rstd, moving_mean, moving_var, (float)(1.0 - decay), bessel, (float*)nullptr, chain_hp());
   return DRS_LAUNCH_CHECK();
@@ -1850,14 +1857,14 @@ int drs_conv_stats_finish(const float* partial, int M, int mtile, int C, double 
 
 int drs_bn_finish(const double* sums, double count, int C, float* mean_rstd, float* moving_mean, float* moving_var,
                   double decay, int bessel, void* stream) {
-  if (!sums || !mean_rstd || count < 1.0) return DRS_ERR_ARG;
+  if (!sums || !mean_rstd || C < 1 || !count_ok(count) || !unit_ok(decay) || (moving_mean == nullptr) != (moving_var == nullptr)) return DRS_ERR_ARG;
   DRS_LAUNCH(bn_finish_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, sums, count, C, mean_rstd,
                      moving_mean, moving_var, (float)(1.0 - decay), bessel);
   return DRS_LAUNCH_CHECK();
 }
 
 int drs_bn_eval_coeffs(const float* moving_mean, const float* moving_var, int C, float* mean_rstd, void* stream) {
-  if (!moving_mean || !moving_var || !mean_rstd) return DRS_ERR_ARG;
+  if (!moving_mean || !moving_var || !mean_rstd || C < 1) return DRS_ERR_ARG;
   DRS_LAUNCH(bn_eval_coeffs_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, moving_mean, moving_var, C,
                      mean_rstd);
   return DRS_LAUNCH_CHECK();
@@ -1867,10 +1874,10 @@ static int bn_act_pool_forward_impl(const float* z, int B, int S, int C, const f
                                     float* out, int P_out, int ld_out, int coff_out, unsigned char* argmax,
                                     unsigned short* terms, int nterms, void* stream, const BnFinish* fin = nullptr) {
   if (!z || !mean_rstd || (!out && !terms) || C % 4) return DRS_ERR_ARG;
+  if (!batch_ok(B, S, P_out) || !unit_ok(alpha) || !drs_slice_ok(ld_out, coff_out, C, 4)) return DRS_ERR_ARG;     // 16-byte stores into the slice
   if (fin && !((pool & 1) && slide_ok(C) && !terms)) return DRS_ERR_ARG;     // the folded finish exists in the pooled sliding kernel only
   if (terms && ((nterms != 2 && nterms != 3) || (ld_out & 31) || (coff_out & 31))) return DRS_ERR_ARG;
   const int Sp = S + 2 * P_out;
-  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
   const int per_row = Sp * (C / 4);
   dim3 grid((per_row + 255) / 256, B * Sp);
   ActView v = mkview(out, S, P_out, ld_out, coff_out);
@@ -1903,7 +1910,8 @@ int drs_bn_act_pool_forward(const float* z, int B, int S, int C, const float* me
 int drs_bn_finish_act_pool_forward(const double* sums, double count, float* mean_rstd, float* moving_mean, float* moving_var, double decay,
                                    int bessel, const float* z, int B, int S, int C, float alpha, int pool, float* out, int P_out, int ld_out,
                                    int coff_out, unsigned char* argmax, void* stream) {
-  if (!sums || !mean_rstd || !out || count < 1.0 || !(pool & 1) || !slide_ok(C)) return DRS_ERR_ARG;
+  if (!sums || !mean_rstd || !out || !count_ok(count) || !unit_ok(decay) || !(pool & 1) || !slide_ok(C)) return DRS_ERR_ARG;
+  if ((moving_mean == nullptr) != (moving_var == nullptr)) return DRS_ERR_ARG;
   const BnFinish fin = {sums, count, moving_mean, moving_var, (float)(1.0 - decay), bessel};
   return bn_act_pool_forward_impl(z, B, S, C, mean_rstd, alpha, pool, out, P_out, ld_out, coff_out, argmax, nullptr, 0, stream, &fin);
 }
@@ -1938,6 +1946,7 @@ int drs_bn_backward_reduce(const float* ga, int ld_ga, int coff_ga, const float*
   if (!ga || !z || !mean_rstd || !gxhat || !partial || C % 4 || (pool && !argmax)) return DRS_ERR_ARG;
   const int CQ = C / 4;
   if (CQ > 256) return DRS_ERR_ARG;
+  if (!batch_ok(B, S, 0) || !unit_ok(alpha) || !drs_slice_ok(ld_ga, coff_ga, C, 4)) return DRS_ERR_ARG;          // 16-byte loads from the slice
   if (pool && slide_ok(C)) {
     const SlideCfg c = slide_cfg(B, S, C);
     const size_t xchg = (size_t)2 * (c.TX + 2) * CQ * 20, redu = (size_t)c.TX * C * 2 * sizeof(float);
@@ -1964,8 +1973,8 @@ static int bn_backward_apply_impl(const float* gxhat, const float* z, int B, int
                                   unsigned short* terms, int nterms, void* stream) {
   if (!gxhat || !z || !mean_rstd || !sums || (!gz && !terms) || C % 4 || C > 1024) return DRS_ERR_ARG;
   if (terms && ((nterms != 2 && nterms != 3) || (ld_out & 31) || (coff_out & 31))) return DRS_ERR_ARG;
+  if (!batch_ok(B, S, P_out) || !count_ok(count) || !drs_slice_ok(ld_out, coff_out, C, 4)) return DRS_ERR_ARG;
   const int Sp = S + 2 * P_out;
-  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
   const int per_row = Sp * (C / 4);
   dim3 grid((per_row + 255) / 256, B * Sp);
   ActView v = mkview(gz, S, P_out, ld_out, coff_out);
@@ -1984,8 +1993,8 @@ int drs_bn_backward_apply(const float* gxhat, const float* z, int B, int S, int 
 int drs_bn_backward_apply_means(const float* gxhat, const float* z, int B, int S, int C, const float* mean_rstd, const float* means,
                                 float* gz, int P_out, int ld_out, int coff_out, void* stream) {
   if (!gxhat || !z || !mean_rstd || !means || !gz || C % 4 || C > 1024) return DRS_ERR_ARG;
+  if (!batch_ok(B, S, P_out) || !drs_slice_ok(ld_out, coff_out, C, 4)) return DRS_ERR_ARG;
   const int Sp = S + 2 * P_out;
-  if ((long long)B * Sp > 65535) return DRS_ERR_ARG;
   const int per_row = Sp * (C / 4);
   DRS_LAUNCH(bn_bwd_apply_means_kernel, dim3((per_row + 255) / 256, B * Sp), dim3(256), 0, (hipStream_t)stream, gxhat, z, B, S, C, mean_rstd,
              means, mkview(gz, S, P_out, ld_out, coff_out), chain_hp());
@@ -2025,9 +2034,17 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
                               float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
                               float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
-  if (!feat || !w || !bias || K < 1 || K > 8 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
+  if (!feat || !w || !bias || K < 1 || K > 8 || C < 64 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
+  if (B < 1 || S < 1 || P < 0 || !std::isfinite(inv_n) || inv_n < 0.f) return DRS_ERR_ARG;
   if (!std::isfinite(focal_gamma) || focal_gamma < 0.f || focal_gamma > 8.f) return DRS_ERR_ARG;
-  bool wt = false;
+  const long long M = (long long)B * S * S;
+  if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
+  if (labels && !loss_partial) return DRS_ERR_ARG;
+  if (gfeat && (!dw_partial || !db_partial || !labels)) return DRS_ERR_ARG;
+  if (ld % 4 || coff % 4 || (gfeat && (ld_g % 4 || coff_g % 4))) return DRS_ERR_ARG;       // 16-byte feature / gradient accesses
+  if (!drs_slice_ok(ld, coff, C, 4) || (gfeat && !drs_slice_ok(ld_g, coff_g, C, 4))) return DRS_ERR_ARG;
+  if ((long long)B * (S + 2LL * P) * (S + 2LL * P) * ld >= (1LL << 30)) return DRS_ERR_ARG;      // 32-bit byte offsets into the feature slab
+  bool wt = false;        // (class_weights is a HOST pointer: read only once everything else has passed)
   if (class_weights)
     for (int k = 0; k < K; ++k) {
       if (!std::isfinite(class_weights[k]) || class_weights[k] < 0.f) return DRS_ERR_ARG;
@@ -2036,11 +2053,6 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
   wt = wt && labels;
   const bool focal = focal_gamma > 0.f && labels;
   const int lm = focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
-  const long long M = (long long)B * S * S;
-  if (M <= 0 || M >= (1 << 24)) return DRS_ERR_ARG;
-  if (labels && !loss_partial) return DRS_ERR_ARG;
-  if (gfeat && (!dw_partial || !db_partial || !labels)) return DRS_ERR_ARG;
-  if (ld % 4 || coff % 4 || (gfeat && (ld_g % 4 || coff_g % 4))) return DRS_ERR_ARG;       // 16-byte feature / gradient accesses
   ClsArgs a;
   a.feat = mkview(const_cast<float*>(feat), S, P, ld, coff); a.C = C; a.K = K; a.M = (int)M; a.w = w; a.bias = bias;
   a.labels = labels; a.loss_mask = loss_mask; a.acc_mask = acc_mask; a.inv_n = inv_n; a.logits = logits; a.pred = pred;
@@ -2156,14 +2168,14 @@ int drs_temperature_stats(const float* sums, const unsigned int* occur, const un
 }
 
 int drs_rows_reduce_f32(const float* in, int nrows, int ncols, float* out, double* scratch, void* stream) {
-  if (!in || !out || !scratch || nrows < 1) return DRS_ERR_ARG;
+  if (!in || !out || !scratch || nrows < 1 || ncols < 1) return DRS_ERR_ARG;
   DRS_LAUNCH(colsum_l1_kernel, dim3((ncols + 63) / 64, COLSUM_BLOCKS), dim3(256), 0, (hipStream_t)stream, in, nrows, ncols, scratch);
   DRS_LAUNCH(colsum_l2_kernel<float>, dim3((ncols + 255) / 256), dim3(256), 0, (hipStream_t)stream, scratch, ncols, out);
   return DRS_LAUNCH_CHECK();
 }
 
 int drs_sum_f64(const double* in, int n, double* out, void* stream) {
-  if (!in || !out) return DRS_ERR_ARG;
+  if (!in || !out || n < 1) return DRS_ERR_ARG;
   DRS_LAUNCH(sum_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, in, n, out);
   return DRS_LAUNCH_CHECK();
 }
@@ -2176,7 +2188,7 @@ int drs_scale_f64(double* x, int n, double s, void* stream) {
 
 // l2 = 0.5 * sum(w[0..n)^2) -> out[0] (fp64); scratch holds 256 doubles
 int drs_l2_loss(const float* w, size_t n, double* scratch, double* out, void* stream) {
-  if (!w || !scratch || !out) return DRS_ERR_ARG;
+  if (!w || !scratch || !out || n < 1 || n >= ((size_t)1 << 40)) return DRS_ERR_ARG;
   DRS_LAUNCH(l2_partial_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, w, n, scratch);
   DRS_LAUNCH(sum_f64_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, 256, out);
   return DRS_LAUNCH_CHECK();
@@ -2184,7 +2196,7 @@ int drs_l2_loss(const float* w, size_t n, double* scratch, double* out, void* st
 
 int drs_momentum_update(float* w, const float* grad, float* accum, size_t n, size_t n_decay, float lr, float weight_decay,
                         float momentum, float grad_scale, void* stream) {
-  if (!w || !grad || !accum) return DRS_ERR_ARG;
+  if (!w || !grad || !accum || n < 1 || n >= ((size_t)1 << 40) || n_decay > n) return DRS_ERR_ARG;
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(momentum_kernel, dim3(nb < 2048 ? (unsigned)nb : 2048u), dim3(256), 0, (hipStream_t)stream, w, grad, accum, n,
                      n_decay, lr, weight_decay, momentum, grad_scale);
@@ -2193,7 +2205,7 @@ int drs_momentum_update(float* w, const float* grad, float* accum, size_t n, siz
 
 int drs_confusion(const unsigned char* labels, const unsigned char* pred, const unsigned char* mask, size_t n, int K,
                   int ignore_label, unsigned int* conf, void* stream) {
-  if (!labels || !pred || !conf || K < 1 || K > 8) return DRS_ERR_ARG;
+  if (!labels || !pred || !conf || K < 1 || K > 8 || n < 1 || n >= ((size_t)1 << 32)) return DRS_ERR_ARG;      // (32-bit counters)
   const size_t nb = (n + 255) / 256;
   DRS_LAUNCH(confusion_kernel, dim3(nb < 1024 ? (unsigned)nb : 1024u), dim3(256), 0, (hipStream_t)stream, labels, pred, mask,
                      n, K, ignore_label, conf);
@@ -2201,7 +2213,7 @@ int drs_confusion(const unsigned char* labels, const unsigned char* pred, const 
 }
 
 int drs_avg_pool_forward(const float* in, int B, int S, int C, int k, float* out, int P_out, int ld_out, int coff_out, void* stream) {
-  if (!in || !out || C % 4 || k < 1 || !(k & 1) || (long long)B * (S + 2 * P_out) > 65535) return DRS_ERR_ARG;
+  if (!in || !out || C % 4 || k < 1 || !(k & 1) || !batch_ok(B, S, P_out) || !drs_slice_ok(ld_out, coff_out, C, 4)) return DRS_ERR_ARG;
   ActView v = mkview(out, S, P_out, ld_out, coff_out);
   if (P_out > 0) {
     const int Sp = S + 2 * P_out;
@@ -2212,7 +2224,7 @@ int drs_avg_pool_forward(const float* in, int B, int S, int C, int k, float* out
 }
 
 int drs_avg_pool_backward(const float* gout, int ld_g, int coff_g, int B, int S, int C, int k, float* gin, void* stream) {
-  if (!gout || !gin || C % 4 || k < 1 || !(k & 1) || (long long)B * S > 65535) return DRS_ERR_ARG;
+  if (!gout || !gin || C % 4 || k < 1 || !(k & 1) || !batch_ok(B, S, 0) || !drs_slice_ok(ld_g, coff_g, C, 4)) return DRS_ERR_ARG;
   DRS_LAUNCH(avg_pool_kernel<true>, dim3((S * (C / 4) + 255) / 256, B * S), dim3(256), 0, (hipStream_t)stream, gout, ld_g, coff_g, B, S, C,
              k, mkview(gin, S, 0, C, 0));
   return DRS_LAUNCH_CHECK();
@@ -2221,7 +2233,8 @@ int drs_avg_pool_backward(const float* gout, int ld_g, int coff_g, int B, int S,
 // state: s [B][C], e1 [B][R], e2 [B][C] (kept for the backward pass)
 int drs_se_forward(const float* act, int B, int S, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
                    float* s, float* e1, float* e2, float* out, int P_out, int ld_out, int coff_out, void* stream) {
-  if (!act || !w1 || !b1 || !w2 || !b2 || !s || !e1 || !e2 || !out || C % 4 || R < 1 || (long long)B * (S + 2 * P_out) > 65535)
+  if (!act || !w1 || !b1 || !w2 || !b2 || !s || !e1 || !e2 || !out || C % 4 || R < 1 || !batch_ok(B, S, P_out) ||
+      !drs_slice_ok(ld_out, coff_out, C, 4) || (long long)C + R > SE_MAX_CR)
     return DRS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   DRS_LAUNCH(se_spatial_reduce_kernel<false>, dim3((C + 63) / 64, B), dim3(256), 0, st, act, C, 0, nullptr, S, C, 1.0f / (float)(S * S), s);
@@ -2239,7 +2252,8 @@ int drs_se_forward(const float* act, int B, int S, int C, int R, const float* w1
 int drs_se_backward(const float* gy, int ld_g, int coff_g, const float* act, const float* s, const float* e1, const float* e2,
                     const float* w1, const float* w2, int B, int S, int C, int R, float* gact, float* dw1, float* db1, float* dw2,
                     float* db2, float* scratch, void* stream) {
-  if (!gy || !act || !s || !e1 || !e2 || !w1 || !w2 || !gact || !dw1 || !db1 || !dw2 || !db2 || !scratch || C % 4 || (long long)B * S > 65535)
+  if (!gy || !act || !s || !e1 || !e2 || !w1 || !w2 || !gact || !dw1 || !db1 || !dw2 || !db2 || !scratch || C % 4 || R < 1 || !batch_ok(B, S, 0) ||
+      !drs_slice_ok(ld_g, coff_g, C, 4) || (long long)C + R > SE_MAX_CR)
     return DRS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   float* ge2 = scratch;                       // [B][C]
@@ -2272,7 +2286,7 @@ int drs_se_core_sums(const float* act, int C, int T, const int* boxes, int n, do
 // arithmetic of drs_se_forward for one "image"
 int drs_se_gate(const double* sums, double count, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
                 float* s, float* e1, float* e2, void* stream) {
-  if (!sums || !w1 || !b1 || !w2 || !b2 || !s || !e1 || !e2 || C < 1 || R < 1 || !(count > 0.0)) return DRS_ERR_ARG;
+  if (!sums || !w1 || !b1 || !w2 || !b2 || !s || !e1 || !e2 || C < 1 || R < 1 || !(count > 0.0) || !std::isfinite(count) || (long long)C + R > SE_MAX_CR) return DRS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   DRS_LAUNCH(se_mean_kernel, dim3((C + 255) / 256), dim3(256), 0, st, sums, count, C, s);
   DRS_LAUNCH(se_excite_kernel, dim3(1), dim3(256), (C + R) * sizeof(float), st, s, w1, b1, w2, b2, C, R, e1, e2);
@@ -2281,7 +2295,7 @@ int drs_se_gate(const double* sums, double count, int C, int R, const float* w1,
 
 // out view = act * e2[c] with ONE gate vector for the whole batch (halo zeroed): drs_se_forward's last step with a given gate
 int drs_se_scale_const(const float* act, int B, int S, int C, const float* e2, float* out, int P_out, int ld_out, int coff_out, void* stream) {
-  if (!act || !e2 || !out || B < 1 || S < 1 || C < 4 || C % 4 || (long long)B * (S + 2 * P_out) > 65535) return DRS_ERR_ARG;
+  if (!act || !e2 || !out || C % 4 || !batch_ok(B, S, P_out) || !drs_slice_ok(ld_out, coff_out, C, 4)) return DRS_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   ActView v = mkview(out, S, P_out, ld_out, coff_out);
   if (P_out > 0) {

@@ -20,7 +20,14 @@
  *     P = 0 gives the reference's plain [B, S, S, C] tensor; filters are HWIO = [k][k][Cin][Cout] as in the
  *     reference (isprs:706);
  *   - B*S*S must be < 2^24, and every activation slab a convolution reads must stay below 4 GiB (2^30 floats): the kernels
- *     address with a wave-uniform 64-bit base plus 32-bit byte offsets.
+ *     address with a wave-uniform 64-bit base plus 32-bit byte offsets;
+ *   - ARGUMENT DOMAINS: every op-level entry point that launches a kernel states its domain ("Ranges, else DRS_ERR_ARG: ...") and
+ *     rejects everything outside it before its first HIP call and before it reads a HOST-pointer argument; a pointer that the text
+ *     does not call optional ("or NULL", "may be NULL") must not be NULL.  The bounds are what the kernels and their launches need:
+ *     grid limits (65535 in y and z), fixed per-thread arrays, the alignment of 16-byte vector accesses (ld and coff multiples of 4
+ *     floats; bases come from an allocator and are at least 16-byte aligned), 32-bit offsets, the halo against the padding, and a
+ *     channel slice inside its row, 0 <= coff and coff + C <= ld ("a slice of C in (ld, coff)" below).  tests/test_abi_contract.py
+ *     holds one violation per stated bound against the library.
  */
 #ifndef DRS_H_
 #define DRS_H_
@@ -44,7 +51,13 @@ extern "C" {
  * of train-mode batch norm (isprs:658-660), two-pass inside the tile as TensorFlow is two-pass over the batch;
  * drs_conv_stats_reduce combines the tiles.
  * The input-gradient pass is this same call on the haloed output gradient with the filter from
- * drs_filter_flip_transpose and pad_before := pad_after. */
+ * drs_filter_flip_transpose and pad_before := pad_after.
+ * Ranges, else DRS_ERR_ARG (drs_conv_forward and drs_conv_forward_ws): in, w, out not NULL (bias, stats_partial, workspace may be);
+ * B, S >= 1, B*S*S < 2^24; k, rate >= 1; cin in {8, 16} or a multiple of 32 (>= 32); cout a multiple of 32 (>= 32);
+ * k*k*cin*cout < 2^31; 0 <= pad_before <= P and (k-1)*rate - pad_before <= P (the halo covers both pads);
+ * B*(S+2P)^2*ld_in < 2^30; a slice of cin in (ld_in, coff_in), of cout in (ld_out, coff_out); cin < 32: ld_in and coff_in multiples
+ * of 4; not accumulate together with stats_partial.  drs_conv_executed_ksteps: B, S, k, rate, cin >= 1, B*S*S < 2^24, cout a
+ * multiple of 32 (>= 32), executed and total (HOST pointers) not NULL. */
 int drs_conv_mtile(int cout);
 /* drs_conv_forward_ws: the same with a caller-owned workspace (>= drs_conv_workspace_floats(cout) floats, 16-byte aligned, enables
  * every geometry; NULL, unaligned or too small for the cut the shape asks for: the plain launch of drs_conv_forward -- the cut, and with
@@ -73,17 +86,24 @@ int drs_conv_forward(const float* in, int B, int S, int P, int ld_in, int coff_i
 /* ---- filter gradient of the same op (what tf.gradients emits for isprs:710-712) --------------------------
  * grad[u][v][c < cin_real][o] = sum_p x[p + (u,v)*rate - pad_before, c] * g[p, o];  x, g haloed views.
  * slab: workspace of drs_conv_wgrad_splits(...) * k*k*cin*cout floats (per-split partial sums, summed in
- * a fixed order -> bitwise reproducible). */
+ * a fixed order -> bitwise reproducible).
+ * Ranges, else DRS_ERR_ARG: x, g, slab, grad not NULL; B, S >= 1, B*S*S < 2^24; k, rate >= 1; cin in {8, 16} or a multiple of 32;
+ * 1 <= cin_real <= cin; cout a multiple of 32 (>= 32); k*k*cin*cout < 2^31; 0 <= pad_before <= Px and (k-1)*rate - pad_before <= Px
+ * (the halo of x covers both pads, as in the forward call: the kernels form the shifted pixel address in 32 bits and a short halo
+ * wraps it); Pg >= 0, any width -- the halo of g is only skipped over, Px and Pg are independent; B*(S+2Px)^2*ld_x < 2^30 and
+ * B*(S+2Pg)^2*ld_g < 2^30; a slice of cin in (ld_x, coff_x), of cout in (ld_g, coff_g); cin < 32: ld_x and coff_x multiples of 4. */
 int drs_conv_wgrad_splits(int B, int S, int k, int cin, int cout);
 int drs_conv_wgrad(const float* x, int B, int S, int Px, int ld_x, int coff_x, const float* g, int Pg, int ld_g,
                    int coff_g, int k, int rate, int pad_before, int cin, int cin_real, int cout, float* slab,
                    float* grad, void* stream);
 
-/* wt[k-1-u][k-1-v][o][c] = w[u][v][c][o]: the filter of the input-gradient pass */
+/* wt[k-1-u][k-1-v][o][c] = w[u][v][c][o]: the filter of the input-gradient pass.
+ * Ranges, else DRS_ERR_ARG: w, wt not NULL; k, cin, cout >= 1; k*k*cin*cout < 2^31 (the element index is an int). */
 int drs_filter_flip_transpose(const float* w, float* wt, int k, int cin, int cout, void* stream);
 /* wp[u][v][c < cin_pad][o] = c < cin ? w[u][v][c][o] : 0.  For cin_pad = 8 / 16 (conv1's 3..5 bands in an 8-channel slab: the
  * packed-tap form of drs_conv_forward, 32 / cin_pad taps to a K-step of 32 rows) the caller's `wp` holds
- * round_up(k*k*cin_pad, 32) * cout floats and the rows past the last tap must be ZERO (this call writes the first k*k*cin_pad rows). */
+ * round_up(k*k*cin_pad, 32) * cout floats and the rows past the last tap must be ZERO (this call writes the first k*k*cin_pad rows).
+ * Ranges, else DRS_ERR_ARG: w, wp not NULL; k, cin, cout >= 1; cin_pad >= cin; k*k*cin_pad*cout < 2^31. */
 int drs_filter_pad_cin(const float* w, float* wp, int k, int cin, int cin_pad, int cout, void* stream);
 
 /* ---- the same convolution in split-bf16 arithmetic (csrc/conv_split.hip) ---------------------------------------
@@ -102,7 +122,20 @@ int drs_filter_pad_cin(const float* w, float* wp, int k, int cin, int cin_pad, i
  *                        stats_partial rows hold drs_split_conv_mtile(cout) pixels.
  *   drs_conv_wgrad_split : drs_conv_wgrad on terms; slab = drs_conv_wgrad_split_splits(..., Pg, nterms) * k*k*cin*cout floats
  *                        (an upper bound that is monotone in B and S: a slab sized for (b_max, s_max) serves every smaller call).
- *                        With Pg > 0 pixels past the end read the gradient slab's first halo pixel (zeros). */
+ *                        With Pg > 0 pixels past the end read the gradient slab's first halo pixel (zeros).
+ * Ranges, else DRS_ERR_ARG: every pointer but bias, stats_partial and wd not NULL; nterms 2 or 3.
+ *   drs_split_terms    : n a multiple of 32 (n == 0 does nothing).
+ *   drs_filter_split   : k, cin >= 1; cin_pad >= cin, a multiple of 32; cout a multiple of 32 (>= 32); with wd: cin a multiple of 32;
+ *                        k*k*cin_pad*cout*nterms < 2^31.
+ *   drs_conv_forward_split : B, S >= 1, B*S*S < 2^24; k, rate >= 1; cin a multiple of 32 (>= 32); cout a multiple of 64 (>= 64);
+ *                        0 <= pad_before <= P and (k-1)*rate - pad_before <= P; a slice of cin in (ld_in, coff_in), both multiples of 32;
+ *                        a slice of cout in (ld_out, coff_out); B*(S+2P)^2*ld_in*nterms < 2^31 and k*k*cin*cout*nterms < 2^31 (32-bit
+ *                        byte offsets into the term images); not accumulate together with stats_partial.
+ *   drs_conv_wgrad_split : B, S >= 1, B*S*S < 2^24; k, rate >= 1; cin a multiple of 32 (>= 32); 1 <= cin_real <= cin; cout a multiple
+ *                        of 64 (>= 64); k*k*cin*cout < 2^31; 0 <= pad_before <= Px and (k-1)*rate - pad_before <= Px; Pg >= 0 (Pg == 0
+ *                        runs the register-staged form: there is no halo pixel to fetch zeros from); a slice of cin in (ld_x, coff_x),
+ *                        of cout in (ld_g, coff_g), all four multiples of 32; B*(S+2Px)^2*ld_x*nterms < 2^32 and
+ *                        B*(S+2Pg)^2*ld_g*nterms < 2^31. */
 int drs_split_conv_mtile(int cout);
 int drs_split_terms(const float* src, size_t n, int nterms, unsigned short* terms, void* stream);
 int drs_filter_split(const float* w, int k, int cin, int cin_pad, int cout, int nterms, unsigned short* wf,
@@ -126,7 +159,10 @@ int drs_conv_wgrad_split(const unsigned short* x, int B, int S, int Px, int ld_x
  * drs_conv_stats_finish : drs_conv_stats_reduce + drs_bn_finish in ONE launch (single rank); sums may be NULL.
  * drs_bn_finish    : sums, count -> mean_rstd[C][2] = (mean, 1/sqrt(biased var + eps)); if moving_* != NULL,
  *                    moving -= (moving - batch) * (1 - decay) with the Bessel-corrected variance when bessel.
- * drs_bn_eval_coeffs: is_training=False branch: mean_rstd from the moving statistics. */
+ * drs_bn_eval_coeffs: is_training=False branch: mean_rstd from the moving statistics.
+ * Ranges, else DRS_ERR_ARG: partial, mean_rstd / means (where the call writes them) not NULL, sums not NULL where the text does not
+ * say it may be; moving_mean and moving_var both NULL or both given; nrows, C, M, mtile >= 1; count finite and >= 1; decay finite in
+ * [0, 1].  drs_rows_reduce_f32: nrows, ncols >= 1; drs_sum_f64, drs_scale_f64: n >= 1. */
 int drs_colsum_scratch_doubles(int ncols);
 int drs_stats_reduce(const float* partial, int nrows, int C, double* sums, double* scratch, void* stream);
 /* drs_stats_reduce that also leaves means[C][2] = (float)(sums / count): what drs_bn_backward_apply_means takes (single rank: the
@@ -144,7 +180,12 @@ int drs_bn_eval_coeffs(const float* moving_mean, const float* moving_var, int C,
  * pool: bit 0 = apply the 3x3 max-pool; bit 1 = the halo of `out` is known to be zero already (a previous call on this slab with
  * the same B, S, P_out wrote it and nothing else has written the slab since) and need not be rewritten (pooling path only).
  * out: haloed view (the halo zeros are written here); argmax (pool only, may be NULL): [B*S*S][C] window
- * position 0..8 of the first maximum, which the backward pass routes gradients to (TF MaxPoolGrad). */
+ * position 0..8 of the first maximum, which the backward pass routes gradients to (TF MaxPoolGrad).
+ * Ranges, else DRS_ERR_ARG (the three forward calls): z, mean_rstd not NULL, out not NULL (drs_bn_act_pool_forward_terms: out or
+ * terms); B, S >= 1, P_out >= 0, B*(S+2*P_out) <= 65535 (grid.y), B*S*S < 2^24; C a multiple of 4 (>= 4); alpha finite in [0, 1]
+ * (max(alpha x, x) is the activation only there); a slice of C in (ld_out, coff_out), both multiples of 4 (16-byte stores), with
+ * terms multiples of 32 and nterms 2 or 3.  drs_bn_finish_act_pool_forward also: sums not NULL, count finite >= 1, decay finite in
+ * [0, 1], moving_mean and moving_var both or neither, pool bit 0 set, C <= 512. */
 int drs_bn_act_pool_forward(const float* z, int B, int S, int C, const float* mean_rstd, float alpha, int pool,
                             float* out, int P_out, int ld_out, int coff_out, unsigned char* argmax, void* stream);
 /* drs_bn_finish + drs_bn_act_pool_forward in one launch (pooled blocks with C <= 512): under data parallelism the batch-norm sums
@@ -161,7 +202,11 @@ int drs_bn_act_pool_forward_terms(const float* z, int B, int S, int C, const flo
 /* ---- backward of the block above ----------------------------------------------------------------------
  * reduce: ga [B*S*S][ld_ga]+coff_ga = gradient wrt the block output -> gxhat [B*S*S][C] (gradient wrt the
  *         normalised activation) and partial[drs_bn_backward_rows(B,S,C,pool)][C][2] = (sum g, sum g*xhat);
- * apply : gz = rstd * (gxhat - sum_g/count - xhat * sum_gx/count) into a haloed view (halo zeroed). */
+ * apply : gz = rstd * (gxhat - sum_g/count - xhat * sum_gx/count) into a haloed view (halo zeroed).
+ * Ranges, else DRS_ERR_ARG: every pointer not NULL (argmax only with pool; gz may be NULL in drs_bn_backward_apply_terms); B, S >= 1,
+ * B*S*S < 2^24; C a multiple of 4, 4 <= C <= 1024; reduce: B*S <= 65535, alpha finite in [0, 1], a slice of C in (ld_ga, coff_ga),
+ * both multiples of 4 (16-byte loads); apply: P_out >= 0, B*(S+2*P_out) <= 65535, count finite >= 1, a slice of C in
+ * (ld_out, coff_out), both multiples of 4, with terms multiples of 32 and nterms 2 or 3. */
 int drs_bn_backward_rows(int B, int S, int C, int pool);
 int drs_bn_backward_reduce(const float* ga, int ld_ga, int coff_ga, const float* z, const unsigned char* argmax, int B,
                            int S, int C, const float* mean_rstd, float alpha, int pool, float* gxhat, float* partial,
@@ -179,7 +224,9 @@ int drs_bn_backward_apply_terms(const float* gxhat, const float* z, int B, int S
 
 /* ---- tf.nn.avg_pool(k x k, stride 1, SAME) of the `_avgpool` variant (isprs:753-758, 818-854) ------------------
  * forward: in [B*S*S][C] -> interior of a haloed view (halo zeroed), divisor = pixels of the window inside the image;
- * backward: gout [B*S*S][ld_g]+coff_g -> gin [B*S*S][C].  k odd. */
+ * backward: gout [B*S*S][ld_g]+coff_g -> gin [B*S*S][C].  k odd.
+ * Ranges, else DRS_ERR_ARG: pointers not NULL; k odd, >= 1; B, S >= 1, P_out >= 0, B*(S+2*P_out) <= 65535 (backward: B*S), B*S*S < 2^24;
+ * C a multiple of 4 (>= 4); a slice of C in (ld_out, coff_out) / (ld_g, coff_g), both multiples of 4. */
 int drs_avg_pool_forward(const float* in, int B, int S, int C, int k, float* out, int P_out, int ld_out, int coff_out,
                          void* stream);
 int drs_avg_pool_backward(const float* gout, int ld_g, int coff_g, int B, int S, int C, int k, float* gin, void* stream);
@@ -188,7 +235,10 @@ int drs_avg_pool_backward(const float* gout, int ld_g, int coff_g, int B, int S,
  * forward : act [B*S*S][C] (activated block output) -> s = spatial mean, e1 = relu(s w1 + b1) [B][R], e2 = sigmoid(e1 w2 + b2)
  *           [B][C] (all three kept for the backward pass), out view = act * e2 (halo zeroed);  w1 [C][R], w2 [R][C].
  * backward: gy (gradient wrt the scaled output) -> gact [B*S*S][C] and the four parameter gradients (sums over this rank's
- *           images, fixed order); scratch: B*(3*C + R) floats. */
+ *           images, fixed order); scratch: B*(3*C + R) floats.
+ * Ranges, else DRS_ERR_ARG (drs_se_forward, drs_se_backward, drs_se_scale_const): pointers not NULL; B, S >= 1, P_out >= 0,
+ * B*(S+2*P_out) <= 65535 (backward: B*S), B*S*S < 2^24; C a multiple of 4 (>= 4); R >= 1; C + R <= 16384 (the excite kernels keep
+ * both vectors in LDS); a slice of C in (ld_out, coff_out) / (ld_g, coff_g), both multiples of 4. */
 int drs_se_forward(const float* act, int B, int S, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
                    float* s, float* e1, float* e2, float* out, int P_out, int ld_out, int coff_out, void* stream);
 int drs_se_backward(const float* gy, int ld_g, int coff_g, const float* act, const float* s, const float* e1, const float* e2,
@@ -203,7 +253,9 @@ int drs_se_backward(const float* gy, int ld_g, int coff_g, const float* act, con
  *           a sweep begins.  scratch: drs_se_core_sums_scratch_doubles(C) doubles.  n * T * T < 2^31.
  * drs_se_gate      : sums [C] over `count` pixels -> s = (float)(sums / count) (fp64 division, one rounding), e1 [R], e2 [C] by
  *           drs_se_forward's excite arithmetic for one image.
- * drs_se_scale_const: out view = act * e2[c] with ONE gate vector e2 [C] for the whole batch (halo zeroed). */
+ * drs_se_scale_const: out view = act * e2[c] with ONE gate vector e2 [C] for the whole batch (halo zeroed).
+ * Ranges, else DRS_ERR_ARG: pointers not NULL.  drs_se_core_sums: C >= 1, 1 <= T <= 65535, 1 <= n <= 65535, n*T*T < 2^31.
+ * drs_se_gate: C, R >= 1, C + R <= 16384, count finite and > 0. */
 int drs_se_core_sums_scratch_doubles(int C);
 int drs_se_core_sums(const float* act, int C, int T, const int* boxes, int n, double* sums, double* scratch, void* stream);
 int drs_se_gate(const double* sums, double count, int C, int R, const float* w1, const float* b1, const float* w2, const float* b2,
@@ -217,7 +269,10 @@ int drs_se_scale_const(const float* act, int B, int S, int C, const float* e2, f
  * w [C][K], K <= 8.  labels == NULL -> inference (logits / pred only).  inv_n = 1 / number of pixels the
  * loss averages over (all ranks).  Per-workgroup slabs (rows = drs_classifier_rows(B,S)):
  * dw_partial [rows][C][K], db_partial [rows][K], loss_partial [rows] (sum of per-pixel CE, fp64).
- * conf: [K][K] counters, ADDED to (integer atomics), rows = label, cols = prediction, gated by acc_mask. */
+ * conf: [K][K] counters, ADDED to (integer atomics), rows = label, cols = prediction, gated by acc_mask.
+ * Ranges, else DRS_ERR_ARG (the three classifier calls): feat, w, bias not NULL; with labels: loss_partial; with gfeat: labels,
+ * dw_partial, db_partial; B, S >= 1, P >= 0, B*S*S < 2^24, B*(S+2P)^2*ld < 2^30; C a multiple of 64, 64..448; K 1..8; inv_n finite
+ * and >= 0; a slice of C in (ld, coff) and, with gfeat, in (ld_g, coff_g), all multiples of 4 (16-byte accesses). */
 int drs_classifier_rows(int B, int S);
 int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
                         const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
@@ -256,7 +311,8 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
                               float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
                               float* db_partial, double* loss_partial, unsigned int* conf, void* stream);
-/* per-class pixel counts of n label bytes (the class-weight recipes): counts[k] += #{i : labels[i] == k}, k < K <= 8, leaving out
+/* Ranges, else DRS_ERR_ARG (drs_label_histogram, drs_reliability_histogram): pointers not NULL; K 1..8; 1 <= n < 2^40.
+ * per-class pixel counts of n label bytes (the class-weight recipes): counts[k] += #{i : labels[i] == k}, k < K <= 8, leaving out
  * labels equal to void_label (-1: none) or >= K; counts = K 64-bit counters on the device, ADDED to (integer atomics: exact and
  * order-independent), so the maps of a pool accumulate over several calls.  n < 2^40. */
 int drs_label_histogram(const unsigned char* labels, size_t n, int K, int void_label, unsigned long long* counts, void* stream);
@@ -283,7 +339,8 @@ int drs_reliability_histogram(const unsigned char* truth, const unsigned char* p
  *   out[4] += A = sum |mu - u_y|                                           the scale G is judged against
  * out = 5 doubles on the device, ADDED to in stream order, so the maps of a split accumulate over several calls.  No float atomics:
  * per-workgroup rows of `scratch` (drs_temperature_scratch_doubles(n) doubles, device) are added in a fixed order by a second
- * launch, and the grid depends on n alone, so two runs give the same bits.  K <= 8, n < 2^40; n == 0 does nothing. */
+ * launch, and the grid depends on n alone, so two runs give the same bits.  K <= 8, n < 2^40; n == 0 does nothing.
+ * Ranges, else DRS_ERR_ARG: pointers not NULL; K 1..8; n < 2^40; beta as above. */
 size_t drs_temperature_scratch_doubles(size_t n);
 int drs_temperature_stats(const float* sums, const unsigned int* occur, const unsigned char* truth, size_t n, int K, int sums_are_prob,
                           int ignore_label, double beta, double* scratch, double* out /* [5] = N, L, G, H, A: ADDED to */, void* stream);
@@ -292,16 +349,19 @@ int drs_temperature_stats(const float* sums, const unsigned int* occur, const un
 int drs_rows_reduce_f32(const float* in, int nrows, int ncols, float* out, double* scratch, void* stream);
 int drs_sum_f64(const double* in, int n, double* out, void* stream);
 int drs_scale_f64(double* x, int n, double s, void* stream);      /* x[i] *= s (the 1/N of the mean cross-entropy) */
-/* tf.nn.l2_loss over the kernels (isprs:646-651): out[0] = 0.5 * sum w^2; scratch = 256 doubles */
+/* tf.nn.l2_loss over the kernels (isprs:646-651): out[0] = 0.5 * sum w^2; scratch = 256 doubles.
+ * Ranges, else DRS_ERR_ARG: pointers not NULL; 1 <= n < 2^40. */
 int drs_l2_loss(const float* w, size_t n, double* scratch, double* out, void* stream);
 
 /* ---- tf.train.MomentumOptimizer(momentum).minimize  (isprs:1685-1687) -----------------------------------
  * g = grad*grad_scale (+ weight_decay*w for the first n_decay entries = the kernels; biases are not decayed,
- * isprs:640-652); accum = momentum*accum + g; w -= lr*accum. */
+ * isprs:640-652); accum = momentum*accum + g; w -= lr*accum.
+ * Ranges, else DRS_ERR_ARG: pointers not NULL; 1 <= n < 2^40; n_decay <= n. */
 int drs_momentum_update(float* w, const float* grad, float* accum, size_t n, size_t n_decay, float lr,
                         float weight_decay, float momentum, float grad_scale, void* stream);
 
-/* ---- calc_accuracy_by_crop / whole-map confusion loops  (isprs:510-531, 1290-1296) ----------------------- */
+/* ---- calc_accuracy_by_crop / whole-map confusion loops  (isprs:510-531, 1290-1296) -----------------------
+ * Ranges, else DRS_ERR_ARG: labels, pred, conf not NULL (mask may be); K 1..8; 1 <= n < 2^32 (conf holds 32-bit counters). */
 int drs_confusion(const unsigned char* labels, const unsigned char* pred, const unsigned char* mask, size_t n, int K,
                   int ignore_label, unsigned int* conf, void* stream);
 
@@ -318,7 +378,10 @@ int drs_confusion(const unsigned char* labels, const unsigned char* pred, const 
  * value, value - mean and (value - mean) / std are each rounded to float16.  NumPy >= 2 evaluates float16-array (op) numpy-scalar in
  * the scalar's type: 1 = mean / std are float32 scalars (what coffee's compute_image_mean yields from its float32 patches, :78-79):
  * float32 arithmetic; 2 = float64 scalars (e.g. statistics read from a float64 .npy): float64 arithmetic.  (NumPy 1.x cast the
- * scalar to float16 first: not reproduced.) */
+ * scalar to float16 first: not reproduced.)
+ * Ranges, else DRS_ERR_ARG (drs_crop_normalize and drs_crop_normalize_scaled): tiles, labels, tile_off, lab_off, tile_h, tile_w, inst,
+ * out, mean3, std3 (and geo) not NULL; rot, rot_on, noise, noise_on, out_lab, out_mask may be; C 1..8; ld >= C, a multiple of 4
+ * (16-byte stores); B, S >= 1, P >= 0, B*(S+2P) <= 65535 (grid.y); noise_index0 >= 0; quantize_f16 0..2; n_maps >= 1. */
 int drs_crop_normalize(const void* tiles, int tiles_are_f64, const unsigned char* labels, const long long* tile_off,
                        const long long* lab_off, const int* tile_h, const int* tile_w, int C, const int* inst,
                        const double* rot, const unsigned char* rot_on, const double* noise,
@@ -362,7 +425,12 @@ int drs_crop_normalize_scaled(const void* tiles, int tiles_are_f64, const unsign
 
 /* ---- overlap-add of window logits and arg-max of the average  (isprs:1261-1284, 1925-1949) ---------------
  * windows [first_window, first_window + n_windows) of the row-major window grid at `stride` (last row/col
- * shifted back to the border) are added, in that order, into prob [h][w][K] / occur [h][w]. */
+ * shifted back to the border) are added, in that order, into prob [h][w][K] / occur [h][w].
+ * THE STRIDE LIMIT: a coordinate may lie under at most 5 regular windows per axis, plus the shifted-back one -- the kernel lists a
+ * pixel's windows in fixed arrays of 6 -- so ceil(S / stride) <= 5.  The reference's stride is floor(S / 2) (isprs:1243): 2 or 3.
+ * Ranges, else DRS_ERR_ARG: pointers not NULL; K 1..8; h, w >= 1; 1 <= S <= min(h, w); stride >= 1 and (S + stride - 1) / stride <= 5;
+ * first_window >= 0, n_windows >= 1, first_window + n_windows <= n_h * n_w (the window grid; n_h * n_w < 2^31); the image rows a call
+ * touches <= 65535 (grid.y).  drs_stitch_finalize, drs_softmax_accumulate (below): pointers not NULL, K 1..8, h, w >= 1. */
 int drs_stitch_accumulate(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int S, int stride,
                           int first_window, int n_windows, void* stream);
 int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int w, int K, unsigned char* out,
@@ -372,7 +440,9 @@ int drs_stitch_finalize(const float* prob, const unsigned int* occur, int h, int
  * core pixel (y, x) the K logits logits[i][y - y0][x - x0][:] (a [n][T][T][K] block, as drs_forward writes it) are COPIED into
  * prob[y][x][:] and occur[y][x] += 1.  Labels: drs_stitch_finalize (occur = 1: an exact arg-max, first maximum).  K <= 8,
  * T <= min(h, w); the boxes are device data, checked on the device: a box outside the image or outside its tile places nothing (the
- * coverage count occur, 1 everywhere after a whole plan, shows the gap).  The tile plan itself is the host's. */
+ * coverage count occur, 1 everywhere after a whole plan, shows the gap).  The tile plan itself is the host's.
+ * Ranges, else DRS_ERR_ARG (drs_tile_place and drs_tile_place_dihedral): pointers not NULL; K 1..8; 1 <= T <= min(h, w), T <= 65535;
+ * 1 <= n <= 65535 (grid.y, grid.z); g 0..7. */
 int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h, int w, int K, int T, const int* boxes, int n,
                    void* stream);
 /* dihedral test-time augmentation of overlap-tile inference (opt-in).  A transform code g in 0..7 is one of the 8
@@ -389,7 +459,9 @@ int drs_tile_place(float* prob, unsigned int* occur, const float* logits, int h,
  * drs_crop_normalize with flip 0 and no augmentation, bit for bit.
  * drs_tile_place_dihedral: boxes as drs_tile_place (same device-side checks); for every core pixel (y, x) at tile-local
  * (a, b) = (y - y0, x - x0), softmax_k(logits[i][sigma_g^-1(a, b)][:]) (max-subtracted, fp32, classes summed in order) is ADDED
- * into acc[y][x][:] and occur[y][x] += 1.  K <= 8.  The cores of one call must be disjoint (plain read-modify-write of acc). */
+ * into acc[y][x][:] and occur[y][x] += 1.  K <= 8.  The cores of one call must be disjoint (plain read-modify-write of acc).
+ * Ranges, else DRS_ERR_ARG (drs_crop_dihedral, and drs_crop_resampled below): pointers not NULL (mean3, std3 HOST); n_maps >= 1; C 1..8;
+ * ld >= C, a multiple of 4; g 0..7; B, T >= 1, P >= 0, B*(T+2P) <= 65535; drs_crop_resampled: hs, ws >= 1. */
 int drs_crop_dihedral(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
                       int C, const int* inst, int g, const double* mean3, const double* std3, int B, int T, int P, int ld, float* out,
                       void* stream);
@@ -410,7 +482,8 @@ int drs_tile_place_dihedral(float* acc, unsigned int* occur, const float* logits
  * drs_resample_accumulate: acc[h][w][K] += U(hs x ws -> h x w) of the class-probability map of src [hs][ws][K]: the vector of a
  * source pixel q is src[q] / occur[q] when src_is_prob (a sum of probabilities), else the max-subtracted fp32 softmax of
  * src[q] / occur[q] as drs_tile_place_dihedral forms it (logits); occur 0 counts as 1.  Coordinates and weights in fp64, the four
- * vectors mixed in fp32 in the order of D above.  K <= 8, h <= 65535.  At hs == h and ws == w it is acc += vector, bit for bit. */
+ * vectors mixed in fp32 in the order of D above.  K <= 8, h <= 65535.  At hs == h and ws == w it is acc += vector, bit for bit.
+ * Ranges, else DRS_ERR_ARG (drs_resample_accumulate): pointers not NULL; K 1..8; hs, ws, h, w >= 1; h <= 65535 (grid.y). */
 int drs_crop_resampled(const void* tiles, int tiles_are_f64, const long long* tile_off, const int* tile_h, const int* tile_w, int n_maps,
                        int C, const int* inst, int hs, int ws, int g, const double* mean3, const double* std3, int B, int T, int P, int ld,
                        float* out, void* stream);
@@ -427,7 +500,8 @@ int drs_resample_accumulate(const float* src, const unsigned int* occur, int hs,
  *                  the exponentials, so that no logarithm of an underflowed p_k is taken   (K == 1: 0)
  * Each score s is clamped to [0, 1] and stored as (unsigned char)(int)(255 s + 0.5f).  An uncovered pixel (occur[i] == 0) gets its
  * label as before and confidence 0, margin 0, entropy 255.  Any of the four outputs may be NULL (it is then neither computed for nor
- * written); all four NULL is DRS_ERR_ARG.  K <= 8. */
+ * written); all four NULL is DRS_ERR_ARG.  K <= 8.
+ * Ranges, else DRS_ERR_ARG (and drs_stitch_finalize_scores_t): sums, occur not NULL; one output at least; K 1..8; h, w >= 1. */
 int drs_stitch_finalize_scores(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob,
                                unsigned char* labels, unsigned char* confidence, unsigned char* margin, unsigned char* entropy,
                                void* stream);
@@ -461,7 +535,8 @@ int drs_stitch_finalize_scores_t(const float* sums, const unsigned int* occur, i
  *     on the host in fp64, the appearance factor is one exp2 per neighbour.  No atomics: a pixel's bits depend neither on the
  *     workgroup tiling nor on how the rows are cut into calls.  Ranges, else DRS_ERR_ARG: K 2..8, C 1..8, R 1..6, step 1..4,
  *     R * step <= 12, w_app, w_smooth finite >= 0, theta_* finite > 0, 0 <= row0, 1 <= rows, row0 + rows <= h.
- * Labels and score maps of the refined posterior: drs_stitch_finalize / drs_stitch_finalize_scores on (Q, live, sums_are_prob = 1). */
+ * Labels and score maps of the refined posterior: drs_stitch_finalize / drs_stitch_finalize_scores on (Q, live, sums_are_prob = 1).
+ * drs_crf_unary ranges, else DRS_ERR_ARG: pointers not NULL; h, w >= 1; K 2..8; beta as above.  drs_crf_step also: pointers not NULL. */
 int drs_crf_unary(const float* sums, const unsigned int* occur, int h, int w, int K, int sums_are_prob, float beta, float* logp, float* q0,
                   unsigned int* live, void* stream);
 int drs_crf_step(const float* q_in, const float* logp, const unsigned int* live, const void* tile, int tile_is_f64, int C, int h, int w,
