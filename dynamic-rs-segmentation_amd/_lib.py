@@ -86,6 +86,11 @@ SIGNATURES = {
     "drs_boundary_distance": (_i, [_p, _i, _i, _i, _p, _p]),
     "drs_boundary_histogram": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p]),
     "drs_scale_f64": (_i, [_p, _i, _d, _p]),
+    # ---- whole-map level (csrc/components.hip)
+    "drs_components": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "drs_sieve_scratch_bytes": (_sz, [_i, _i]),
+    "drs_sieve_round": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "drs_component_census": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     # ---- step level (csrc/engine.hip)
     "drs_net_create": (_i, [C.c_char_p, _i, _i, _f, _i, _i, _i, _f, C.POINTER(_p)]),
     "drs_net_destroy": (None, [_p]),

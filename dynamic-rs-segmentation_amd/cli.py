@@ -27,6 +27,12 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
   + optionally, anywhere, `--boundary-scores[=d0,d1,...]` (validate_test; any inference path, with or without --crf): one more line per
     map and for all maps with the trimap accuracy and the Boundary IoU at the distances given (pixels; 1 to 8 ascending integers in
     1..16; the bare flag means 1,2,4,8) and the plain IoU (loops.validate_test's boundary_scores)
+  + optionally, anywhere, `--sieve=N|n0,n1,...,n5` (validate_test / generate_final_maps; any inference path, with or without --crf):
+    a minimum mapping unit: every map is sieved before anything scores or writes it -- connected regions of a class k below n_k pixels
+    (N: the same threshold for every class; 0: leave the class alone) merge into their largest neighbouring region that is itself large
+    enough, round after round until none is left (loops.sieve_labels); one `Sieve` line per map and for all maps.
+    `--sieve-connectivity=4|8` (default 4; with --sieve only) says what holds a region together.  Score maps and calibration lines
+    stay those of the unsieved labels
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -214,6 +220,32 @@ def parse_boundary_scores(argv):
         % (BOUNDARY_FLAG, BOUNDARY_FLAG, P.BOUNDARY_MAX_DISTANCES, P.BOUNDARY_MAX_REACH)), bare=P.BOUNDARY_DEFAULT)
 
 
+SIEVE_FLAG = "--sieve"
+SIEVE_CONNECTIVITY_FLAG = "--sieve-connectivity"
+
+
+def parse_sieve(argv, num_classes=None):
+    """isprs flavour: the optional `--sieve=N|n0,n1,...` and `--sieve-connectivity=4|8` (anywhere in argv; validate_test /
+    generate_final_maps, which main checks).  Returns (argv without the flags, the patches.SieveParams of patches.check_sieve), or
+    (argv unchanged, None) without either.  A bare --sieve, a malformed or out-of-range value, a count of thresholds other than 1 or
+    num_classes (when given), --sieve-connectivity without --sieve, or a flag given twice, raises ValueError."""
+    form = "%s=N or %s=n0,n1,... (%s integers in 0..2^30, pixels)" % (SIEVE_FLAG, SIEVE_FLAG,
+                                                                     "one or one per class:" if num_classes is None else "1 or %d" % num_classes)
+
+    def sizes(a, v):
+        ms = _or_expected(P.parse_sieve, a, v, form)
+        if num_classes is not None and len(ms) not in (1, num_classes):
+            raise ValueError("%s: %d thresholds given, expected %s" % (a, len(ms), form))
+        return ms
+    argv, min_size = _take_flag(argv, SIEVE_FLAG, sizes)
+    argv, conn = _take_flag(argv, SIEVE_CONNECTIVITY_FLAG, _one_of(("4", "8"), SIEVE_CONNECTIVITY_FLAG))
+    if min_size is None:
+        if conn is not None:
+            raise ValueError(SIEVE_CONNECTIVITY_FLAG + " applies to the sieve only: give " + SIEVE_FLAG + " as well")
+        return argv, None
+    return argv, P.check_sieve(dict(min_size=min_size, connectivity=P.SIEVE_CONNECTIVITY if conn is None else int(conn)))
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -317,6 +349,7 @@ def main(argv=None, device=None, comm=None):
         argv, temperature = parse_temperature(argv)
         argv, crf = parse_crf(argv)
         argv, boundary = parse_boundary_scores(argv)
+        argv, sieve = parse_sieve(argv, 6)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
@@ -348,6 +381,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(CRF_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if boundary is not None and argv[16] != "validate_test":
         sys.exit(BOUNDARY_FLAG + " applies to the validate_test process only")
+    if sieve is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(SIEVE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -424,6 +459,7 @@ def main(argv=None, device=None, comm=None):
     path_kw = dict(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     crf_kw = {} if crf is None else dict(crf=crf)          # without the flag the loops are called as they always were
     boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
+    sieve_kw = {} if sieve is None else dict(sieve=sieve)
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
@@ -438,11 +474,12 @@ def main(argv=None, device=None, comm=None):
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
                                    step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                   **boundary_kw)
+                                   **boundary_kw, **sieve_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
-                                         score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw)
+                                         score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
+                                         **sieve_kw)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

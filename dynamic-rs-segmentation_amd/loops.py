@@ -12,6 +12,7 @@ side files), with every per-pixel operation on the device.  Differences that are
   * under data parallelism every rank runs the same host code with the same RNG streams and takes its slice of the batch.
 """
 import collections
+import contextlib
 import ctypes
 import datetime
 import math
@@ -1050,6 +1051,98 @@ def _boundary_str(b):
             " Mean IoU= " + "{:.6f}".format(b["mean_iou"]))
 
 
+def _on_stream(dev, stream):
+    """context in which torch's own operations run on the raw stream handle `stream` (None: torch's current stream on dev, as it is)"""
+    return contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev))
+
+
+def components(map_dev, h, w, connectivity, stream=None):
+    """Connected components of a uint8 device map [h][w] (drs_components; include/drs.h): (label, size) as device
+    tensors [h, w], label int32 = the smallest linear index y w + x of the pixel's component, size int32 = its pixel count (at most
+    2^30), at every pixel.  connectivity 4 or 8.  stream: a raw stream handle (default: torch's current stream on the map's device)."""
+    from . import _lib
+    if connectivity not in (4, 8):
+        raise ValueError("components: connectivity %r, expected 4 or 8" % (connectivity,))
+    if map_dev.dtype != torch.uint8 or map_dev.numel() != h * w or not map_dev.is_contiguous():
+        raise ValueError("components: the map must be a contiguous uint8 tensor of %d x %d elements" % (h, w))
+    with _on_stream(map_dev.device, stream):
+        st = torch.cuda.current_stream(map_dev.device).cuda_stream
+        label = torch.empty((h, w), dtype=torch.int32, device=map_dev.device)
+        size = torch.empty((h, w), dtype=torch.int32, device=map_dev.device)
+        _lib.call("drs_components", map_dev.data_ptr(), int(h), int(w), int(connectivity), label.data_ptr(), size.data_ptr(), st)
+    return label, size
+
+
+def sieve_labels(map_dev, h, w, K, sieve, stream=None):
+    """The sieve of a uint8 device map [h][w] of K classes (include/drs.h): a minimum mapping unit.  sieve: what
+    patches.check_sieve accepts (one threshold or K of them, in pixels; connectivity 4 or 8).  Components (drs_components), then one
+    round (drs_sieve_round: every component of a class k below min_size[k] pixels takes the class of its largest 4-neighbouring
+    region that is not small itself, ties to the lower class), again until a round merges nothing or patches.SIEVE_MAX_ROUNDS rounds
+    have run; the host reads two counters per round.  Bytes >= K never change.  Returns (the sieved map, a new uint8 device tensor
+    shaped like map_dev, info) with info = {"rounds": rounds run, the last one, which merged nothing, included; "merged": components
+    merged over all rounds; "left_small": small components of the result (0 wherever some component of a class is not small);
+    "changed_pixels"; "objects_before" / "objects_after": K component counts each (drs_component_census); "capped": the loop ended at
+    SIEVE_MAX_ROUNDS}.  stream: a raw stream handle (default: torch's current stream on the map's device)."""
+    from . import _lib
+    sieve = P.check_sieve(sieve)
+    min_size = P.sieve_thresholds(sieve, K)
+    if map_dev.dtype != torch.uint8 or map_dev.numel() != h * w or not map_dev.is_contiguous():
+        raise ValueError("sieve_labels: the map must be a contiguous uint8 tensor of %d x %d elements" % (h, w))
+    dev, n = map_dev.device, h * w
+    host_min = (ctypes.c_int * K)(*min_size)
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        cur = map_dev.clone()
+        label = torch.empty(n, dtype=torch.int32, device=dev)
+        size = torch.empty(n, dtype=torch.int32, device=dev)
+        scratch = torch.empty(_lib.query("drs_sieve_scratch_bytes", int(h), int(w)) // 8, dtype=torch.int64, device=dev)
+        counters = torch.empty(2, dtype=torch.int32, device=dev)
+
+        def label_them():
+            _lib.call("drs_components", cur.data_ptr(), int(h), int(w), sieve.connectivity, label.data_ptr(), size.data_ptr(), st)
+
+        def objects():
+            table = torch.zeros((K, 32), dtype=torch.int64, device=dev)
+            _lib.call("drs_component_census", cur.data_ptr(), label.data_ptr(), size.data_ptr(), int(h), int(w), int(K), table.data_ptr(), st)
+            return [int(v) for v in table.sum(dim=1).cpu().tolist()]
+
+        def one_round(out):
+            _lib.call("drs_sieve_round", cur.data_ptr(), label.data_ptr(), size.data_ptr(), int(h), int(w), int(K),
+                      ctypes.addressof(host_min), scratch.data_ptr(), out.data_ptr(), counters.data_ptr(), st)
+            return [int(v) for v in counters.cpu().tolist()]
+        rounds = merged = 0
+        capped = False
+        while True:
+            label_them()
+            if rounds == 0:
+                before = objects()
+            left, now = one_round(cur)                     # in place
+            rounds += 1
+            merged += now
+            if now == 0:
+                break                                      # nothing moved: label and size are those of the result
+            if rounds == P.SIEVE_MAX_ROUNDS:
+                capped = True
+                label_them()
+                left = one_round(torch.empty_like(cur))[0]     # counted only: the result is `cur`
+                break
+        info = {"rounds": rounds, "merged": merged, "left_small": left, "changed_pixels": int((cur != map_dev).sum().item()),
+                "objects_before": before, "objects_after": objects(), "capped": capped}
+    return cur, info
+
+
+def _sieve_str(sieve, infos):
+    """the Sieve line's text from one sieve_labels info, or from those of all maps (counts summed, the most rounds)"""
+    infos = infos if isinstance(infos, list) else [infos]
+    total = lambda key: [sum(i[key][k] for i in infos) for k in range(len(infos[0][key]))]
+    return ("Sieve min= " + " ".join(str(v) for v in sieve.min_size) + " connectivity= " + str(sieve.connectivity) +
+            " Rounds= " + str(max(i["rounds"] for i in infos)) +
+            " Merged Components= " + str(sum(i["merged"] for i in infos)) +
+            " Changed Pixels= " + str(sum(i["changed_pixels"] for i in infos)) +
+            " Objects per class= [" + " ".join(str(v) for v in total("objects_before")) + "] -> [" +
+            " ".join(str(v) for v in total("objects_after")) + "]")
+
+
 FIT_RESIDENT_BYTES = 32 << 30       # default cap on the accumulators fit_temperature keeps on the device
 
 
@@ -1101,7 +1194,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
                   dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None,
-                  boundary_scores=None):
+                  boundary_scores=None, sieve=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1128,7 +1221,17 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     IoU per class= ... Mean IoU= ...` follows the reference-format line (and the Calibration line where there is one), per map and
     for all maps from the summed table.  Returns (all-maps confusion matrix, label maps, extra) with extra["boundary"] =
     metrics.boundary_scores of the all-maps table, plus "per_map": [the same per map] and "hist": the int64 numpy table; the score-map
-    keys are in extra only when score_maps is given too.  Without boundary_scores nothing changes."""
+    keys are in extra only when score_maps is given too.  Without boundary_scores nothing changes.
+    sieve (opt-in; any inference path; what patches.check_sieve accepts: one threshold in pixels or one per class, and a
+    connectivity): a minimum mapping unit (sieve_labels).  The map the path returns -- the refined map with crf -- is
+    sieved before anything scores it: confusion matrix, accuracy, F1, kappa, the boundary scores and the returned maps are those of
+    the sieved map.  Score maps and Calibration lines describe the posterior and stay those of the UNSIEVED labels: a sieved pixel's
+    label is no longer its winning class.  Every rank sieves the whole map itself and gets the same bits.  One line
+    `---- Iter N -- Test Map M: Sieve min= ... connectivity= c Rounds= r Merged Components= n Changed Pixels= p Objects per class=
+    [before] -> [after]` follows the map's other lines, and one for all maps (counts summed, the most rounds) the all-maps lines.
+    Returns (all-maps confusion matrix, label maps, extra) with extra["sieve"] = {"params": the SieveParams, "per_map": [sieve_labels'
+    info per map], "rounds" (the most), "merged", "changed_pixels", "left_small", "objects_before", "objects_after" (summed)}.  Without
+    sieve nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
@@ -1136,6 +1239,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     crf = None if crf is None else P.check_crf(crf)
     beta = _check_temperature(temperature_beta, score_maps, crf)
     bdist = None if boundary_scores is None else P.check_boundary_distances(boundary_scores)
+    sieve = None if sieve is None else P.check_sieve(sieve)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
@@ -1144,6 +1248,9 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         all_hist = np.zeros((256, 2), dtype=np.int64)
         score_list, cal_list = [], []
     K = net.plan.K
+    if sieve is not None:
+        P.sieve_thresholds(sieve, K)
+        sieve_list = []
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
     all_kappa = np.zeros(len(testing_data), dtype=np.float32)
@@ -1156,6 +1263,10 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     for k in range(len(testing_data)):
         pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
+        voted = pred                                       # the labels the posterior voted for: what the score maps describe
+        if sieve is not None:
+            pred, sinfo = sieve_labels(pred, h, w, K, sieve, stream=net._stream())
+            sieve_list.append(sinfo)
         conf = torch.zeros(K * K, dtype=torch.int32, device=net.dev)
         lab = pool.labels[int(pool.lab_off[k].item()):int(pool.lab_off[k].item()) + h * w]
         _lib.call("drs_confusion", lab.data_ptr(), pred.data_ptr(), None, h * w, K, ignore_label, conf.data_ptr(), net._stream())
@@ -1179,7 +1290,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
                   " Confusion Matrix= " + _cm_str(cm))
         if kinds is not None:
             hist = torch.zeros(512, dtype=torch.int64, device=net.dev)
-            _lib.call("drs_reliability_histogram", lab.data_ptr(), pred.data_ptr(), smaps["confidence"].data_ptr(), h * w, K, ignore_label,
+            _lib.call("drs_reliability_histogram", lab.data_ptr(), voted.data_ptr(), smaps["confidence"].data_ptr(), h * w, K, ignore_label,
                       hist.data_ptr(), net._stream())
             hist = hist.cpu().numpy().reshape(256, 2)
             all_hist += hist
@@ -1193,6 +1304,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             boundary_list.append(MT.boundary_scores(bhist, bdist))
             if comm.rank == 0:
                 print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _boundary_str(boundary_list[-1]))
+        if sieve is not None and comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _sieve_str(sieve, sinfo))
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -1220,7 +1333,16 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _boundary_str(bnd))
         extra = dict(extra if kinds is not None else {}, boundary=bnd)
-    if kinds is not None or bdist is not None:
+    if sieve is not None:
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _sieve_str(sieve, sieve_list))
+        sv = {"params": sieve, "per_map": sieve_list, "rounds": max([i["rounds"] for i in sieve_list] or [0])}
+        for key in ("merged", "changed_pixels", "left_small"):
+            sv[key] = sum(i[key] for i in sieve_list)
+        for key in ("objects_before", "objects_after"):
+            sv[key] = [sum(i[key][c] for i in sieve_list) for c in range(K)]
+        extra = dict(extra if kinds is not None or bdist is not None else {}, sieve=sv)
+    if kinds is not None or bdist is not None or sieve is not None:
         return all_cm, maps, extra
     return all_cm, maps
 
@@ -1228,7 +1350,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
                         dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None,
-                        crf=None):
+                        crf=None, sieve=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
@@ -1241,13 +1363,18 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     temperature): the score files are of the calibrated probabilities; the label files do not change.
     crf (opt-in; any inference path; what patches.check_crf accepts): the written maps and score maps are those of the path's
     posterior refined by a local dense CRF against the image (refine_crf).  With crf a temperature_beta is accepted
-    without score_maps: it scales the unary, so with a CRF it CAN change the label files."""
+    without score_maps: it scales the unary, so with a CRF it CAN change the label files.
+    sieve (opt-in; any inference path; what patches.check_sieve accepts): the written and returned maps are sieved to a minimum
+    mapping unit first (sieve_labels), the refined map with crf; the score files stay those of the unsieved labels."""
     comm = comm or NoComm()
     path = InferencePath(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     path.check()
     crf = None if crf is None else P.check_crf(crf)
     beta = _check_temperature(temperature_beta, score_maps, crf)
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
+    sieve = None if sieve is None else P.check_sieve(sieve)
+    if sieve is not None:
+        P.sieve_thresholds(sieve, net.plan.K)
     score_list = []
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
     if dense_tile is None:
@@ -1257,6 +1384,8 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     maps = []
     for k in range(len(testing_data)):
         pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
+        if sieve is not None:
+            pred, _ = sieve_labels(pred, pool.h[k], pool.w[k], net.plan.K, sieve, stream=net._stream())
         maps.append(pred.cpu().numpy())
         if kinds is not None:
             score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})

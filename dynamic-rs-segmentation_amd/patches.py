@@ -525,6 +525,67 @@ def parse_boundary_scores(text):
     return check_boundary_distances([int(t) for t in parts])
 
 
+# ------------------------------------------------------------------- sieve of whole-map labels: a minimum mapping unit
+SIEVE_MAX_ROUNDS = 64
+SIEVE_CONNECTIVITY = 4                     # gdal_sieve's default
+SIEVE_MAX_CLASSES, SIEVE_MAX_SIZE = 32, 1 << 30        # the ranges include/drs.h accepts
+SieveParams = collections.namedtuple("SieveParams", "min_size connectivity")
+
+
+def _sieve_size(v, of):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) <= SIEVE_MAX_SIZE:
+        raise ValueError("sieve threshold %r%s: expected an integer in 0..2^30 (pixels)" % (v, of))
+    return int(v)
+
+
+def check_sieve(spec):
+    """The sieve's parameters as SieveParams(min_size, connectivity).  spec: an int (one threshold in pixels for every class), a
+    sequence of 1 to 32 ints (one per class; loops.sieve_labels wants exactly K or one), a dict {"min_size": either of those,
+    "connectivity": 4 | 8} (connectivity optional), or a SieveParams.  min_size comes back as a tuple of ints in 0..2^30 -- of ONE
+    int for a scalar spec: it stands for every class --, connectivity as 4 (the default, gdal_sieve's) or 8.  Anything else raises
+    ValueError naming the offending value."""
+    connectivity = SIEVE_CONNECTIVITY
+    if isinstance(spec, SieveParams):
+        spec = spec._asdict()
+    if isinstance(spec, dict):
+        unknown = sorted(set(spec) - {"min_size", "connectivity"})
+        if unknown or "min_size" not in spec:
+            raise ValueError("sieve %r: expected the keys min_size and, optionally, connectivity%s"
+                             % (spec, "; unknown: " + ", ".join(map(repr, unknown)) if unknown else ""))
+        connectivity = spec.get("connectivity", SIEVE_CONNECTIVITY)
+        if isinstance(connectivity, bool) or not isinstance(connectivity, (int, np.integer)) or int(connectivity) not in (4, 8):
+            raise ValueError("sieve connectivity %r: expected 4 or 8" % (connectivity,))
+        spec = spec["min_size"]
+    if isinstance(spec, (int, np.integer)) and not isinstance(spec, bool):
+        return SieveParams((_sieve_size(spec, ""),), int(connectivity))
+    if isinstance(spec, (str, bytes)) or not isinstance(spec, (tuple, list, np.ndarray)) or not 1 <= len(spec) <= SIEVE_MAX_CLASSES:
+        raise ValueError("sieve thresholds %r: expected an integer or 1 to %d integers in 0..2^30, one per class" % (spec, SIEVE_MAX_CLASSES))
+    return SieveParams(tuple(_sieve_size(v, " of %r" % (tuple(spec),)) for v in spec), int(connectivity))
+
+
+def sieve_thresholds(sieve, K):
+    """the K thresholds of a SieveParams for a net of K classes; a count other than 1 or K raises ValueError"""
+    if not 1 <= K <= SIEVE_MAX_CLASSES:
+        raise ValueError("sieve: %r classes, expected 1..%d" % (K, SIEVE_MAX_CLASSES))
+    if len(sieve.min_size) == 1:
+        return sieve.min_size * K
+    if len(sieve.min_size) != K:
+        raise ValueError("sieve thresholds %r: %d given, expected 1 or %d (one per class)" % (sieve.min_size, len(sieve.min_size), K))
+    return sieve.min_size
+
+
+def parse_sieve(text):
+    """The value of the command line's --sieve option: "N" or "n0,n1,..." as check_sieve's min_size (a tuple of ints).  An empty
+    value, blanks, or anything that is not a plain decimal integer raise ValueError."""
+    parts = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else []
+    for t in parts:
+        if not (t.isascii() and t.isdigit()):
+            raise ValueError("sieve threshold %r of %r: expected integers, comma-separated (e.g. 16 or 32,32,8,32,4,0)" % (t, text))
+    if not parts:
+        raise ValueError("sieve thresholds %r: expected integers, comma-separated (e.g. 16 or 32,32,8,32,4,0)" % (text,))
+    return check_sieve([int(t) for t in parts]).min_size
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

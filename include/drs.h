@@ -724,6 +724,44 @@ int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
 int drs_net_timing_summary(drs_net_t* net, int kind, char* name, int name_cap, int* launches, double* ms, double* work);
 
+/* ==================================================================================================================
+ * Whole-map level: objects of a finished label map (opt-in; csrc/components.hip).  Connected components, the sieve
+ * round that enforces a minimum mapping unit, and the object census.  NORMATIVE: this text and the numpy statement tests/sieve_ref.py.
+ * Label-only and integer-only: every output is exact and independent of tiling and scheduling.
+ * Inputs: a byte map m, uint8 [h][w] on the device (a byte is just a byte, as in drs_boundary_*); a connectivity c in {4, 8}; a class
+ *     count K; K HOST ints min_size[k] >= 0.
+ * Components: a component is a maximal c-connected set of pixels that carry the same byte.  label[p] = the smallest linear index
+ *     y w + x over the pixels of p's component (int32); size[p] = that component's pixel count (uint32), stored at EVERY pixel of
+ *     the component.  The edge of the map connects nothing.
+ * Small: a component of byte b is small iff b < K and size < min_size[b].  Bytes >= K are never small, never change, never spread.
+ * One round (synchronous: everything is decided on the map as it stands at the start of the round): for a small component S take
+ *     every pair (p, q), p in S, q one of p's FOUR edge neighbours inside the map (whatever c is), with m[q] != m[p], m[q] < K and q's
+ *     component NOT small.  Each pair offers the key (size[q], 255 - m[q]); S takes the byte of the lexicographically largest key:
+ *     the largest non-small neighbour region, ties to the lower class byte.  A small component without such a pair stays as it is in
+ *     this round.  All relabelling happens after all keys are chosen.
+ * The sieve (the host's loop, loops.sieve_labels): components, then a round, repeated until a round merges nothing or 64 rounds
+ *     have run.  Only non-small regions attract, so components only coarsen and the loop ends with no small component
+ *     left wherever a non-small component of a byte < K exists; a map without one comes back unchanged.
+ * Census: for every component whose byte is < K, table[byte][floor(log2(size))] += 1.
+ *
+ * drs_components: label and size of map at connectivity 4 or 8 (four launches: tiles in LDS, tile borders on the global forest --
+ *     label[] is parent[] --, flatten + count, spread).
+ * drs_sieve_scratch_bytes: bytes of drs_sieve_round's scratch for an h x w map (8 h w); 0 outside the ranges.
+ * drs_sieve_round: one round from map_in to map_out (map_out == map_in, in place, is allowed); label and size are those of
+ *     drs_components on map_in at the caller's connectivity.  The round initialises what it reads of its scratch: the result does
+ *     not depend on what the scratch held.  counters = device uint32 [2], STORED: [0] the small components at the start of the
+ *     round, [1] those of them that merged.  min_size = K HOST ints, copied into the launch.
+ * drs_component_census: table = [K][32] 64-bit device counters, ADDED to.
+ * No entry point synchronises: the host reads counters between rounds.
+ * Ranges, else DRS_ERR_ARG (nothing is launched, no host pointer is read): pointers not NULL; h, w >= 1, h w <= 2^30; connectivity
+ * 4 or 8; 1 <= K <= 32; 0 <= min_size[k] <= 2^30. */
+int drs_components(const unsigned char* map, int h, int w, int connectivity, int* label, unsigned int* size, void* stream);
+size_t drs_sieve_scratch_bytes(int h, int w);
+int drs_sieve_round(const unsigned char* map_in, const int* label, const unsigned int* size, int h, int w, int K, const int* min_size,
+                    void* scratch, unsigned char* map_out, unsigned int* counters, void* stream);
+int drs_component_census(const unsigned char* map, const int* label, const unsigned int* size, int h, int w, int K,
+                         unsigned long long* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
