@@ -37,6 +37,10 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
     of the focal loss, 0 or in (0, 8] (loops.train's focal_gamma)
+  + optionally, anywhere, in all three flavours, `--boundary-weight=a[,sigma[,R]]` (training; on top of --class-weights and
+    --focal-gamma): every pixel's loss term is multiplied by 1 + a exp(-d^2 / 2 sigma^2), d the distance to the nearest pixel of
+    another class inside the patch and a (2R + 1)^2 window; a in [-1, 64] (0: off), sigma in (0, 64] (default 4), R in 1..16
+    (default min(16, ceil(3 sigma))) (loops.train's boundary_weight)
   + optionally, anywhere, in all three flavours, `--scale-jitter=lo,hi` (training): every training patch is resampled at a scale
     drawn log-uniformly from [lo, hi], 0.25 <= lo <= hi <= 4 (loops.train's scale_jitter); validation and inference
     stay at scale 1
@@ -275,6 +279,18 @@ def parse_focal_gamma(argv):
         P.parse_focal_gamma, a, v, "%s=G (one number, 0 or finite in (0, %g])" % (FOCAL_GAMMA_FLAG, P.MAX_FOCAL_GAMMA)))
 
 
+BOUNDARY_WEIGHT_FLAG = "--boundary-weight"
+
+
+def parse_boundary_weight(argv):
+    """all flavours: the optional `--boundary-weight=a[,sigma[,R]]` (anywhere in argv; training).  Returns (argv without the flag,
+    (a, sigma, R) with the defaults filled in), or (argv unchanged, None) without it.  A bare flag, a value outside the ranges of
+    patches.check_boundary_weight, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, BOUNDARY_WEIGHT_FLAG, lambda a, v: _or_expected(
+        P.parse_boundary_weight, a, v, "%s=a[,sigma[,R]] (a in [-1, %g], sigma in (0, %g], R an integer in 1..%d)" % (
+            BOUNDARY_WEIGHT_FLAG, P.MAX_BOUNDARY_A, P.MAX_BOUNDARY_SIGMA, P.MAX_BOUNDARY_R)))
+
+
 SCALE_JITTER_FLAG = "--scale-jitter"
 
 
@@ -352,6 +368,7 @@ def main(argv=None, device=None, comm=None):
         argv, sieve = parse_sieve(argv, 6)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, boundary_weight = parse_boundary_weight(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -387,6 +404,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the training process only")
+    if boundary_weight is not None and argv[16] != "training":
+        sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the training process only")
     if scale_jitter is not None and argv[16] != "training":
         sys.exit(SCALE_JITTER_FLAG + " applies to the training process only")
     if comm.rank == 0:
@@ -438,7 +457,8 @@ def main(argv=None, device=None, comm=None):
                            testing_instances, lr_initial, batch_size, niter, weight_decay, mean_full, std_full, update_type,
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
-                           class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter)
+                           class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter,
+                           boundary_weight=boundary_weight)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -510,6 +530,7 @@ def main_coffee(argv=None, device=None, comm=None):
     try:
         argv, class_weights = parse_class_weights(argv, 2)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, boundary_weight = parse_boundary_weight(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -529,7 +550,7 @@ def main_coffee(argv=None, device=None, comm=None):
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
                     quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma,     # coffee:293: training patches pass through float16
-                    scale_jitter=scale_jitter)
+                    scale_jitter=scale_jitter, boundary_weight=boundary_weight)
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -540,6 +561,7 @@ def main_contest(argv=None, device=None, comm=None):
     try:
         argv, class_weights = parse_class_weights(argv, 7)
         argv, focal_gamma = parse_focal_gamma(argv)
+        argv, boundary_weight = parse_boundary_weight(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -550,6 +572,8 @@ def main_contest(argv=None, device=None, comm=None):
     path, output_path, current_model, lr, wd, bs, niter, crop, stride, net_type, dist, pv, update_type, operation = argv[1:15]
     if focal_gamma is not None and operation != "train":
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the train operation only")
+    if boundary_weight is not None and operation != "train":
+        sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the train operation only")
     if scale_jitter is not None and operation != "train":
         sys.exit(SCALE_JITTER_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
@@ -569,7 +593,7 @@ def main_contest(argv=None, device=None, comm=None):
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
                         void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
-                        focal_gamma=focal_gamma, scale_jitter=scale_jitter)
+                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

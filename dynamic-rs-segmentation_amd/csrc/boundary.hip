@@ -3,8 +3,11 @@
 // byte, inside a (2R+1)^2 window and inside the map, binned against d_i^2 in both maps and counted per (truth bin, prediction bin,
 // truth label, prediction label).  Trimap accuracy (Kohli et al. 2009) and Boundary IoU (Cheng et al. 2021) are sums over that table
 // (metrics.boundary_scores).  tests/boundary_ref.py states the rule in numpy.  Everything is integer: nothing is rounded anywhere.
+// Also here, at the end: the boundary weight map of a training step's label patches (drs_patch_boundary_weight), which
+// shares the tile geometry and the distance convention but not the scan.
 #include "drs_common.hpp"
 #include "../../include/drs.h"
+#include <cmath>
 
 namespace {
 
@@ -185,6 +188,87 @@ bool bd_geometry(int h, int w, BdArgs& a, unsigned& grid) {
   return true;
 }
 
+// ---------------------------------------------------------------------------- boundary weight map of a step's label patches
+// (opt-in; include/drs.h: drs_patch_boundary_weight; tests/boundary_weight_ref.py states the rule in numpy.)
+// lab, valid: [B][S][S] bytes, valid may be null ("all valid").  For a valid pixel p, D2(p) = min dy^2 + dx^2 over the positions
+// q = p + (dy, dx) with |dy|, |dx| <= R, q inside the SAME patch, q valid and lab[q] != lab[p]; infinite when there is none or when p
+// is invalid.  weight = 1 where D2 is infinite, else (float)(1 + a exp(-D2 c)) evaluated in fp64 and rounded once.  The patch edge is
+// no boundary, a byte is just a byte, and an invalid q never counts as "different" (rotated-in fill draws no contour).
+// The row / column scan of bd_d2 does not carry over: when the cell straight above p is invalid it is not "different", and it has
+// no byte whose row distance would say anything about the bytes that differ from p's.  So the window is scanned directly, in LDS, ring by
+// ring: ring r (Chebyshev distance r) holds squared distances r^2 .. 2 r^2 only, so the scan leaves at the first ring with
+// r^2 >= the minimum so far -- an interior pixel next to a contour reads a ring or two, and only pixels far from any contour read the
+// whole (2R + 1)^2 window.
+// One staged cell: the byte, or BW_OUT for a position outside the patch or an invalid one -- a 16-bit value no byte equals, so
+// "inside, valid, another byte" is two compares and no bound is clamped.
+constexpr unsigned short BW_OUT = 0xFFFFu;
+
+struct BwArgs {
+  const unsigned char* lab;
+  const unsigned char* valid;
+  int B, S, R, tiles_x, tiles_per_patch, ntiles;
+  double a, c;
+  unsigned short* d2;
+  float* weight;
+};
+
+__global__ void __launch_bounds__(BD_THREADS) patch_boundary_weight_kernel(const BwArgs a) {
+  __shared__ unsigned short cell[BD_LH * BD_LW];
+  const int R = a.R, S = a.S;
+  const int LW = BD_TX + 2 * R, LH = BD_TY + 2 * R;
+  const float rcp = 1.0f / (float)LW;
+  const int lx = threadIdx.x & (BD_TX - 1), q = threadIdx.x / BD_TX;
+  for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+    const int b = t / a.tiles_per_patch, rem = t - b * a.tiles_per_patch;
+    const int tyi = rem / a.tiles_x;
+    const int y0 = tyi * BD_TY, x0 = (rem - tyi * a.tiles_x) * BD_TX;
+    const int base = b * S * S;              // (B S S < 2^24: every index fits an int)
+    for (int idx = threadIdx.x; idx < LW * LH; idx += BD_THREADS) {
+      int ry, rx;
+      divmod24(idx, LW, rcp, ry, rx);
+      const int gy = y0 - R + ry, gx = x0 - R + rx;
+      unsigned short v = BW_OUT;
+      if (gy >= 0 && gy < S && gx >= 0 && gx < S) {
+        const int g = base + gy * S + gx;
+        if (!a.valid || a.valid[g]) v = a.lab[g];
+      }
+      cell[idx] = v;
+    }
+    __syncthreads();
+    const int gx = x0 + lx;
+    if (gx < S) {
+      for (int i = 0; i < BD_PIX; ++i) {
+        const int ly = q * BD_PIX + i, gy = y0 + ly;
+        if (gy >= S) break;
+        const unsigned short* ctr = cell + (ly + R) * LW + lx + R;
+        const unsigned short mine = ctr[0];
+        int best = BD_INF;
+        if (mine != BW_OUT) {
+          auto look = [&](int dy, int dx) {
+            const unsigned short v = ctr[dy * LW + dx];
+            const int cand = dy * dy + dx * dx;
+            if (v != mine && v != BW_OUT && cand < best) best = cand;
+          };
+          for (int r = 1; r <= R && best > r * r; ++r) {
+            for (int s = -r; s <= r; ++s) {
+              look(-r, s);
+              look(r, s);
+            }
+            for (int s = 1 - r; s < r; ++s) {
+              look(s, -r);
+              look(s, r);
+            }
+          }
+        }
+        const int g = base + gy * S + gx;
+        if (a.d2) a.d2[g] = (unsigned short)(best < 65535 ? best : 65535);
+        a.weight[g] = best == BD_INF ? 1.0f : (float)(1.0 + a.a * exp(-(double)best * a.c));
+      }
+    }
+    __syncthreads();              // the next tile's staging overwrites the cells this one still reads
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -219,6 +303,20 @@ int drs_boundary_histogram(const unsigned char* truth, const unsigned char* pred
   a.R = distances[n - 1];
   a.hist = hist;
   DRS_LAUNCH(boundary_histogram_kernel, dim3(grid), dim3(BD_THREADS), 0, (hipStream_t)stream, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_patch_boundary_weight(const unsigned char* lab, const unsigned char* valid, int B, int S, int R, double a, double c,
+                              unsigned short* d2_out, float* weight_out, void* stream) {
+  if (!lab || !weight_out || B < 1 || S < 1 || S >= (1 << 12) || (long long)B * S * S >= (1LL << 24) || R < 1 || R > BD_MAX_R) return DRS_ERR_ARG;
+  if (!std::isfinite(a) || a < -1.0 || a > 64.0 || !std::isfinite(c) || !(c > 0.0)) return DRS_ERR_ARG;
+  BwArgs k = {};
+  k.lab = lab; k.valid = valid; k.B = B; k.S = S; k.R = R; k.a = a; k.c = c; k.d2 = d2_out; k.weight = weight_out;
+  k.tiles_x = (S + BD_TX - 1) / BD_TX;
+  k.tiles_per_patch = k.tiles_x * ((S + BD_TY - 1) / BD_TY);
+  k.ntiles = B * k.tiles_per_patch;              // (< 2^24: a tile holds at least one pixel)
+  DRS_LAUNCH(patch_boundary_weight_kernel, dim3(k.ntiles < BD_MAX_GRID ? k.ntiles : BD_MAX_GRID), dim3(BD_THREADS), 0,
+             (hipStream_t)stream, k);
   return DRS_LAUNCH_CHECK();
 }
 

@@ -142,7 +142,7 @@ struct LayerPtrs {
 struct Ptrs {
   bool ok = false;
   float *params, *grads, *momentum, *bn, *partial, *gxh, *gz[2], *slab, *w0pad, *conv_ws, *bwd_means, *act, *gpool, *se_scratch;
-  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact;
+  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight;
   size_t conv_ws_floats;
   double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch;
   unsigned char *pred, *labels, *acc_mask, *loss_mask;
@@ -192,6 +192,8 @@ struct drs_net {
   bool has_wc = false;                      // class weights of the training loss (drs_net_set_class_weights); none: the unweighted kernels
   float wc[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
   float focal_gamma = 0.f;                  // focusing parameter of the training loss (drs_net_set_focal_gamma); 0: no focal term
+  double bw_a = 0.0, bw_sigma = 4.0;         // boundary weight of the training loss (drs_net_set_boundary_weight); a == 0: off, no launch
+  int bw_R = 12;
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -429,6 +431,7 @@ void list_buffers(drs_net* n) {
   n->add_buf("labels", M, U8);
   n->add_buf("acc_mask", M, U8);
   n->add_buf("loss_mask", M, U8);
+  n->add_buf("pixel_weight", M, F32);        // boundary weight map of the step's labels (drs_net_set_boundary_weight); untouched while it is off
 }
 
 // HIP-event bracket of one family's launches (drs_net_timing).  Events are recycled through drs_net::pool_events, and a run that
@@ -574,6 +577,7 @@ bool resolve(drs_net* n) {
   P.loss_partial = n->p<double>("loss_partial"); P.l2_scratch = n->p<double>("l2_scratch");
   P.pred = n->p<unsigned char>("pred"); P.labels = n->p<unsigned char>("labels"); P.acc_mask = n->p<unsigned char>("acc_mask");
   P.loss_mask = n->p<unsigned char>("loss_mask"); P.conf = n->p<unsigned int>("conf");
+  P.pixel_weight = n->p<float>("pixel_weight");
   const Slab& f = n->slabs[n->feat];
   P.feat_act = n->p<float>("act:" + f.name); P.feat_gact = n->p<float>("gact:" + f.name);
   P.L.assign(n->layers.size(), LayerPtrs());
@@ -1088,6 +1092,23 @@ int drs_net_get_focal_gamma(const drs_net_t* n, float* gamma) {
   return DRS_OK;
 }
 
+// Boundary weight of the training loss (drs_train_step only; include/drs.h, "Training level"): a == 0 switches it off.  The step
+// makes the weight map of its labels (drs_patch_boundary_weight) and hands it to the classifier launch (drs_classifier_loss_pixel).
+int drs_net_set_boundary_weight(drs_net_t* n, double a, double sigma, int R) {
+  if (!n || !std::isfinite(a) || a < -1.0 || a > 64.0 || !std::isfinite(sigma) || !(sigma > 0.0) || sigma > 64.0 || R < 1 || R > 16)
+    return DRS_ERR_ARG;
+  n->bw_a = a; n->bw_sigma = sigma; n->bw_R = R;
+  return DRS_OK;
+}
+
+int drs_net_get_boundary_weight(const drs_net_t* n, double* a, double* sigma, int* R) {
+  if (!n) return DRS_ERR_ARG;
+  if (a) *a = n->bw_a;
+  if (sigma) *sigma = n->bw_sigma;
+  if (R) *R = n->bw_R;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1298,10 +1319,15 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   double* scratch = P.colsum_scratch;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
-    DRS_TRY(drs_classifier_loss_focal(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+    const bool bw = n->bw_a != 0.0;          // off: no launch, and drs_classifier_loss_pixel without a map is drs_classifier_loss_focal
+    if (bw)
+      DRS_TRY(drs_patch_boundary_weight(P.labels, (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, B, S, n->bw_R, n->bw_a,
+                                        1.0 / (2.0 * n->bw_sigma * n->bw_sigma), nullptr, P.pixel_weight, st));
+    DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
                                       P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
                                       (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                      n->has_wc ? n->wc : nullptr, n->focal_gamma, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
+                                      n->has_wc ? n->wc : nullptr, n->focal_gamma, bw ? P.pixel_weight : nullptr,
+                                      (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
                                       P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
   }
   // the classifier's slab reductions (its kernel / bias gradients, the cross-entropy sum) and the L2 term: seven launches of ~5 us that

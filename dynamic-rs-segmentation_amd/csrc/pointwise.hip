@@ -896,11 +896,16 @@ struct ClsArgs {
   float rcpS, rcpSS;
   float wc[8];               // class weights of the weighted and focal forms, by value: scalar registers, no buffer and no load
   float gamma;               // focusing parameter of the focal forms (CLS_FOCAL), by value; the other forms do not read it
+  const float* pixel_weight; // [M] per-pixel weights of the CLS_PIXEL forms (the boundary weight map); the other forms do not read it
 };
 
 // Loss mode of the three classifier forms (template argument LM).  CLS_PLAIN: the cross-entropy, the code the kernels always had;
 // CLS_WEIGHTED: wc[y] * CE; CLS_FOCAL: wc[y] * (1 - p_t)^gamma * CE -- it always multiplies wc[y] in (ones when no weights are set).
-constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2;
+// CLS_PIXEL, a flag on top of CLS_WEIGHTED or CLS_FOCAL (never CLS_PLAIN): the pixel's own weight pixel_weight[p] is multiplied into
+// wc[y] -- one more load and one more multiply per pixel, in the slot the class weight already has; nothing else changes, so the
+// order of every sum is that of the form without the flag.  cls_base(LM) strips it.
+constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2, CLS_PIXEL = 4;
+constexpr int cls_base(int lm) { return lm & 3; }
 
 // The weight of a pixel's label: a register select over the eight by-value weights (a label outside [0, K) never enters the loss:
 // whatever comes out for it is multiplied into nothing)
@@ -944,14 +949,14 @@ __device__ __forceinline__ void focal_terms(float gamma, float so, float ey, flo
 // the loss sum.  wy = wc[y]; f, m, ce: focal_terms (CLS_FOCAL reads nothing else); ly = the label's logit.
 template <int LM>
 __device__ __forceinline__ float cls_grad_scale(float inv_n, float wy, float f) {
-  if constexpr (LM == CLS_FOCAL) return inv_n * wy * f;
-  else if constexpr (LM == CLS_WEIGHTED) return inv_n * wy;
+  if constexpr (cls_base(LM) == CLS_FOCAL) return inv_n * wy * f;
+  else if constexpr (cls_base(LM) == CLS_WEIGHTED) return inv_n * wy;
   else return inv_n;
 }
 template <int LM>
 __device__ __forceinline__ double cls_loss_term(float wy, float se, float mx, float ly, float m, float ce) {
-  if constexpr (LM == CLS_FOCAL) return (double)wy * ((double)m * (double)ce);
-  else if constexpr (LM == CLS_WEIGHTED) return (double)wy * (double)(__logf(se) + mx - ly);
+  if constexpr (cls_base(LM) == CLS_FOCAL) return (double)wy * ((double)m * (double)ce);
+  else if constexpr (cls_base(LM) == CLS_WEIGHTED) return (double)wy * (double)(__logf(se) + mx - ly);
   else return (double)(__logf(se) + mx - ly);
 }
 
@@ -1056,8 +1061,9 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
     float ly = 0.f;
     float dl[KM];
     constexpr bool WT = LM != CLS_PLAIN;
-    const float wy = WT ? cls_weight<KM>(a, y) : 1.f;
-    if constexpr (LM == CLS_FOCAL) {
+    float wy = WT ? cls_weight<KM>(a, y) : 1.f;
+    if constexpr ((LM & CLS_PIXEL) != 0) wy *= a.pixel_weight[p];
+    if constexpr (cls_base(LM) == CLS_FOCAL) {
       // every lane holds all the classes: so in ascending class order, then a few scalar-like operations per pixel
       float so = 0.f;
 #pragma unroll
@@ -1226,15 +1232,16 @@ __device__ __forceinline__ void cls_mc_argmax_store(const ClsArgs& a, int K, int
 // == b + a bit for bit; the logit sum has one non-zero term: exact); the focal ex_y is recomputed from that logit, the same
 // instruction on the same operands as in the lane that owns class y.
 template <int LM>
-__device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, int cls0, int cls1, float lg0, float lg1,
-                                                  float mx, float& dl0, float& dl1, double& lsum) {
+__device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, float pw, int cls0, int cls1, float lg0,
+                                                  float lg1, float mx, float& dl0, float& dl1, double& lsum) {
   const float ex0 = cls0 < K ? __expf(lg0 - mx) : 0.f, ex1 = cls1 < K ? __expf(lg1 - mx) : 0.f;
   float se = ex0 + ex1;
   se += __shfl_xor(se, 16);
   se += __shfl_xor(se, 32);
   const float inv = 1.0f / se;
-  const float wy = LM != CLS_PLAIN ? cls_weight(a, y) : 1.f;
-  if constexpr (LM == CLS_FOCAL) {
+  float wy = LM != CLS_PLAIN ? cls_weight(a, y) : 1.f;
+  if constexpr ((LM & CLS_PIXEL) != 0) wy *= pw;          // (pw: the pixel's weight, the same bits in its four lanes; unread otherwise)
+  if constexpr (cls_base(LM) == CLS_FOCAL) {
     float so = (cls0 == y ? 0.f : ex0) + (cls1 == y ? 0.f : ex1);
     so += __shfl_xor(so, 16);
     so += __shfl_xor(so, 32);
@@ -1378,8 +1385,9 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     const int y = a.labels[pixc];
     if (G == 0 && valid && a.conf && (!a.acc_mask || a.acc_mask[pix]) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
     const bool in_loss = valid && (!a.loss_mask || a.loss_mask[pixc]) && y < K;     // a label outside [0, K) never trains the net
-    float dl0, dl1;
-    cls_mc_pixel_grad<LM>(a, K, y, in_loss, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
+    float dl0, dl1, pw = 1.f;
+    if constexpr ((LM & CLS_PIXEL) != 0) pw = a.pixel_weight[pixc];
+    cls_mc_pixel_grad<LM>(a, K, y, in_loss, pw, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
     db0 += dl0;
     db1 += dl1;
     if (!a.gfeat) continue;
@@ -1491,6 +1499,9 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
     __builtin_amdgcn_wave_barrier();
     // label / mask bytes of this tile: hidden from the compiler's wait bookkeeping (it would drain the DMA below at their first use)
     unsigned ylab = 0, vlm = 1, vam = 1;
+    float vpw = 1.f;          // the pixel's weight (CLS_PIXEL): a fourth load beside the three bytes, older than the DMA like them
+    if constexpr ((LM & CLS_PIXEL) != 0)
+      asm volatile("global_load_dword %0, %1, off" : "=v"(vpw) : "v"(a.pixel_weight + pixc) : "memory");
     if (TRAIN) {
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(ylab) : "v"(a.labels + pixc) : "memory");
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(vlm) : "v"(lm + pixc) : "memory");
@@ -1520,13 +1531,14 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       // the three byte loads are older than the NI DMA instructions (or nothing, on the last tile) issued after them
       if (tb + 64 < pend) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(ylab), "+v"(vlm), "+v"(vam) : "n"(NI) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" : "+v"(ylab), "+v"(vlm), "+v"(vam) :: "memory");
+      if constexpr ((LM & CLS_PIXEL) != 0) asm volatile("" : "+v"(vpw) :: "memory");      // (the same wait covers it: read only from here on)
       const int y = (int)ylab;
       if (G == 0 && valid && a.conf && (!a.acc_mask || vam) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
       const bool in_loss = valid && (!a.loss_mask || vlm) && y < K;
       // (the weight select and the focal factor's four cross-lane moves and arithmetic: vector-ALU work of the softmax section,
       // after the logits' MFMAs have been issued and before the filter gradient's -- no MFMA waits for it)
       float dl0, dl1;
-      cls_mc_pixel_grad<LM>(a, K, y, in_loss, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
+      cls_mc_pixel_grad<LM>(a, K, y, in_loss, vpw, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
       db0 += dl0;
       db1 += dl1;
       if (a.gfeat) {
@@ -1579,7 +1591,7 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
 
 // Run-time launch parameters onto template arguments, handed to a generic lambda as std::integral_constants.
 // cls_width: the width C / 64 = Q .. QMAX - 1, anything else QMAX.  cls_mode: (loss mode, labels present) onto <TRAIN, LM> -- the
-// weighted and focal modes exist for training only, so no TRAIN = false kernel is instantiated with them.
+// weighted and focal modes, with or without CLS_PIXEL, exist for training only, so no TRAIN = false kernel is instantiated with them.
 template <int Q, int QMAX, typename F>
 static void cls_width(int cq, F&& f) {
   if constexpr (Q < QMAX)
@@ -1588,7 +1600,9 @@ static void cls_width(int cq, F&& f) {
 }
 template <typename F>
 static void cls_mode(int lm, bool train, F&& f) {
-  if (lm == CLS_FOCAL) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL>{});
+  if (lm == (CLS_FOCAL | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_PIXEL>{});
+  else if (lm == (CLS_WEIGHTED | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_PIXEL>{});
+  else if (lm == CLS_FOCAL) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL>{});
   else if (lm == CLS_WEIGHTED) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED>{});
   else if (train) f(std::true_type{}, std::integral_constant<int, CLS_PLAIN>{});
   else f(std::false_type{}, std::integral_constant<int, CLS_PLAIN>{});
@@ -2028,12 +2042,14 @@ int drs_debug_cls_variant(int v) { const int old = g_cls_variant; if (v >= 0) g_
 // class_weights: HOST pointer to K floats or NULL.  NULL, all weights exactly 1, or no labels (inference): the unweighted kernels,
 // which do not multiply at all (bit for bit drs_classifier_loss); otherwise the CLS_WEIGHTED instantiations with the weights by
 // value.  focal_gamma: 0 is not a focal launch -- the dispatch above, unchanged; in (0, 8] with labels the CLS_FOCAL instantiations,
-// which carry gamma by value and multiply the weights in, ones when none are set.
-int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+// which carry gamma by value and multiply the weights in, ones when none are set.  pixel_weight: DEVICE pointer to B S S floats or
+// NULL.  NULL or no labels: the dispatch above, unchanged; otherwise the CLS_PIXEL instantiations of the weighted form (the focal one
+// with gamma > 0), which multiply pixel_weight[p] into the class weight (ones when none are set).
+int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
                               const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
-                              float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
-                              float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
+                              const float* pixel_weight, float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g,
+                              float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
   if (!feat || !w || !bias || K < 1 || K > 8 || C < 64 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
   if (B < 1 || S < 1 || P < 0 || !std::isfinite(inv_n) || inv_n < 0.f) return DRS_ERR_ARG;
   if (!std::isfinite(focal_gamma) || focal_gamma < 0.f || focal_gamma > 8.f) return DRS_ERR_ARG;
@@ -2052,7 +2068,8 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
     }
   wt = wt && labels;
   const bool focal = focal_gamma > 0.f && labels;
-  const int lm = focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
+  const bool px = pixel_weight && labels;
+  const int lm = px ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_PIXEL) : focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
   ClsArgs a;
   a.feat = mkview(const_cast<float*>(feat), S, P, ld, coff); a.C = C; a.K = K; a.M = (int)M; a.w = w; a.bias = bias;
   a.labels = labels; a.loss_mask = loss_mask; a.acc_mask = acc_mask; a.inv_n = inv_n; a.logits = logits; a.pred = pred;
@@ -2061,6 +2078,7 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
   a.rcpS = 1.0f / (float)S; a.rcpSS = 1.0f / (float)(S * S);
   for (int k = 0; k < 8; ++k) a.wc[k] = wt && k < K ? class_weights[k] : 1.f;
   a.gamma = focal ? focal_gamma : 0.f;
+  a.pixel_weight = px ? pixel_weight : nullptr;
   const int nblk = drs_classifier_rows(B, S);
   a.rows_per_block = (int)(((M + nblk - 1) / nblk + 63) / 64 * 64);      // whole 16-pixel tiles per wave; trailing workgroups may be empty
   hipStream_t st = (hipStream_t)stream;
@@ -2100,6 +2118,15 @@ int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, in
     });
   });
   return DRS_LAUNCH_CHECK();
+}
+
+int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                              float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial,
+                              float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
+  return drs_classifier_loss_pixel(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, class_weights, focal_gamma,
+                                   nullptr, logits, pred, gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
 }
 
 int drs_classifier_loss(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,

@@ -106,7 +106,7 @@ class EngineNet(DilatedNet):
         self.idx = [b.get("idx%d" % i) for i in range(nl)]
         self.mean_rstd = [b["mean_rstd%d" % i] for i in range(nl)]
         for n in ("sums", "partial", "gxh", "gz", "slab", "w0pad", "dw_partial", "db_partial", "loss_partial", "scalars", "logits", "pred", "conf",
-                  "labels", "acc_mask", "loss_mask"):
+                  "labels", "acc_mask", "loss_mask", "pixel_weight"):
             setattr(self, n, b[n])
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
@@ -312,6 +312,19 @@ class EngineNet(DilatedNet):
         g = C.c_float()
         _lib.call("drs_net_get_focal_gamma", self.h, C.byref(g))
         return float(g.value)
+
+    def _boundary_weight_changed(self):
+        """hand the triple to the library's net (drs_net_set_boundary_weight: the step launches the weight kernel before its classifier)"""
+        from .patches import DEFAULT_BOUNDARY_SIGMA, default_boundary_radius
+        a, sigma, radius = self._boundary_weight or (0.0, DEFAULT_BOUNDARY_SIGMA, default_boundary_radius(DEFAULT_BOUNDARY_SIGMA))
+        _lib.call("drs_net_set_boundary_weight", self.h, float(a), float(sigma), int(radius))
+
+    @property
+    def boundary_weight(self):
+        """the triple (a, sigma, R) the library's net holds (drs_net_get_boundary_weight), or None when it is off (a == 0)"""
+        a, sigma, radius = C.c_double(), C.c_double(), C.c_int()
+        _lib.call("drs_net_get_boundary_weight", self.h, C.byref(a), C.byref(sigma), C.byref(radius))
+        return None if a.value == 0.0 else (float(a.value), float(sigma.value), int(radius.value))
 
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always

@@ -116,12 +116,41 @@ def load_focal_gamma(net, former_model_path):
             print("Focal loss (restored from " + path + "): gamma " + "{:.6g}".format(net.focal_gamma))
 
 
+BOUNDARY_WEIGHT_SIDE = "boundary_weight_step_"
+
+
+def _boundary_weight_str(bw):
+    return "a " + "{:.6g}".format(bw[0]) + " sigma " + "{:.6g}".format(bw[1]) + " R " + str(int(bw[2]))
+
+
+def save_boundary_weight(net, output_path, step):
+    """the boundary weight of the training loss, when on, as the side file `boundary_weight_step_<step>.npy` beside the size scores:
+    three float64 (a, sigma, R) (state of the run, not of the model, as the class weights and the focal gamma are)"""
+    bw = getattr(net, "boundary_weight", None)
+    if bw is not None:
+        np.save(output_path + BOUNDARY_WEIGHT_SIDE + str(step) + ".npy", np.asarray([bw[0], bw[1], bw[2]], dtype=np.float64))
+
+
+def load_boundary_weight(net, former_model_path):
+    """set the triple that save_boundary_weight left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep:
+        return
+    path = head + BOUNDARY_WEIGHT_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        a, sigma, radius = np.load(path).tolist()
+        net.set_boundary_weight((a, sigma, int(radius)))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Boundary weight (restored from " + path + "): " + _boundary_weight_str(net.boundary_weight))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
-    """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights
-    and the focal gamma of the loss when set (save_class_weights, save_focal_gamma)."""
+    """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights,
+    the focal gamma and the boundary weight of the loss when set (save_class_weights, save_focal_gamma, save_boundary_weight)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
     save_focal_gamma(net, output_path, step)
+    save_boundary_weight(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -142,6 +171,7 @@ def load_checkpoint(net, former_model_path):
         net.load_state_dict({k: d[k] for k in d.files})
     load_class_weights(net, former_model_path)
     load_focal_gamma(net, former_model_path)
+    load_boundary_weight(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -221,6 +251,51 @@ def setup_focal_gamma(net, focal_gamma, comm, say):
         say("Focal loss: gamma " + "{:.6g}".format(g) + (" (the loss is wc[y] (1 - p_t)^gamma CE)" if g > 0.0 else " (off: the cross-entropy)") +
             ("" if restored == 0.0 or restored == g else " -- replacing the gamma restored from the checkpoint, " + "{:.6g}".format(restored)))
     return g
+
+
+def setup_boundary_weight(net, boundary_weight, comm, say):
+    """The boundary weight of a training run (train's `boundary_weight`; patches.check_boundary_weight): every rank must hold the same
+    triple (a, sigma, R), asserted once over the ranks on the float64 bits.  Given, it replaces a triple restored from a checkpoint's
+    side file.  One log line names it; a = 0 on a run that restored none is today's run and says nothing."""
+    bw = P.check_boundary_weight(boundary_weight)
+    bits = np.asarray(bw[:2], dtype=np.float64).view(np.uint32)
+    comm.agree([int(b) for b in bits] + [int(bw[2])], "boundary weight")
+    restored = net.boundary_weight
+    net.set_boundary_weight(bw)
+    on = bw[0] != 0.0
+    if on or restored is not None:
+        say("Boundary weight: " + (_boundary_weight_str(bw) + " (the loss is (1 + a exp(-D2 / 2 sigma^2)) wc[y] m CE, normalised as before)"
+                                   if on else "a 0 (off: every pixel weighs one)") +
+            ("" if restored is None or restored == bw else " -- replacing the triple restored from the checkpoint, " + _boundary_weight_str(restored)))
+    return bw
+
+
+def boundary_weight_map(labels, valid, a, sigma, R):
+    """The weight map drs_train_step makes of a step's labels, for inspection: labels uint8 [B, S, S] (a tensor on the
+    GPU, or anything np.asarray takes -- then on the current device), valid the same shape or None.  Returns (weight float32 [B, S, S],
+    d2 int32 [B, S, S]: the kernel's uint16 min(D2, 65535), 65535 = no other class within the window) as tensors on the labels' device."""
+    from . import _lib
+    a, sigma, R = P.check_boundary_weight((a, sigma, R))
+
+    def dev_u8(t, device):
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.uint8)))
+        return t.to(device=device, dtype=torch.uint8).contiguous()
+
+    device = labels.device if isinstance(labels, torch.Tensor) and labels.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    lab = dev_u8(labels, device)
+    if lab.dim() != 3 or lab.shape[1] != lab.shape[2]:
+        raise ValueError("labels: expected [B, S, S], got %s" % (tuple(lab.shape),))
+    val = None if valid is None else dev_u8(valid, device)
+    if val is not None and val.shape != lab.shape:
+        raise ValueError("valid: expected the shape of labels, got %s" % (tuple(val.shape),))
+    B, S = int(lab.shape[0]), int(lab.shape[1])
+    weight = torch.empty((B, S, S), dtype=torch.float32, device=device)
+    d2 = torch.empty((B, S, S), dtype=torch.int16, device=device)
+    with torch.cuda.device(device):
+        _lib.call("drs_patch_boundary_weight", lab.data_ptr(), None if val is None else val.data_ptr(), B, S, R, a,
+                  1.0 / (2.0 * sigma * sigma), d2.data_ptr(), weight.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return weight, d2.to(torch.int32) & 0xFFFF
 
 
 # ------------------------------------------------------------------------------------------------- data parallelism
@@ -316,7 +391,7 @@ def train(training_data, training_labels, training_class_distribution, training_
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
           loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
-          scale_jitter=None):
+          scale_jitter=None, boundary_weight=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -327,6 +402,13 @@ def train(training_data, training_labels, training_class_distribution, training_
     size scores with update_type="loss", is then the MODULATED one (inv_n * sum wc[y] (1 - p_t)^gamma CE + the L2 term); accuracies,
     confusion matrices and validation are not modulated.  Given here, it replaces a gamma restored from a checkpoint's side file;
     None keeps that.
+    boundary_weight (opt-in; None or a = 0 = today's run, bit for bit): (a, sigma, R), or fewer with the defaults of
+    patches.check_boundary_weight -- every pixel's loss term and gradient are multiplied by 1 + a exp(-D2 / 2 sigma^2), D2 the squared
+    distance to the nearest valid pixel of another class inside the augmented patch (setup_boundary_weight,
+    DilatedNet.set_boundary_weight; on top of class_weights and focal_gamma).  The loss this loop prints, and that feeds the size
+    scores with update_type="loss", is then the WEIGHTED one: its normaliser is unchanged, so it rises with the mean weight;
+    accuracies, confusion matrices and validation are not weighted.  Given here, it replaces a triple restored from a checkpoint's
+    side file; None keeps that.  Under data parallelism nothing is added: patches are independent and the normaliser is unchanged.
     scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
     log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
     their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
@@ -374,6 +456,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_class_weights(net, train_pool, num_classes, class_weights, comm, say)
     if focal_gamma is not None:
         setup_focal_gamma(net, focal_gamma, comm, say)
+    if boundary_weight is not None:
+        setup_boundary_weight(net, boundary_weight, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)

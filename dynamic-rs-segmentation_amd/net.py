@@ -153,6 +153,7 @@ class DilatedNet(object):
         self.global_step = 0
         self._class_weights = None
         self._focal_gamma = 0.0
+        self._boundary_weight = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -259,6 +260,29 @@ class DilatedNet(object):
     def focal_gamma(self):
         """the focusing parameter in use (a float32 value as a Python float); 0.0: no focal term"""
         return self._focal_gamma
+
+    # ------------------------------------------------------------------ boundary weight of the training loss
+    def set_boundary_weight(self, bw):
+        """Boundary-weighted training loss (opt-in): bw = (a, sigma, R) as patches.check_boundary_weight takes it, or
+        None / a == 0 (the step as it is, bit for bit, no new launch).  train_step then makes a weight map of its labels,
+        pw = 1 + a exp(-D2 / 2 sigma^2) with D2 the squared distance to the nearest valid pixel of another class inside the patch and
+        a (2R + 1)^2 window (1 where there is none; validity = acc_mask when the step uses it), and its data term becomes
+        inv_n * sum over the pixels in the loss of pw[p] * wc[y] * m * CE (wc, m: class weights and focal factor, ones when not set;
+        inv_n unchanged, so the loss scales with the mean weight).  The loss train_step reports is the WEIGHTED one; logits, pred, the
+        confusion matrix, the L2 term and every forward pass are not weighted.  State of the training run, not of the model:
+        loops.save_checkpoint keeps it in a side file, and an inference twin does not copy it."""
+        from .patches import check_boundary_weight
+        self._boundary_weight = None if bw is None else check_boundary_weight(bw)
+        self._boundary_weight_changed()
+
+    def _boundary_weight_changed(self):
+        pass
+
+    @property
+    def boundary_weight(self):
+        """the triple (a, sigma, R) in use, or None when it is off (never set, or a == 0)"""
+        bw = self._boundary_weight
+        return None if bw is None or bw[0] == 0.0 else bw
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

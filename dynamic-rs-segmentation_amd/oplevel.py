@@ -102,6 +102,7 @@ class OpLevelNet(DilatedNet):
         self.labels = torch.zeros(M, **u8)
         self.acc_mask = torch.ones(M, **u8)
         self.loss_mask = torch.ones(M, **u8)
+        self.pixel_weight = torch.zeros(M, **f32)      # boundary weight map of the step's labels (set_boundary_weight); untouched while it is off
 
     def workspace_bytes(self):
         tot = 0
@@ -338,10 +339,15 @@ class OpLevelNet(DilatedNet):
         gfeat, ldg, cg = self.gbuf[p.feat], p.buffers[p.feat][0], 0
         self.conf.zero_()
         wc = self._class_weights          # (HOST pointer: the library copies the K floats into the kernel arguments; None: unweighted)
-        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_focal", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
+        bw = self.boundary_weight         # (a, sigma, R) or None: off, no launch, and the pixel form without a map is the focal one
+        if bw is not None:
+            a_bw, sigma_bw, r_bw = bw
+            _lib.call("drs_patch_boundary_weight", _ptr(self.labels), _ptr(self.acc_mask) if use_acc_mask else None, B, S, r_bw, a_bw,
+                      1.0 / (2.0 * sigma_bw * sigma_bw), None, _ptr(self.pixel_weight), st)
+        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_pixel", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
                 self.params[woff:].data_ptr(), self.params[boff:].data_ptr(), _ptr(self.labels), _ptr(self.loss_mask) if use_loss_mask else None,
                   _ptr(self.acc_mask) if use_acc_mask else None, 1.0 / n_glob, None if wc is None else wc.ctypes.data, float(self._focal_gamma),
-                  _ptr(self.logits) if want_logits else None,
+                  None if bw is None else _ptr(self.pixel_weight), _ptr(self.logits) if want_logits else None,
                   _ptr(self.pred), _ptr(gfeat), ldg, cg, _ptr(self.dw_partial), _ptr(self.db_partial), _ptr(self.loss_partial),
                   _ptr(self.conf), st)
         crow = _lib.query("drs_classifier_rows", B, S)

@@ -365,6 +365,56 @@ def parse_focal_gamma(text):
     return check_focal_gamma(v)
 
 
+# ------------------------------------------------------------------- boundary weight of the training loss
+MAX_BOUNDARY_A, MAX_BOUNDARY_SIGMA, MAX_BOUNDARY_R = 64.0, 64.0, 16    # the ranges drs_net_set_boundary_weight takes (include/drs.h)
+DEFAULT_BOUNDARY_SIGMA = 4.0
+
+
+def default_boundary_radius(sigma):
+    """the window radius when none is given: three sigma, at most the 16 the kernel's LDS halo holds"""
+    return min(MAX_BOUNDARY_R, max(1, int(math.ceil(3.0 * sigma))))
+
+
+def check_boundary_weight(bw):
+    """The boundary weight of the training loss as the library takes it: (a, sigma, R) -- or (a,), (a, sigma), or a
+    bare number a -- with a finite in [-1, 64] (0: off), sigma finite in (0, 64] (default 4) and R an integer in 1..16 (default
+    min(16, ceil(3 sigma))).  Returns the triple (float, float, int).  Anything else: ValueError."""
+    t = tuple(bw) if isinstance(bw, (tuple, list)) else (bw,)
+    what = "boundary weight %r: expected a[, sigma[, R]] with a in [-1, %g], sigma in (0, %g], R an integer in 1..%d" % (
+        bw, MAX_BOUNDARY_A, MAX_BOUNDARY_SIGMA, MAX_BOUNDARY_R)
+    if not 1 <= len(t) <= 3 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in t):
+        raise ValueError(what)
+    a = float(t[0])
+    sigma = float(t[1]) if len(t) > 1 else DEFAULT_BOUNDARY_SIGMA
+    if not math.isfinite(a) or a < -1.0 or a > MAX_BOUNDARY_A or not math.isfinite(sigma) or not 0.0 < sigma <= MAX_BOUNDARY_SIGMA:
+        raise ValueError(what)
+    if len(t) > 2:
+        if not isinstance(t[2], (int, np.integer)) and float(t[2]) != int(t[2]):
+            raise ValueError(what)
+        radius = int(t[2])
+    else:
+        radius = default_boundary_radius(sigma)
+    if not 1 <= radius <= MAX_BOUNDARY_R:
+        raise ValueError(what)
+    return a, sigma, radius
+
+
+def parse_boundary_weight(text):
+    """The value of the command lines' --boundary-weight option: `a`, `a,sigma` or `a,sigma,R` as check_boundary_weight takes them (R
+    written as an integer).  Anything else raises ValueError."""
+    vals = None
+    if text and text == text.strip():
+        parts = text.split(",")
+        try:
+            if 1 <= len(parts) <= 3 and all(q and q == q.strip() for q in parts):
+                vals = [float(q) for q in parts[:2]] + [int(q) for q in parts[2:]]
+        except ValueError:
+            vals = None
+    if vals is None:
+        raise ValueError("boundary weight %r: expected a[,sigma[,R]] (numbers; R an integer)" % (text,))
+    return check_boundary_weight(tuple(vals))
+
+
 # ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
 SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores (DESIGN.md 8a.4)
 

@@ -719,6 +719,15 @@ int drs_net_get_class_weights(const drs_net_t* net, float* host_w, int K_cap, in
  * else DRS_ERR_ARG.  drs_forward and drs_forward_staged have no loss and ignore it. */
 int drs_net_set_focal_gamma(drs_net_t* net, float gamma);
 int drs_net_get_focal_gamma(const drs_net_t* net, float* gamma);
+/* boundary weight of drs_train_step's loss (opt-in; the section "Training level" below states the rule): a in [-1, 64], a == 0 (the
+ * default) switches it off -- no new launch, the step is the launches it was, bit for bit; sigma finite in (0, 64]; R in 1..16;
+ * anything else DRS_ERR_ARG, also with a == 0.  With a != 0 the step launches drs_patch_boundary_weight(labels, acc_mask if and only
+ * if DRS_USE_ACC_MASK, B, S, R, a, 1 / (2 sigma^2)) into the bound buffer "pixel_weight" before the classifier, and the classifier
+ * as drs_classifier_loss_pixel with that map; the launch is accounted under the timing kind "classifier_loss".  "scalars"[0] is then
+ * the boundary-weighted loss.  drs_forward and drs_forward_staged have no loss and ignore it.
+ * drs_net_get_boundary_weight: the triple in use (any pointer may be NULL); (0, 4, 12) when never set. */
+int drs_net_set_boundary_weight(drs_net_t* net, double a, double sigma, int R);
+int drs_net_get_boundary_weight(const drs_net_t* net, double* a, double* sigma, int* R);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
@@ -761,6 +770,44 @@ int drs_sieve_round(const unsigned char* map_in, const int* label, const unsigne
                     void* scratch, unsigned char* map_out, unsigned int* counters, void* stream);
 int drs_component_census(const unsigned char* map, const int* label, const unsigned int* size, int h, int w, int K,
                          unsigned long long* table, void* stream);
+
+/* ==================================================================================================================
+ * Training level: boundary-weighted cross-entropy (opt-in; csrc/boundary.hip, csrc/pointwise.hip).  A per-pixel weight
+ * map that rises towards the nearest pixel of another class (Ronneberger et al., U-Net, 2015: w = 1 + w0 exp(-d^2 / 2 sigma^2)), made
+ * from the augmented label patches of a step, and the classifier form that reads it.  NORMATIVE: this text and the numpy statement
+ * tests/boundary_weight_ref.py.
+ * Inputs: lab, uint8 [B][S][S], the labels the crop kernel wrote; valid, uint8 [B][S][S] or NULL for "all valid"; R in 1..16; a, a
+ *     double in [-1, 64]; c = 1 / (2 sigma^2), a double made by the host, sigma in (0, 64].
+ * Distance, for patch b and pixel p = (y, x): if valid is given and valid[p] == 0, D2(p) is infinite.  Otherwise
+ *     D2(p) = min { dy^2 + dx^2 } over the positions q = p + (dy, dx) with |dy| <= R and |dx| <= R; q inside the same patch,
+ *     0 <= qy, qx < S; valid NULL or valid[q] != 0; lab[q] != lab[p].  Infinite if there is no such q.  Integer arithmetic, nothing
+ *     is rounded.  As in drs_boundary_*, the edge of the patch is not a boundary and a byte is just a byte.  Patches are independent:
+ *     no window reads into the next row's wrap-around or into the next patch.  An invalid q never counts as "different": rotated-in
+ *     fill (label 0, mask 0) and void pixels draw no contour along the rotation cut.
+ * Weight: w(p) = 1.0f where D2 is infinite (so also at an invalid p, whose treatment by the loss does not change); elsewhere
+ *     w(p) = (float)(1.0 + a exp(-D2 c)), evaluated in fp64 and rounded once.  w >= 0 because a >= -1; the tail beyond R is cut to
+ *     exactly 1.
+ * Loss: with pw the weight map, L = inv_n * sum over the pixels in the loss of pw[p] * wc[y] * m * CE, wc and the focal factor m
+ *     exactly those of drs_classifier_loss_focal; the logit gradient is scaled by the same factor pw[p].  Logits, arg-max and the
+ *     confusion matrix are not weighted.  inv_n stays the normaliser: no pre-pass, no collective, and the scale of the loss rises with
+ *     the mean weight.
+ *
+ * drs_patch_boundary_weight: weight_out = float [B][S][S]; d2_out = uint16 [B][S][S], min(D2, 65535) (infinite -> 65535), may be NULL:
+ *     it exists so that a wrong distance and a wrong weight can be told apart.  One launch, no scratch, no synchronisation.
+ *     Ranges, else DRS_ERR_ARG (nothing is launched): lab and weight_out not NULL; B, S >= 1, B S S < 2^24; R in 1..16; a finite in
+ *     [-1, 64]; c finite and > 0.
+ * drs_classifier_loss_pixel: the arguments of drs_classifier_loss_focal plus pixel_weight, DEVICE float [B S S] or NULL.  With NULL,
+ *     or with labels == NULL, it IS drs_classifier_loss_focal: the same launches, every output bit for bit.  Otherwise all three kernel
+ *     forms multiply pixel_weight[p] into wc[y] (ones when no class weights are set; the focal form with focal_gamma > 0, else the
+ *     weighted one).  The order of every sum is that of the form without a map: it does not depend on the weights.  The weights
+ *     themselves are device data and are not checked: the caller keeps them finite and non-negative. */
+int drs_patch_boundary_weight(const unsigned char* lab, const unsigned char* valid, int B, int S, int R, double a, double c,
+                              unsigned short* d2_out, float* weight_out, void* stream);
+int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                              const float* pixel_weight, float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g,
+                              float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf, void* stream);
 
 #ifdef __cplusplus
 }
