@@ -91,6 +91,9 @@ SIGNATURES = {
     "drs_sieve_scratch_bytes": (_sz, [_i, _i]),
     "drs_sieve_round": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "drs_component_census": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
+    "drs_object_scratch_bytes": (_sz, [_i, _i]),
+    "drs_object_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "drs_object_table": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     # ---- training level: boundary-weighted cross-entropy (csrc/boundary.hip, csrc/pointwise.hip)
     "drs_patch_boundary_weight": (_i, [_p, _p, _i, _i, _i, _d, _d, _p, _p, _p]),
     "drs_classifier_loss_pixel": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _p, _i, _i, _p, _p,

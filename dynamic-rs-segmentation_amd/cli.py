@@ -33,6 +33,11 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     enough, round after round until none is left (loops.sieve_labels); one `Sieve` line per map and for all maps.
     `--sieve-connectivity=4|8` (default 4; with --sieve only) says what holds a region together.  Score maps and calibration lines
     stay those of the unsieved labels
+  + optionally, anywhere, `--object-scores[=4|8]` (validate_test; any inference path, with or without --crf / --sieve): one more line
+    per map and for all maps with object-level scores -- the connected regions of each class (4-connected by default) are the objects,
+    a truth object and a predicted one match when their IoU exceeds 1/2 --: per class the truth / predicted / matched counts, detection
+    precision, recall and F1, the mean IoU of the matched objects (SQ) and the panoptic quality PQ (loops.validate_test's
+    object_scores)
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -250,6 +255,18 @@ def parse_sieve(argv, num_classes=None):
     return argv, P.check_sieve(dict(min_size=min_size, connectivity=P.SIEVE_CONNECTIVITY if conn is None else int(conn)))
 
 
+OBJECT_SCORES_FLAG = "--object-scores"
+
+
+def parse_object_scores(argv):
+    """isprs flavour: the optional `--object-scores[=4|8]` (anywhere in argv; validate_test, which main checks).  Returns (argv without
+    the flag, the connectivity; patches.parse_object_scores) -- patches.OBJECT_CONNECTIVITY for the bare flag --, or (argv unchanged,
+    None) without it.  Any other value, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, OBJECT_SCORES_FLAG, lambda a, v: _or_expected(
+        P.parse_object_scores, a, v, "%s or %s=4|8 (what holds an object together)" % (OBJECT_SCORES_FLAG, OBJECT_SCORES_FLAG)),
+        bare=P.OBJECT_CONNECTIVITY)
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -366,6 +383,7 @@ def main(argv=None, device=None, comm=None):
         argv, crf = parse_crf(argv)
         argv, boundary = parse_boundary_scores(argv)
         argv, sieve = parse_sieve(argv, 6)
+        argv, objects = parse_object_scores(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
@@ -400,6 +418,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(BOUNDARY_FLAG + " applies to the validate_test process only")
     if sieve is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(SIEVE_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if objects is not None and argv[16] != "validate_test":
+        sys.exit(OBJECT_SCORES_FLAG + " applies to the validate_test process only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -480,6 +500,7 @@ def main(argv=None, device=None, comm=None):
     crf_kw = {} if crf is None else dict(crf=crf)          # without the flag the loops are called as they always were
     boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
     sieve_kw = {} if sieve is None else dict(sieve=sieve)
+    objects_kw = {} if objects is None else dict(object_scores=objects)
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
@@ -494,7 +515,7 @@ def main(argv=None, device=None, comm=None):
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
                                    step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                   **boundary_kw, **sieve_kw)
+                                   **boundary_kw, **sieve_kw, **objects_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,

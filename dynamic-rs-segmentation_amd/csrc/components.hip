@@ -1,7 +1,9 @@
 // Connected components of a whole label map, the sieve round built on them and the object census (opt-in; include/drs.h:
 // drs_components, drs_sieve_round, drs_component_census).  tests/sieve_ref.py states the rule in numpy.  Everything is
 // integer and every cross-workgroup combination is an integer atomic (min, max, add): every output is exact and independent of tiling
-// and scheduling.
+// and scheduling.  Below the census: the match of two labellings of one map and the object table (drs_object_match, drs_object_table;
+// DESIGN.md 8a.9; tests/objects_ref.py), held to the same discipline -- its one compare-and-swap loop is a weighted majority vote whose
+// outcome, where anything reads it, does not depend on the order of the votes.
 //
 // Labelling is a block-based union-find (Komura 2015; Playne & Hawick 2018): parent[i] <= i always, a root is a pixel with
 // parent[i] == i, a union hangs the larger root under the smaller with one atomicMin and goes on with the value that atomic RETURNED
@@ -267,6 +269,197 @@ __global__ void __launch_bounds__(CC_THREADS) census_kernel(const unsigned char*
     if (tab[j]) atomicAdd(table + j, (unsigned long long)tab[j]);
 }
 
+// ------------------------------------------------------------------------------------------------------------------ object match
+// Two labellings of one map, (tlabel, tsize) of truth and (plabel, psize) of pred.  A truth object t can only match the predicted
+// object that holds more than half of it, so the pair table of the two labellings is never made: t's majority partner is found by a
+// weighted Boyer-Moore vote, one 64-bit word (candidate << 32 | count) per truth root.
+//   1. om_init_kernel    every vote word, inter[] and cover[] zeroed (the result does not depend on what the scratch held)
+//   2. om_vote_kernel    one workgroup per tile: the tile's same-class pairs (tlabel, plabel) and its counted pixels per predicted root
+//                        counted in LDS; one atomicAdd per (predicted root, tile) into cover[], one weighted vote per (pair, tile)
+//   3. om_count_kernel   (a LATER launch: the votes are final) inter[t] += the tile's pixels of the pair (t, candidate[t])
+//   4. om_decide_kernel  one thread per pixel: the test 3 I > |t| + cover(candidate) at the truth roots, match[] and inter[] stored
+// Any serialisation of the votes of step 2 is a run of the weighted majority algorithm on the same multiset, so where a partner with
+// more than half of the votes exists the word ends holding it, whatever the schedule.  Where none exists the candidate is arbitrary,
+// but step 3 counts its intersection exactly, the test of step 4 then fails (it implies I > |t| / 2) and inter is stored as 0: no
+// output depends on the schedule.  SCOPE as above: workgroup for the LDS tables, agent for the vote words and the adds that other
+// workgroups make in the same launch; the next phase reads them in a later launch.
+struct OmArgs {
+  const unsigned char* truth;
+  const unsigned char* pred;
+  const int* tlabel;
+  const unsigned int* tsize;
+  const int* plabel;
+  const unsigned int* psize;
+  unsigned long long* vote;                   // the scratch
+  int* match;
+  unsigned int* inter;
+  unsigned int* cover;
+  int h, w, K, ignore_label, tiles_x;
+};
+
+constexpr unsigned long long OM_EMPTY = ~0ull;
+
+__device__ __forceinline__ bool om_counted(const OmArgs& a, int tb) { return tb != a.ignore_label && tb < a.K; }
+
+// the per-tile (pair -> count) table: at most 1024 distinct pairs in CC_HASH slots, so a probe ends
+__device__ __forceinline__ void om_count_pair(unsigned long long* key, unsigned int* cnt, unsigned long long pair, unsigned int c) {
+  unsigned int s = (((unsigned int)(pair >> 32) * 2654435761u) ^ ((unsigned int)pair * 2246822519u)) >> 21;
+  for (;;) {
+    const unsigned long long old = atomicCAS(key + s, OM_EMPTY, pair);
+    if (old == OM_EMPTY || old == pair) break;
+    s = (s + 1) & (CC_HASH - 1);
+  }
+  atomicAdd(cnt + s, c);
+}
+
+// m votes for p in the word of one truth root.  The decision rests on the value the compare-and-swap returned.
+__device__ __forceinline__ void om_vote(unsigned long long* word, unsigned int p, unsigned int m) {
+  unsigned long long old = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (;;) {
+    const unsigned int cand = (unsigned int)(old >> 32), c = (unsigned int)old;
+    unsigned long long now;
+    if (cand == p) now = ((unsigned long long)p << 32) | (unsigned long long)(c + m);
+    else if (c >= m) now = ((unsigned long long)cand << 32) | (unsigned long long)(c - m);
+    else now = ((unsigned long long)p << 32) | (unsigned long long)(m - c);
+    if (__hip_atomic_compare_exchange_strong(word, &old, now, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  }
+}
+
+__global__ void __launch_bounds__(CC_THREADS) om_init_kernel(const OmArgs a) {
+  const int p = blockIdx.x * CC_THREADS + threadIdx.x;
+  if (p >= a.h * a.w) return;
+  a.vote[p] = 0ull;
+  a.inter[p] = 0u;
+  a.cover[p] = 0u;
+}
+
+// A wave whose 64 pixels agree on the pair, or on the predicted root, counts them at once, as the flatten kernel does.
+__global__ void __launch_bounds__(CC_THREADS) om_vote_kernel(const OmArgs a) {
+  __shared__ unsigned long long pkey[CC_HASH];
+  __shared__ unsigned int pcnt[CC_HASH];
+  __shared__ int ckey[CC_HASH];
+  __shared__ unsigned int ccnt[CC_HASH];
+  for (int s = threadIdx.x; s < CC_HASH; s += CC_THREADS) { pkey[s] = OM_EMPTY; pcnt[s] = 0u; ckey[s] = -1; ccnt[s] = 0u; }
+  __syncthreads();
+  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int y0 = ty * CC_T, x0 = tx * CC_T;
+  for (int j = 0; j < CC_PER; ++j) {
+    const int i = threadIdx.x + j * CC_THREADS, gy = y0 + (i >> 5), gx = x0 + (i & 31);
+    int cov = -1;                             // the predicted root this pixel adds to the cover of
+    unsigned long long pair = OM_EMPTY;       // the same-class pair this pixel belongs to
+    if (gy < a.h && gx < a.w) {
+      const int p = gy * a.w + gx;
+      const int tb = a.truth[p], pb = a.pred[p];
+      if (om_counted(a, tb) && pb < a.K) {
+        cov = a.plabel[p];
+        if (pb == tb) pair = ((unsigned long long)(unsigned int)a.tlabel[p] << 32) | (unsigned long long)(unsigned int)cov;
+      }
+    }
+    const int cov0 = __builtin_amdgcn_readfirstlane(cov);
+    if (__all(cov == cov0)) {
+      if (cov0 >= 0 && (threadIdx.x & 63) == 0) cc_count(ckey, ccnt, cov0, 64u);
+    } else if (cov >= 0) {
+      cc_count(ckey, ccnt, cov, 1u);
+    }
+    const unsigned int lo0 = __builtin_amdgcn_readfirstlane((unsigned int)pair), hi0 = __builtin_amdgcn_readfirstlane((unsigned int)(pair >> 32));
+    const unsigned long long pair0 = ((unsigned long long)hi0 << 32) | (unsigned long long)lo0;
+    if (__all(pair == pair0)) {
+      if (pair0 != OM_EMPTY && (threadIdx.x & 63) == 0) om_count_pair(pkey, pcnt, pair0, 64u);
+    } else if (pair != OM_EMPTY) {
+      om_count_pair(pkey, pcnt, pair, 1u);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < CC_HASH; s += CC_THREADS) {
+    if (ckey[s] >= 0) atomicAdd(a.cover + ckey[s], ccnt[s]);
+    if (pkey[s] != OM_EMPTY) om_vote(a.vote + (pkey[s] >> 32), (unsigned int)pkey[s], pcnt[s]);
+  }
+}
+
+// 3. the vote words are read, never written, here
+__global__ void __launch_bounds__(CC_THREADS) om_count_kernel(const OmArgs a) {
+  __shared__ int key[CC_HASH];
+  __shared__ unsigned int cnt[CC_HASH];
+  for (int s = threadIdx.x; s < CC_HASH; s += CC_THREADS) { key[s] = -1; cnt[s] = 0u; }
+  __syncthreads();
+  const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
+  const int y0 = ty * CC_T, x0 = tx * CC_T;
+  for (int j = 0; j < CC_PER; ++j) {
+    const int i = threadIdx.x + j * CC_THREADS, gy = y0 + (i >> 5), gx = x0 + (i & 31);
+    int r = -1;
+    if (gy < a.h && gx < a.w) {
+      const int p = gy * a.w + gx;
+      const int tb = a.truth[p];
+      if (om_counted(a, tb) && a.pred[p] == tb) {
+        const int t = a.tlabel[p];
+        if ((unsigned int)(a.vote[t] >> 32) == (unsigned int)a.plabel[p]) r = t;
+      }
+    }
+    const int first = __builtin_amdgcn_readfirstlane(r);
+    if (__all(r == first)) {
+      if (first >= 0 && (threadIdx.x & 63) == 0) cc_count(key, cnt, first, 64u);
+    } else if (r >= 0) {
+      cc_count(key, cnt, r, 1u);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < CC_HASH; s += CC_THREADS)
+    if (key[s] >= 0) atomicAdd(a.inter + key[s], cnt[s]);
+}
+
+// 4. every thread reads and writes its own element of inter[] only.  A candidate is a predicted root or the 0 the word started with:
+// below h w either way.
+__global__ void __launch_bounds__(CC_THREADS) om_decide_kernel(const OmArgs a) {
+  const int p = blockIdx.x * CC_THREADS + threadIdx.x;
+  if (p >= a.h * a.w) return;
+  int m = -2;
+  unsigned int keep = 0u;
+  if (a.tlabel[p] == p && om_counted(a, a.truth[p])) {
+    const unsigned int cand = (unsigned int)(a.vote[p] >> 32);
+    const unsigned long long I = a.inter[p];
+    m = -1;
+    if (3ull * I > (unsigned long long)a.tsize[p] + (unsigned long long)a.cover[cand]) { m = (int)cand; keep = (unsigned int)I; }
+  }
+  a.match[p] = m;
+  a.inter[p] = keep;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ object table
+constexpr int OT_ROWS = 4;
+
+__global__ void __launch_bounds__(CC_THREADS) object_table_kernel(const OmArgs a, int n, unsigned long long* table) {
+  __shared__ unsigned long long tab[CC_MAX_K * OT_ROWS * 32];
+  const int cells = a.K * OT_ROWS * 32;
+  for (int j = threadIdx.x; j < cells; j += CC_THREADS) tab[j] = 0ull;
+  __syncthreads();
+  for (long long q = (long long)blockIdx.x * CC_THREADS + threadIdx.x; q < n; q += (long long)gridDim.x * CC_THREADS) {
+    const int p = (int)q;
+    const int tb = a.truth[p], pb = a.pred[p];
+    if (a.tlabel[p] == p && om_counted(a, tb)) {
+      const unsigned int ts = a.tsize[p];
+      const int bin = 31 - __clz(ts);
+      unsigned long long* row = tab + tb * OT_ROWS * 32;
+      atomicAdd(row + bin, 1ull);
+      const int m = a.match[p];
+      if (m >= 0) {
+        const unsigned long long I = a.inter[p], cov = a.cover[m];
+        atomicAdd(row + 2 * 32 + bin, 1ull);
+        atomicAdd(row + 3 * 32 + bin, (I << 20) / ((unsigned long long)ts + cov - I));
+        // a matched predicted object counts whatever its cover: the one the walk over the predicted roots below leaves out is added here
+        const unsigned int ps = a.psize[m];
+        if (2ull * cov < (unsigned long long)ps) atomicAdd(row + 32 + 31 - __clz(ps), 1ull);
+      }
+    }
+    if (a.plabel[p] == p && pb < a.K) {
+      const unsigned int ps = a.psize[p];
+      if (2ull * (unsigned long long)a.cover[p] >= (unsigned long long)ps) atomicAdd(tab + (pb * OT_ROWS + 1) * 32 + 31 - __clz(ps), 1ull);
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < cells; j += CC_THREADS)
+    if (tab[j]) atomicAdd(table + j, tab[j]);
+}
+
 bool cc_shape_ok(int h, int w) { return h >= 1 && w >= 1 && (long long)h * (long long)w <= (long long)CC_MAX_PIXELS; }
 
 unsigned cc_blocks(long long n) { return (unsigned)((n + CC_THREADS - 1) / CC_THREADS); }
@@ -335,6 +528,46 @@ int drs_component_census(const unsigned char* map, const int* label, const unsig
   const unsigned need = cc_blocks((long long)h * w);
   DRS_LAUNCH(census_kernel, dim3(need < (unsigned)CC_CENSUS_GRID ? need : (unsigned)CC_CENSUS_GRID), dim3(CC_THREADS), 0,
              (hipStream_t)stream, map, label, size, h * w, K, table);
+  return DRS_LAUNCH_CHECK();
+}
+
+size_t drs_object_scratch_bytes(int h, int w) { return cc_shape_ok(h, w) ? (size_t)h * (size_t)w * sizeof(unsigned long long) : 0; }
+
+int drs_object_match(const unsigned char* truth, const unsigned char* pred, const int* tlabel, const unsigned int* tsize, const int* plabel,
+                     const unsigned int* psize, int h, int w, int K, int ignore_label, void* scratch, int* match, unsigned int* inter,
+                     unsigned int* cover, void* stream) {
+  if (!truth || !pred || !tlabel || !tsize || !plabel || !psize || !scratch || !match || !inter || !cover || !cc_shape_ok(h, w) || K < 1 ||
+      K > CC_MAX_K || ignore_label < -1 || ignore_label > 255)
+    return DRS_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const OmArgs a = {truth, pred, tlabel, tsize, plabel, psize, (unsigned long long*)scratch, match, inter, cover,
+                    h,     w,    K,      ignore_label, (w + CC_T - 1) / CC_T};
+  const unsigned ntiles = (unsigned)a.tiles_x * (unsigned)((h + CC_T - 1) / CC_T);
+  const unsigned blocks = cc_blocks((long long)h * w);
+  DRS_LAUNCH(om_init_kernel, dim3(blocks), dim3(CC_THREADS), 0, st, a);
+  int rc = DRS_LAUNCH_CHECK();
+  if (rc != DRS_OK) return rc;
+  DRS_LAUNCH(om_vote_kernel, dim3(ntiles), dim3(CC_THREADS), 0, st, a);
+  rc = DRS_LAUNCH_CHECK();
+  if (rc != DRS_OK) return rc;
+  DRS_LAUNCH(om_count_kernel, dim3(ntiles), dim3(CC_THREADS), 0, st, a);
+  rc = DRS_LAUNCH_CHECK();
+  if (rc != DRS_OK) return rc;
+  DRS_LAUNCH(om_decide_kernel, dim3(blocks), dim3(CC_THREADS), 0, st, a);
+  return DRS_LAUNCH_CHECK();
+}
+
+int drs_object_table(const unsigned char* truth, const int* tlabel, const unsigned int* tsize, const unsigned char* pred, const int* plabel,
+                     const unsigned int* psize, const int* match, const unsigned int* inter, const unsigned int* cover, int h, int w, int K,
+                     int ignore_label, unsigned long long* table, void* stream) {
+  if (!truth || !tlabel || !tsize || !pred || !plabel || !psize || !match || !inter || !cover || !table || !cc_shape_ok(h, w) || K < 1 ||
+      K > CC_MAX_K || ignore_label < -1 || ignore_label > 255)
+    return DRS_ERR_ARG;
+  const OmArgs a = {truth, pred, tlabel, tsize, plabel, psize, nullptr, const_cast<int*>(match), const_cast<unsigned int*>(inter),
+                    const_cast<unsigned int*>(cover), h, w, K, ignore_label, (w + CC_T - 1) / CC_T};
+  const unsigned need = cc_blocks((long long)h * w);
+  DRS_LAUNCH(object_table_kernel, dim3(need < (unsigned)CC_CENSUS_GRID ? need : (unsigned)CC_CENSUS_GRID), dim3(CC_THREADS), 0,
+             (hipStream_t)stream, a, h * w, table);
   return DRS_LAUNCH_CHECK();
 }
 

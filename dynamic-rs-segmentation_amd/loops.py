@@ -1227,6 +1227,51 @@ def _sieve_str(sieve, infos):
             " ".join(str(v) for v in total("objects_after")) + "]")
 
 
+def object_table(truth_dev, pred_dev, h, w, K, ignore_label, connectivity, table=None, stream=None):
+    """The object table of one (truth, prediction) pair of uint8 device maps [h][w] (include/drs.h): the connected
+    components of both maps at `connectivity` (two drs_components), the match of the two labellings (drs_object_match: a truth object
+    and a predicted object of the same class match iff their IoU exceeds 1/2, pixels over ignored truth aside) and the counts
+    (drs_object_table): int64 device tensor [K][4][32], by floor(log2(size)): truth objects, predicted objects, matched truth
+    objects, the sum of floor(IoU 2^20) over them.  `table` (such a tensor) is ADDED to and returned, so the maps of a split
+    accumulate; without it a zeroed one is made.  ignore_label: None or -1 for none.  stream: a raw stream handle (default: torch's
+    current stream on the maps' device); everything, the zeroing of a new table included, is enqueued there and nothing waits: a
+    caller that names a stream orders its own reads of the table after it.  metrics.object_scores turns the table into scores."""
+    from . import _lib
+    connectivity = P.check_object_scores(connectivity)
+    for name, m in (("truth", truth_dev), ("prediction", pred_dev)):
+        if m.dtype != torch.uint8 or m.numel() != h * w or not m.is_contiguous():
+            raise ValueError("object_table: the %s must be a contiguous uint8 tensor of %d x %d elements" % (name, h, w))
+    dev, n = truth_dev.device, h * w
+    if table is not None and (table.dtype != torch.int64 or tuple(table.shape) != (K, 4, 32) or not table.is_contiguous()):
+        raise ValueError("object_table: table must be a contiguous int64 tensor [%d][4][32]" % K)
+    ignore = -1 if ignore_label is None else int(ignore_label)
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if table is None:
+            table = torch.zeros((K, 4, 32), dtype=torch.int64, device=dev)
+        tlabel, tsize, plabel, psize, match, inter, cover = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(7)]
+        scratch = torch.empty(_lib.query("drs_object_scratch_bytes", int(h), int(w)) // 8, dtype=torch.int64, device=dev)
+        _lib.call("drs_components", truth_dev.data_ptr(), int(h), int(w), connectivity, tlabel.data_ptr(), tsize.data_ptr(), st)
+        _lib.call("drs_components", pred_dev.data_ptr(), int(h), int(w), connectivity, plabel.data_ptr(), psize.data_ptr(), st)
+        _lib.call("drs_object_match", truth_dev.data_ptr(), pred_dev.data_ptr(), tlabel.data_ptr(), tsize.data_ptr(), plabel.data_ptr(),
+                  psize.data_ptr(), int(h), int(w), int(K), ignore, scratch.data_ptr(), match.data_ptr(), inter.data_ptr(), cover.data_ptr(), st)
+        _lib.call("drs_object_table", truth_dev.data_ptr(), tlabel.data_ptr(), tsize.data_ptr(), pred_dev.data_ptr(), plabel.data_ptr(),
+                  psize.data_ptr(), match.data_ptr(), inter.data_ptr(), cover.data_ptr(), int(h), int(w), int(K), ignore, table.data_ptr(), st)
+    return table
+
+
+def _objects_str(connectivity, o):
+    """the Objects line's text from metrics.object_scores' dict"""
+    ints = lambda v: "[" + " ".join(str(int(x)) for x in v) + "]"
+    vals = lambda v: "[" + " ".join("{:.6f}".format(x) for x in v) + "]"
+    return ("Objects connectivity= " + str(connectivity) + " Truth= " + ints(o["truth"]) + " Predicted= " + ints(o["predicted"]) +
+            " Matched= " + ints(o["matched"]) + " Precision= " + vals(o["precision"]) + " Recall= " + vals(o["recall"]) +
+            " F1= " + vals(o["f1"]) + " SQ= " + vals(o["sq"]) + " PQ= " + vals(o["pq"]) +
+            " Mean F1= " + "{:.6f}".format(o["mean_f1"]) + " Mean SQ= " + "{:.6f}".format(o["mean_sq"]) +
+            " Mean PQ= " + "{:.6f}".format(o["mean_pq"]) + " All Objects F1= " + "{:.6f}".format(o["all"]["f1"]) +
+            " SQ= " + "{:.6f}".format(o["all"]["sq"]) + " PQ= " + "{:.6f}".format(o["all"]["pq"]))
+
+
 FIT_RESIDENT_BYTES = 32 << 30       # default cap on the accumulators fit_temperature keeps on the device
 
 
@@ -1278,7 +1323,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
                   dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None,
-                  boundary_scores=None, sieve=None):
+                  boundary_scores=None, sieve=None, object_scores=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1315,7 +1360,16 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     [before] -> [after]` follows the map's other lines, and one for all maps (counts summed, the most rounds) the all-maps lines.
     Returns (all-maps confusion matrix, label maps, extra) with extra["sieve"] = {"params": the SieveParams, "per_map": [sieve_labels'
     info per map], "rounds" (the most), "merged", "changed_pixels", "left_small", "objects_before", "objects_after" (summed)}.  Without
-    sieve nothing changes."""
+    sieve nothing changes.
+    object_scores (opt-in; any inference path; a connectivity, 4 or 8, patches.check_object_scores): object-level scores of every map
+    and of all maps: per map, one object_table call on the labels and the map that drs_confusion scored -- the sieved
+    refined map with crf / sieve --, with the ignore label the boundary scores pass; the connected regions of each class are the
+    objects, a truth object and a predicted one match iff their IoU exceeds 1/2.  Every rank scores the whole map itself and gets the
+    same bits.  One line `---- Iter N -- Test Map M: Objects connectivity= c Truth= [..] Predicted= [..] Matched= [..] Precision= [..]
+    Recall= [..] F1= [..] SQ= [..] PQ= [..] Mean F1= ... Mean SQ= ... Mean PQ= ... All Objects F1= ... SQ= ... PQ= ...` follows the
+    map's other lines, and one for all maps, from the summed table, the all-maps lines.  Returns (all-maps confusion matrix, label
+    maps, extra) with extra["objects"] = metrics.object_scores of the all-maps table, plus "connectivity", "table" (the int64 numpy
+    table [K][4][32]) and "per_map": [the same per map, each with its "table"].  Without object_scores nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
@@ -1324,6 +1378,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     beta = _check_temperature(temperature_beta, score_maps, crf)
     bdist = None if boundary_scores is None else P.check_boundary_distances(boundary_scores)
     sieve = None if sieve is None else P.check_sieve(sieve)
+    oconn = None if object_scores is None else P.check_object_scores(object_scores)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
@@ -1344,6 +1399,9 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     if bdist is not None:
         all_bhist = np.zeros((len(bdist) + 1, len(bdist) + 1, K, K), dtype=np.int64)
         boundary_list = []
+    if oconn is not None:
+        all_otable = np.zeros((K, 4, 32), dtype=np.int64)
+        object_list = []
     for k in range(len(testing_data)):
         pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
@@ -1390,6 +1448,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
                 print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _boundary_str(boundary_list[-1]))
         if sieve is not None and comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _sieve_str(sieve, sinfo))
+        if oconn is not None:
+            otable = object_table(lab, pred, h, w, K, ignore_label, oconn).cpu().numpy()       # on the current stream: the net's
+            all_otable += otable
+            object_list.append(dict(MT.object_scores(otable), table=otable))
+            if comm.rank == 0:
+                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _objects_str(oconn, object_list[-1]))
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -1426,7 +1490,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         for key in ("objects_before", "objects_after"):
             sv[key] = [sum(i[key][c] for i in sieve_list) for c in range(K)]
         extra = dict(extra if kinds is not None or bdist is not None else {}, sieve=sv)
-    if kinds is not None or bdist is not None or sieve is not None:
+    if oconn is not None:
+        obj = dict(MT.object_scores(all_otable), connectivity=oconn, table=all_otable, per_map=object_list)
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _objects_str(oconn, obj))
+        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None else {}, objects=obj)
+    if kinds is not None or bdist is not None or sieve is not None or oconn is not None:
         return all_cm, maps, extra
     return all_cm, maps
 

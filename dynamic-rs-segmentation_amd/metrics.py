@@ -92,6 +92,48 @@ def boundary_scores(hist, distances):
             "bands": bands}
 
 
+def object_scores(table):
+    """Object-level scores from the table of drs_object_table (include/drs.h): table [K][4][32] integers, by
+    floor(log2(size)): row 0 truth objects, row 1 predicted objects, row 2 matched truth objects, row 3 the sum over them of
+    floor(IoU 2^20).  Per class, in fp64:  TP = sum of row 2, FN = sum of row 0 - TP, FP = sum of row 1 - TP;
+      precision = TP / (TP + FP), recall = TP / (TP + FN), RQ = F1 = 2 TP / (2 TP + FP + FN)      (recognition quality)
+      SQ = sum of row 3 / (TP 2^20)    the mean IoU of the matched objects                        (segmentation quality)
+      PQ = SQ RQ                       (Kirillov et al. 2019)
+    A class with no truth object and no predicted object is absent: it has no score (nan) and is left out of the means, the way
+    iou_per_class treats an absent class.  Of a present class, precision is nan without a predicted object, recall without a truth
+    object and SQ without a match (PQ is then 0, as its sum form says); a mean runs over the classes that have the score, 0.0 without
+    any.  Returns {"truth", "predicted", "matched" (K ints each), "present", "precision", "recall", "f1", "sq", "pq" (K values),
+    "recall_by_size" ([K][32], nan where no truth object has that size), "mean_precision", "mean_recall", "mean_f1", "mean_sq",
+    "mean_pq", "all": the same counts and scores of the table summed over the classes}.  A table of another shape, of a non-integer
+    dtype, with a negative entry or with more matches than objects raises ValueError."""
+    t = np.asarray(table)
+    if t.ndim != 3 or t.shape[0] < 1 or t.shape[1:] != (4, 32) or not np.issubdtype(t.dtype, np.integer) or np.any(t < 0):
+        raise ValueError("object table: expected [K][4][32] non-negative integers, not %s of shape %r" % (t.dtype, t.shape))
+    t = t.astype(np.int64)
+    if np.any(t[:, 2] > t[:, 0]) or np.any(t[:, 2].sum(axis=1) > t[:, 1].sum(axis=1)):
+        raise ValueError("object table: more matched objects than objects")
+
+    def scores(rows):
+        """rows [..][4][32] -> the counts and scores along the leading axes"""
+        nt, npred, tp, s3 = [rows[..., r, :].sum(axis=-1) for r in range(4)]
+        fn, fp = nt - tp, npred - tp
+        present = (nt + npred) > 0
+        nan = np.full(nt.shape, np.nan)
+        div = lambda a, b, where: np.where(where, a / np.where(where, b, 1), nan)
+        f1 = div(2.0 * tp, 2.0 * tp + fp + fn, present)
+        sq = div(s3 / 2.0 ** 20, tp, tp > 0)
+        return {"truth": nt, "predicted": npred, "matched": tp, "present": present, "precision": div(tp, npred, npred > 0),
+                "recall": div(tp, nt, nt > 0), "f1": f1, "sq": sq, "pq": np.where(tp > 0, sq * f1, np.where(present, 0.0, np.nan))}
+    out = scores(t)
+    out["recall_by_size"] = np.where(t[:, 0] > 0, t[:, 2] / np.where(t[:, 0] > 0, t[:, 0], 1), np.nan)
+    for key in ("precision", "recall", "f1", "sq", "pq"):
+        have = ~np.isnan(out[key])
+        out["mean_" + key] = float(out[key][have].mean()) if have.any() else 0.0
+    whole = scores(t.sum(axis=0))
+    out["all"] = {k: (bool(v) if k == "present" else int(v) if k in ("truth", "predicted", "matched") else float(v)) for k, v in whole.items()}
+    return out
+
+
 def cohen_kappa(cm):
     """sklearn cohen_kappa_score(y_true, y_pred) from the confusion matrix."""
     cm = np.asarray(cm, dtype=np.float64)

@@ -636,6 +636,26 @@ def parse_sieve(text):
     return check_sieve([int(t) for t in parts]).min_size
 
 
+# ------------------------------------------------------------------- object-level scores of validation
+OBJECT_CONNECTIVITY = 4                    # what holds an object together by default: the sieve's default
+
+
+def check_object_scores(v):
+    """The connectivity of the object scores as an int: 4 (the default) or 8 (drs_components').  Anything else raises ValueError
+    naming the offending value."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in (4, 8):
+        raise ValueError("object scores connectivity %r: expected 4 or 8" % (v,))
+    return int(v)
+
+
+def parse_object_scores(text):
+    """The value of the command line's --object-scores option: "4" or "8" as an int (check_object_scores).  Anything else raises
+    ValueError."""
+    if not isinstance(text, str) or text not in ("4", "8"):
+        raise ValueError("object scores connectivity %r: expected 4 or 8" % (text,))
+    return check_object_scores(int(text))
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

@@ -770,6 +770,49 @@ int drs_sieve_round(const unsigned char* map_in, const int* label, const unsigne
                     void* scratch, unsigned char* map_out, unsigned int* counters, void* stream);
 int drs_component_census(const unsigned char* map, const int* label, const unsigned int* size, int h, int w, int K,
                          unsigned long long* table, void* stream);
+/* Object-level scores of a (truth, prediction) pair of label maps (opt-in; csrc/components.hip): per class, how many
+ * truth objects were found, how many predicted objects are spurious and how well the found ones are outlined -- recognition quality,
+ * segmentation quality and PQ = SQ RQ (Kirillov et al., Panoptic Segmentation, CVPR 2019, with the connected regions of each class
+ * as the segments).  NORMATIVE: this text and the numpy statement tests/objects_ref.py.  Integer-only: every output is exact and
+ * independent of tiling and scheduling.
+ * Inputs: truth and pred, uint8 [h][w] on the device; K in 1..32; ignore_label, -1 for none; a connectivity c in {4, 8}; (tlabel, tsize)
+ *     and (plabel, psize): what drs_components gives for truth and for pred at c.
+ * Terms: a truth pixel is COUNTED iff truth != ignore_label and truth < K.  A truth object t is a component of truth whose byte is
+ *     counted; |t| = tsize.  A predicted object p is a component of pred with byte < K; |p| = psize.  cover(p) = the number of pixels
+ *     of p whose truth pixel is counted.  I(t, p) = |t n p|, used only when t and p carry the same byte.
+ *     IoU(t, p) = I / (|t| + cover(p) - I): pixels of p over ignored truth count neither for nor against it.
+ * Match: t and p of the same class match iff IoU > 1/2, in integers 3 I > |t| + cover(p).  The match is unique in both directions:
+ *     from cover(p) >= I the test gives I > |t| / 2, so at most one p can match a given t; from |t| >= I it gives I > cover(p) / 2, and
+ *     the intersections of p with different t are disjoint, so at most one t can match a given p.  No assignment problem arises and
+ *     nothing depends on order.
+ * Unmatched predicted objects: an unmatched p counts as a predicted object iff 2 cover(p) >= |p|; one that lies mostly over ignored
+ *     truth is dropped, as Kirillov et al. drop segments that are mostly void.
+ * Outputs of the match (int32 / uint32 [h w], every element stored):
+ *     match[i]: i a root of a truth object (tlabel[i] == i, counted): the root of the matched p, or -1; every other i: -2.
+ *     inter[i]: root of a matched truth object: I; every other i: 0.
+ *     cover[i]: i a root of a predicted object: cover(p); every other i: 0.
+ * Table: table[K][4][32], 64-bit device counters, ADDED to, so the maps of a split accumulate; bin(n) = floor(log2 n).
+ *     row 0: truth objects by bin(|t|).   row 1: predicted objects by bin(|p|): the matched ones plus the unmatched ones with
+ *     2 cover >= |p|.   row 2: matched truth objects by bin(|t|).   row 3: the sum over the matched truth objects, by bin(|t|), of
+ *     floor(I 2^20 / (|t| + cover(p) - I)), a 64-bit integer division: exact and order-free.
+ * Scores (the host's, metrics.object_scores, fp64), per class and over all classes: TP = sum of row 2, FN = sum of row 0 - TP,
+ *     FP = sum of row 1 - TP; precision, recall, RQ = F1 = 2 TP / (2 TP + FP + FN); SQ = sum of row 3 / (TP 2^20); PQ = SQ RQ; recall
+ *     per size bin row 2 / row 0.  A class with no truth object and no predicted object has no score.
+ *
+ * drs_object_scratch_bytes: bytes of drs_object_match's scratch for an h x w map (8 h w: one vote word per pixel); 0 outside the ranges.
+ * drs_object_match: match, inter and cover of the pair (four launches: init, the weighted majority vote of every truth object for its
+ *     partner, the intersection with the elected candidate, the test).  It initialises what it reads of its scratch: the result does
+ *     not depend on what the scratch held.
+ * drs_object_table: the table from the outputs of drs_object_match on the same arguments (one launch).
+ * No entry point synchronises.  Ranges, else DRS_ERR_ARG (nothing is launched, no pointer is read): pointers not NULL; h, w >= 1,
+ * h w <= 2^30; 1 <= K <= 32; -1 <= ignore_label <= 255. */
+size_t drs_object_scratch_bytes(int h, int w);
+int drs_object_match(const unsigned char* truth, const unsigned char* pred, const int* tlabel, const unsigned int* tsize, const int* plabel,
+                     const unsigned int* psize, int h, int w, int K, int ignore_label, void* scratch, int* match, unsigned int* inter,
+                     unsigned int* cover, void* stream);
+int drs_object_table(const unsigned char* truth, const int* tlabel, const unsigned int* tsize, const unsigned char* pred, const int* plabel,
+                     const unsigned int* psize, const int* match, const unsigned int* inter, const unsigned int* cover, int h, int w, int K,
+                     int ignore_label, unsigned long long* table, void* stream);
 
 /* ==================================================================================================================
  * Training level: boundary-weighted cross-entropy (opt-in; csrc/boundary.hip, csrc/pointwise.hip).  A per-pixel weight
