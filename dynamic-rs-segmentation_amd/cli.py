@@ -46,6 +46,10 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     --focal-gamma): every pixel's loss term is multiplied by 1 + a exp(-d^2 / 2 sigma^2), d the distance to the nearest pixel of
     another class inside the patch and a (2R + 1)^2 window; a in [-1, 64] (0: off), sigma in (0, 64] (default 4), R in 1..16
     (default min(16, ceil(3 sigma))) (loops.train's boundary_weight)
+  + optionally, anywhere, in all three flavours, `--dice-weight=lam[,alpha,beta[,smooth]]` (training; beside --class-weights,
+    --focal-gamma and --boundary-weight, which do not weight it): lam times a soft Dice / Tversky term per patch is added to the loss;
+    lam in [0, 64] (0: off), alpha and beta in [0, 1] (default 0.5,0.5: Dice), smooth in (0, 2^20] (default 1) (loops.train's dice;
+    DESIGN.md 3d)
   + optionally, anywhere, in all three flavours, `--scale-jitter=lo,hi` (training): every training patch is resampled at a scale
     drawn log-uniformly from [lo, hi], 0.25 <= lo <= hi <= 4 (loops.train's scale_jitter); validation and inference
     stay at scale 1
@@ -308,6 +312,18 @@ def parse_boundary_weight(argv):
             BOUNDARY_WEIGHT_FLAG, P.MAX_BOUNDARY_A, P.MAX_BOUNDARY_SIGMA, P.MAX_BOUNDARY_R)))
 
 
+DICE_FLAG = "--dice-weight"
+
+
+def parse_dice(argv):
+    """all flavours: the optional `--dice-weight=lam[,alpha,beta[,smooth]]` (anywhere in argv; training).  Returns (argv without the
+    flag, (lam, alpha, beta, smooth) with the defaults filled in), or (argv unchanged, None) without it.  A bare flag, a value outside
+    the ranges of patches.check_dice, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, DICE_FLAG, lambda a, v: _or_expected(
+        P.parse_dice, a, v, "%s=lam[,alpha,beta[,smooth]] (lam in [0, %g], alpha and beta in [0, 1], smooth in (0, %g])" % (
+            DICE_FLAG, P.MAX_DICE_LAMBDA, P.MAX_DICE_SMOOTH)))
+
+
 SCALE_JITTER_FLAG = "--scale-jitter"
 
 
@@ -387,6 +403,7 @@ def main(argv=None, device=None, comm=None):
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
+        argv, dice = parse_dice(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -426,6 +443,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the training process only")
     if boundary_weight is not None and argv[16] != "training":
         sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the training process only")
+    if dice is not None and argv[16] != "training":
+        sys.exit(DICE_FLAG + " applies to the training process only")
     if scale_jitter is not None and argv[16] != "training":
         sys.exit(SCALE_JITTER_FLAG + " applies to the training process only")
     if comm.rank == 0:
@@ -478,7 +497,7 @@ def main(argv=None, device=None, comm=None):
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
                            class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter,
-                           boundary_weight=boundary_weight)
+                           boundary_weight=boundary_weight, dice=dice)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -552,6 +571,7 @@ def main_coffee(argv=None, device=None, comm=None):
         argv, class_weights = parse_class_weights(argv, 2)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
+        argv, dice = parse_dice(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -571,7 +591,7 @@ def main_coffee(argv=None, device=None, comm=None):
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
                     quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma,     # coffee:293: training patches pass through float16
-                    scale_jitter=scale_jitter, boundary_weight=boundary_weight)
+                    scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice)
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -583,6 +603,7 @@ def main_contest(argv=None, device=None, comm=None):
         argv, class_weights = parse_class_weights(argv, 7)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
+        argv, dice = parse_dice(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -595,6 +616,8 @@ def main_contest(argv=None, device=None, comm=None):
         sys.exit(FOCAL_GAMMA_FLAG + " applies to the train operation only")
     if boundary_weight is not None and operation != "train":
         sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the train operation only")
+    if dice is not None and operation != "train":
+        sys.exit(DICE_FLAG + " applies to the train operation only")
     if scale_jitter is not None and operation != "train":
         sys.exit(SCALE_JITTER_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
@@ -614,7 +637,7 @@ def main_contest(argv=None, device=None, comm=None):
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
                         void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
-                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight)
+                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

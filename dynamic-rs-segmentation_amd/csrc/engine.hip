@@ -142,9 +142,9 @@ struct LayerPtrs {
 struct Ptrs {
   bool ok = false;
   float *params, *grads, *momentum, *bn, *partial, *gxh, *gz[2], *slab, *w0pad, *conv_ws, *bwd_means, *act, *gpool, *se_scratch;
-  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight;
+  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef;
   size_t conv_ws_floats;
-  double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch;
+  double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch, *dice_loss;
   unsigned char *pred, *labels, *acc_mask, *loss_mask;
   unsigned int* conf;
   std::vector<LayerPtrs> L;
@@ -194,6 +194,7 @@ struct drs_net {
   float focal_gamma = 0.f;                  // focusing parameter of the training loss (drs_net_set_focal_gamma); 0: no focal term
   double bw_a = 0.0, bw_sigma = 4.0;         // boundary weight of the training loss (drs_net_set_boundary_weight); a == 0: off, no launch
   int bw_R = 12;
+  double dice_lam = 0.0, dice_alpha = 0.5, dice_beta = 0.5, dice_smooth = 1.0;      // soft Dice / Tversky term of the training loss (drs_net_set_dice); lam == 0: off, no launch
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -425,6 +426,8 @@ void list_buffers(drs_net* n) {
   n->add_buf("loss_partial", crow, F64);
   n->add_buf("scalars", 4, F64);             // [0] mean CE (all ranks), [1] 0.5 * sum w^2
   n->add_buf("l2_scratch", 256, F64);
+  n->add_buf("dice_coef", B * n->K * 2, F32);      // (G_in, G_out) per patch and class, and the patches' loss terms (drs_net_set_dice); untouched while it is off
+  n->add_buf("dice_loss", B, F64);
   n->add_buf("logits", M * n->K, F32);
   n->add_buf("pred", M, U8);
   n->add_buf("conf", (size_t)n->K * n->K, I32);
@@ -578,6 +581,7 @@ bool resolve(drs_net* n) {
   P.pred = n->p<unsigned char>("pred"); P.labels = n->p<unsigned char>("labels"); P.acc_mask = n->p<unsigned char>("acc_mask");
   P.loss_mask = n->p<unsigned char>("loss_mask"); P.conf = n->p<unsigned int>("conf");
   P.pixel_weight = n->p<float>("pixel_weight");
+  P.dice_coef = n->p<float>("dice_coef"); P.dice_loss = n->p<double>("dice_loss");
   const Slab& f = n->slabs[n->feat];
   P.feat_act = n->p<float>("act:" + f.name); P.feat_gact = n->p<float>("gact:" + f.name);
   P.L.assign(n->layers.size(), LayerPtrs());
@@ -1109,6 +1113,26 @@ int drs_net_get_boundary_weight(const drs_net_t* n, double* a, double* sigma, in
   return DRS_OK;
 }
 
+// Soft Dice / Tversky term of the training loss (drs_train_step only; include/drs.h, "Training level: soft Dice / Tversky term"):
+// lam == 0 switches it off.  The step then runs the classifier in its inference form into "logits", drs_patch_dice_coeffs over them,
+// and the fused classifier as drs_classifier_loss_dice; the patches' terms join scalars[0] before its all-reduce.
+int drs_net_set_dice(drs_net_t* n, double lam, double alpha, double beta, double smooth) {
+  if (!n || !std::isfinite(lam) || lam < 0.0 || lam > 64.0 || !(alpha >= 0.0 && alpha <= 1.0) || !(beta >= 0.0 && beta <= 1.0) ||
+      !std::isfinite(smooth) || !(smooth > 0.0) || smooth > 1048576.0)
+    return DRS_ERR_ARG;
+  n->dice_lam = lam; n->dice_alpha = alpha; n->dice_beta = beta; n->dice_smooth = smooth;
+  return DRS_OK;
+}
+
+int drs_net_get_dice(const drs_net_t* n, double* lam, double* alpha, double* beta, double* smooth) {
+  if (!n) return DRS_ERR_ARG;
+  if (lam) *lam = n->dice_lam;
+  if (alpha) *alpha = n->dice_alpha;
+  if (beta) *beta = n->dice_beta;
+  if (smooth) *smooth = n->dice_smooth;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1317,18 +1341,29 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   float* gfeat = P.feat_gact;
   double* scalars = P.scalars;
   double* scratch = P.colsum_scratch;
+  const bool dice = n->dice_lam != 0.0;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
     const bool bw = n->bw_a != 0.0;          // off: no launch, and drs_classifier_loss_pixel without a map is drs_classifier_loss_focal
     if (bw)
       DRS_TRY(drs_patch_boundary_weight(P.labels, (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, B, S, n->bw_R, n->bw_a,
                                         1.0 / (2.0 * n->bw_sigma * n->bw_sigma), nullptr, P.pixel_weight, st));
-    DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
-                                      P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
-                                      (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                      n->has_wc ? n->wc : nullptr, n->focal_gamma, bw ? P.pixel_weight : nullptr,
-                                      (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
-                                      P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    // the Dice term needs sums over whole patches before any gradient: the classifier once in its inference form (logits only), the
+    // coefficients of every (patch, class), then the fused launch with them.  Off: none of it, and drs_classifier_loss_dice without
+    // coefficients is drs_classifier_loss_pixel
+    if (dice) {
+      DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b, nullptr, nullptr,
+                                        nullptr, 1.f, nullptr, 0.f, nullptr, P.logits, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
+                                        nullptr, st));
+      DRS_TRY(drs_patch_dice_coeffs(P.logits, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K, n->dice_lam,
+                                    n->dice_alpha, n->dice_beta, n->dice_smooth, nullptr, P.dice_coef, P.dice_loss, st));
+    }
+    DRS_TRY(drs_classifier_loss_dice(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+                                     P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                     (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
+                                     n->has_wc ? n->wc : nullptr, n->focal_gamma, bw ? P.pixel_weight : nullptr,
+                                     dice ? P.dice_coef : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
+                                     P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
   }
   // the classifier's slab reductions (its kernel / bias gradients, the cross-entropy sum) and the L2 term: seven launches of ~5 us that
   // nothing needs before the end of the step -- in the two-stream backward pass they go to the filter-gradient stream (below), off
@@ -1338,6 +1373,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     DRS_TRY(drs_rows_reduce_f32(P.dw_partial, crow, n->c_last * n->K, grads + n->cls_w, scratch, s));
     DRS_TRY(drs_rows_reduce_f32(P.db_partial, crow, n->K, grads + n->cls_b, scratch, s));
     DRS_TRY(drs_sum_f64(P.loss_partial, crow, scalars, s));
+    if (dice) DRS_TRY(drs_dice_loss_add(P.dice_loss, B, scalars, s));      // (+ the patches' Dice terms: scalars[0] goes on to its all-reduce and 1 / n_glob as before)
     DRS_TRY(drs_l2_loss(params, n->n_decay, P.l2_scratch, scalars + 1, s));
     return DRS_OK;
   };

@@ -897,6 +897,8 @@ struct ClsArgs {
   float wc[8];               // class weights of the weighted and focal forms, by value: scalar registers, no buffer and no load
   float gamma;               // focusing parameter of the focal forms (CLS_FOCAL), by value; the other forms do not read it
   const float* pixel_weight; // [M] per-pixel weights of the CLS_PIXEL forms (the boundary weight map); the other forms do not read it
+                             // (the CLS_DICE forms read it when it is not null)
+  const float* dice_coef;    // [B][K][2] (G_in, G_out) of the CLS_DICE forms (drs_patch_dice_coeffs); the other forms do not read it
 };
 
 // Loss mode of the three classifier forms (template argument LM).  CLS_PLAIN: the cross-entropy, the code the kernels always had;
@@ -904,8 +906,17 @@ struct ClsArgs {
 // CLS_PIXEL, a flag on top of CLS_WEIGHTED or CLS_FOCAL (never CLS_PLAIN): the pixel's own weight pixel_weight[p] is multiplied into
 // wc[y] -- one more load and one more multiply per pixel, in the slot the class weight already has; nothing else changes, so the
 // order of every sum is that of the form without the flag.  cls_base(LM) strips it.
-constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2, CLS_PIXEL = 4;
+// CLS_DICE, a flag on top of CLS_WEIGHTED or CLS_FOCAL (never CLS_PLAIN, never with CLS_PIXEL): the soft Dice / Tversky term of the
+// pixel's patch (include/drs.h) is ADDED to the pixel's logit gradients, inv_n P_k (g_k - sum_c P_c g_c) with
+// g_c = [y == c] ? G_in[b][c] : G_out[b][c] from dice_coef; class weights, focal factor and pixel weight do not touch it, and the loss
+// sum stays the cross-entropy part.  The Dice forms always multiply a pixel weight in: pixel_weight[p], or 1 when there is no map
+// (x * 1 is x: the cross-entropy part is bit for bit that of the form without the flag), which halves the instantiations.
+constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2, CLS_PIXEL = 4, CLS_DICE = 8;
 constexpr int cls_base(int lm) { return lm & 3; }
+constexpr bool cls_has_pw(int lm) { return (lm & (CLS_PIXEL | CLS_DICE)) != 0; }
+// A pixel's Dice coefficients in the matrix-core forms: (G_in, G_out) of its patch for the lane's two class slots
+typedef float cls_f32x2 __attribute__((ext_vector_type(2)));
+struct ClsDice { cls_f32x2 c0, c1; };
 
 // The weight of a pixel's label: a register select over the eight by-value weights (a label outside [0, K) never enters the loss:
 // whatever comes out for it is multiplied into nothing)
@@ -1063,6 +1074,7 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
     constexpr bool WT = LM != CLS_PLAIN;
     float wy = WT ? cls_weight<KM>(a, y) : 1.f;
     if constexpr ((LM & CLS_PIXEL) != 0) wy *= a.pixel_weight[p];
+    if constexpr ((LM & CLS_DICE) != 0) wy *= a.pixel_weight ? a.pixel_weight[p] : 1.f;
     if constexpr (cls_base(LM) == CLS_FOCAL) {
       // every lane holds all the classes: so in ascending class order, then a few scalar-like operations per pixel
       float so = 0.f;
@@ -1086,6 +1098,21 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
         if (k == y) ly = lg[k];
       }
       if (in_loss) lsum += cls_loss_term<LM>(wy, se, mx, ly, 0.f, 0.f);
+    }
+    if constexpr ((LM & CLS_DICE) != 0) {
+      if (in_loss) {          // (wave-uniform: every lane holds the pixel's label and mask)
+        int b, rem;
+        divmod24(p, a.feat.S * a.feat.S, a.rcpSS, b, rem);
+        const float* cf = a.dice_coef + (size_t)b * K * 2;
+        float g[KM], s = 0.f;
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+          g[k] = k < K ? (k == y ? cf[2 * k] : cf[2 * k + 1]) : 0.f;
+          s += ex[k] * inv * g[k];
+        }
+#pragma unroll
+        for (int k = 0; k < KM; ++k) dl[k] += a.inv_n * (ex[k] * inv) * (g[k] - s);
+      }
     }
     if (a.gfeat) {
 #pragma unroll
@@ -1232,15 +1259,15 @@ __device__ __forceinline__ void cls_mc_argmax_store(const ClsArgs& a, int K, int
 // == b + a bit for bit; the logit sum has one non-zero term: exact); the focal ex_y is recomputed from that logit, the same
 // instruction on the same operands as in the lane that owns class y.
 template <int LM>
-__device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, float pw, int cls0, int cls1, float lg0,
-                                                  float lg1, float mx, float& dl0, float& dl1, double& lsum) {
+__device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, float pw, const ClsDice& dc, int cls0,
+                                                  int cls1, float lg0, float lg1, float mx, float& dl0, float& dl1, double& lsum) {
   const float ex0 = cls0 < K ? __expf(lg0 - mx) : 0.f, ex1 = cls1 < K ? __expf(lg1 - mx) : 0.f;
   float se = ex0 + ex1;
   se += __shfl_xor(se, 16);
   se += __shfl_xor(se, 32);
   const float inv = 1.0f / se;
   float wy = LM != CLS_PLAIN ? cls_weight(a, y) : 1.f;
-  if constexpr ((LM & CLS_PIXEL) != 0) wy *= pw;          // (pw: the pixel's weight, the same bits in its four lanes; unread otherwise)
+  if constexpr (cls_has_pw(LM)) wy *= pw;          // (pw: the pixel's weight, the same bits in its four lanes; unread otherwise)
   if constexpr (cls_base(LM) == CLS_FOCAL) {
     float so = (cls0 == y ? 0.f : ex0) + (cls1 == y ? 0.f : ex1);
     so += __shfl_xor(so, 16);
@@ -1261,6 +1288,24 @@ __device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y
     if (in_loss && cls0 == y) lsum += cls_loss_term<LM>(wy, se, mx, lg0, 0.f, 0.f);
     if (in_loss && cls1 == y) lsum += cls_loss_term<LM>(wy, se, mx, lg1, 0.f, 0.f);
   }
+  if constexpr ((LM & CLS_DICE) != 0) {
+    // the Dice term (dc: the coefficients of the pixel's patch for this lane's two slots, unread otherwise): sum_c P_c g_c over the
+    // pixel's four lanes by the exchange pattern of se; a slot beyond K has ex = 0 and adds nothing
+    const float g0 = cls0 == y ? dc.c0.x : dc.c0.y, g1 = cls1 == y ? dc.c1.x : dc.c1.y;
+    const float pr0 = ex0 * inv, pr1 = ex1 * inv;
+    float s = pr0 * g0 + pr1 * g1;
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    dl0 += in_loss ? a.inv_n * pr0 * (g0 - s) : 0.f;
+    dl1 += in_loss ? a.inv_n * pr1 * (g1 - s) : 0.f;
+  }
+}
+
+// The address of a pixel's Dice coefficients for class slot cls (slot 0's for a slot beyond K: loaded, never used)
+__device__ __forceinline__ const cls_f32x2* cls_dice_at(const ClsArgs& a, int K, int pix, int cls) {
+  int b, rem;
+  divmod24(pix, a.feat.S * a.feat.S, a.rcpSS, b, rem);
+  return reinterpret_cast<const cls_f32x2*>(a.dice_coef) + (size_t)b * K + (cls < K ? cls : 0);
 }
 
 // The workgroup's sums in wave order, into slab row blockIdx.x, and its confusion counts into a.conf.
@@ -1386,8 +1431,14 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
     if (G == 0 && valid && a.conf && (!a.acc_mask || a.acc_mask[pix]) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
     const bool in_loss = valid && (!a.loss_mask || a.loss_mask[pixc]) && y < K;     // a label outside [0, K) never trains the net
     float dl0, dl1, pw = 1.f;
+    ClsDice dc = {};
     if constexpr ((LM & CLS_PIXEL) != 0) pw = a.pixel_weight[pixc];
-    cls_mc_pixel_grad<LM>(a, K, y, in_loss, pw, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
+    if constexpr ((LM & CLS_DICE) != 0) {
+      if (a.pixel_weight) pw = a.pixel_weight[pixc];
+      dc.c0 = *cls_dice_at(a, K, pixc, cls0);
+      dc.c1 = *cls_dice_at(a, K, pixc, cls1);
+    }
+    cls_mc_pixel_grad<LM>(a, K, y, in_loss, pw, dc, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
     db0 += dl0;
     db1 += dl1;
     if (!a.gfeat) continue;
@@ -1502,6 +1553,14 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
     float vpw = 1.f;          // the pixel's weight (CLS_PIXEL): a fourth load beside the three bytes, older than the DMA like them
     if constexpr ((LM & CLS_PIXEL) != 0)
       asm volatile("global_load_dword %0, %1, off" : "=v"(vpw) : "v"(a.pixel_weight + pixc) : "memory");
+    // CLS_DICE: the pixel weight (no map: any readable float keeps the load count fixed; the value is dropped below) and the two
+    // 8-byte coefficient pairs of the lane's class slots -- three more loads that are older than the DMA, like the bytes
+    ClsDice dc = {};
+    if constexpr ((LM & CLS_DICE) != 0) {
+      asm volatile("global_load_dword %0, %1, off" : "=v"(vpw) : "v"(a.pixel_weight ? a.pixel_weight + pixc : a.dice_coef) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dc.c0) : "v"(cls_dice_at(a, K, pixc, cls0)) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dc.c1) : "v"(cls_dice_at(a, K, pixc, cls1)) : "memory");
+    }
     if (TRAIN) {
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(ylab) : "v"(a.labels + pixc) : "memory");
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(vlm) : "v"(lm + pixc) : "memory");
@@ -1532,13 +1591,17 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       if (tb + 64 < pend) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(ylab), "+v"(vlm), "+v"(vam) : "n"(NI) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" : "+v"(ylab), "+v"(vlm), "+v"(vam) :: "memory");
       if constexpr ((LM & CLS_PIXEL) != 0) asm volatile("" : "+v"(vpw) :: "memory");      // (the same wait covers it: read only from here on)
+      if constexpr ((LM & CLS_DICE) != 0) {      // (and the Dice loads: issued before the DMA, so older than the NI operations the wait leaves)
+        asm volatile("" : "+v"(vpw), "+v"(dc.c0), "+v"(dc.c1) :: "memory");
+        vpw = a.pixel_weight ? vpw : 1.f;
+      }
       const int y = (int)ylab;
       if (G == 0 && valid && a.conf && (!a.acc_mask || vam) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
       const bool in_loss = valid && (!a.loss_mask || vlm) && y < K;
       // (the weight select and the focal factor's four cross-lane moves and arithmetic: vector-ALU work of the softmax section,
       // after the logits' MFMAs have been issued and before the filter gradient's -- no MFMA waits for it)
       float dl0, dl1;
-      cls_mc_pixel_grad<LM>(a, K, y, in_loss, vpw, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
+      cls_mc_pixel_grad<LM>(a, K, y, in_loss, vpw, dc, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
       db0 += dl0;
       db1 += dl1;
       if (a.gfeat) {
@@ -1591,7 +1654,8 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
 
 // Run-time launch parameters onto template arguments, handed to a generic lambda as std::integral_constants.
 // cls_width: the width C / 64 = Q .. QMAX - 1, anything else QMAX.  cls_mode: (loss mode, labels present) onto <TRAIN, LM> -- the
-// weighted and focal modes, with or without CLS_PIXEL, exist for training only, so no TRAIN = false kernel is instantiated with them.
+// weighted and focal modes, with or without CLS_PIXEL or CLS_DICE, exist for training only, so no TRAIN = false kernel is instantiated
+// with them.
 template <int Q, int QMAX, typename F>
 static void cls_width(int cq, F&& f) {
   if constexpr (Q < QMAX)
@@ -1600,7 +1664,9 @@ static void cls_width(int cq, F&& f) {
 }
 template <typename F>
 static void cls_mode(int lm, bool train, F&& f) {
-  if (lm == (CLS_FOCAL | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_PIXEL>{});
+  if (lm == (CLS_FOCAL | CLS_DICE)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_DICE>{});
+  else if (lm == (CLS_WEIGHTED | CLS_DICE)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_DICE>{});
+  else if (lm == (CLS_FOCAL | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_PIXEL>{});
   else if (lm == (CLS_WEIGHTED | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_PIXEL>{});
   else if (lm == CLS_FOCAL) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL>{});
   else if (lm == CLS_WEIGHTED) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED>{});
@@ -2044,12 +2110,15 @@ int drs_debug_cls_variant(int v) { const int old = g_cls_variant; if (v >= 0) g_
 // value.  focal_gamma: 0 is not a focal launch -- the dispatch above, unchanged; in (0, 8] with labels the CLS_FOCAL instantiations,
 // which carry gamma by value and multiply the weights in, ones when none are set.  pixel_weight: DEVICE pointer to B S S floats or
 // NULL.  NULL or no labels: the dispatch above, unchanged; otherwise the CLS_PIXEL instantiations of the weighted form (the focal one
-// with gamma > 0), which multiply pixel_weight[p] into the class weight (ones when none are set).
-int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
-                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
-                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
-                              const float* pixel_weight, float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g,
-                              float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
+// with gamma > 0), which multiply pixel_weight[p] into the class weight (ones when none are set).  dice_coef: DEVICE pointer to
+// B K 2 floats (8-byte aligned) or NULL.  NULL or no labels: the dispatch above, unchanged; otherwise the CLS_DICE instantiations of the
+// weighted form (the focal one with gamma > 0), which read the map when there is one.
+int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                             const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                             const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                             const float* pixel_weight, const float* dice_coef, float* logits, unsigned char* pred, float* gfeat,
+                             int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
+                             void* stream) {
   if (!feat || !w || !bias || K < 1 || K > 8 || C < 64 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
   if (B < 1 || S < 1 || P < 0 || !std::isfinite(inv_n) || inv_n < 0.f) return DRS_ERR_ARG;
   if (!std::isfinite(focal_gamma) || focal_gamma < 0.f || focal_gamma > 8.f) return DRS_ERR_ARG;
@@ -2060,6 +2129,7 @@ int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, in
   if (ld % 4 || coff % 4 || (gfeat && (ld_g % 4 || coff_g % 4))) return DRS_ERR_ARG;       // 16-byte feature / gradient accesses
   if (!drs_slice_ok(ld, coff, C, 4) || (gfeat && !drs_slice_ok(ld_g, coff_g, C, 4))) return DRS_ERR_ARG;
   if ((long long)B * (S + 2LL * P) * (S + 2LL * P) * ld >= (1LL << 30)) return DRS_ERR_ARG;      // 32-bit byte offsets into the feature slab
+  if ((uintptr_t)dice_coef % 8) return DRS_ERR_ARG;                                             // 8-byte coefficient pairs
   bool wt = false;        // (class_weights is a HOST pointer: read only once everything else has passed)
   if (class_weights)
     for (int k = 0; k < K; ++k) {
@@ -2069,7 +2139,9 @@ int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, in
   wt = wt && labels;
   const bool focal = focal_gamma > 0.f && labels;
   const bool px = pixel_weight && labels;
-  const int lm = px ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_PIXEL) : focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
+  const bool dice = dice_coef && labels;
+  const int lm = dice ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_DICE)
+                      : px ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_PIXEL) : focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
   ClsArgs a;
   a.feat = mkview(const_cast<float*>(feat), S, P, ld, coff); a.C = C; a.K = K; a.M = (int)M; a.w = w; a.bias = bias;
   a.labels = labels; a.loss_mask = loss_mask; a.acc_mask = acc_mask; a.inv_n = inv_n; a.logits = logits; a.pred = pred;
@@ -2079,6 +2151,7 @@ int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, in
   for (int k = 0; k < 8; ++k) a.wc[k] = wt && k < K ? class_weights[k] : 1.f;
   a.gamma = focal ? focal_gamma : 0.f;
   a.pixel_weight = px ? pixel_weight : nullptr;
+  a.dice_coef = dice ? dice_coef : nullptr;
   const int nblk = drs_classifier_rows(B, S);
   a.rows_per_block = (int)(((M + nblk - 1) / nblk + 63) / 64 * 64);      // whole 16-pixel tiles per wave; trailing workgroups may be empty
   hipStream_t st = (hipStream_t)stream;
@@ -2118,6 +2191,15 @@ int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, in
     });
   });
   return DRS_LAUNCH_CHECK();
+}
+
+int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                              const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                              const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                              const float* pixel_weight, float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g,
+                              float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf, void* stream) {
+  return drs_classifier_loss_dice(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, class_weights, focal_gamma,
+                                  pixel_weight, nullptr, logits, pred, gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf, stream);
 }
 
 int drs_classifier_loss_focal(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,

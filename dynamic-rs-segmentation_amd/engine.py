@@ -106,7 +106,7 @@ class EngineNet(DilatedNet):
         self.idx = [b.get("idx%d" % i) for i in range(nl)]
         self.mean_rstd = [b["mean_rstd%d" % i] for i in range(nl)]
         for n in ("sums", "partial", "gxh", "gz", "slab", "w0pad", "dw_partial", "db_partial", "loss_partial", "scalars", "logits", "pred", "conf",
-                  "labels", "acc_mask", "loss_mask", "pixel_weight"):
+                  "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss"):
             setattr(self, n, b[n])
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
@@ -325,6 +325,19 @@ class EngineNet(DilatedNet):
         a, sigma, radius = C.c_double(), C.c_double(), C.c_int()
         _lib.call("drs_net_get_boundary_weight", self.h, C.byref(a), C.byref(sigma), C.byref(radius))
         return None if a.value == 0.0 else (float(a.value), float(sigma.value), int(radius.value))
+
+    def _dice_changed(self):
+        """hand the quadruple to the library's net (drs_net_set_dice: the step runs the Dice pre-pass before its fused classifier)"""
+        from .patches import DEFAULT_DICE
+        lam, alpha, beta, smooth = self._dice or DEFAULT_DICE
+        _lib.call("drs_net_set_dice", self.h, float(lam), float(alpha), float(beta), float(smooth))
+
+    @property
+    def dice(self):
+        """the quadruple (lam, alpha, beta, smooth) the library's net holds (drs_net_get_dice), or None when it is off (lam == 0)"""
+        v = [C.c_double() for _ in range(4)]
+        _lib.call("drs_net_get_dice", self.h, *[C.byref(x) for x in v])
+        return None if v[0].value == 0.0 else tuple(float(x.value) for x in v)
 
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always

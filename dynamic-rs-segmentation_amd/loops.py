@@ -144,13 +144,42 @@ def load_boundary_weight(net, former_model_path):
             print("Boundary weight (restored from " + path + "): " + _boundary_weight_str(net.boundary_weight))
 
 
+DICE_SIDE = "dice_step_"
+
+
+def _dice_str(d):
+    return "lambda " + "{:.6g}".format(d[0]) + " alpha " + "{:.6g}".format(d[1]) + " beta " + "{:.6g}".format(d[2]) + " smooth " + "{:.6g}".format(d[3])
+
+
+def save_dice(net, output_path, step):
+    """the soft Dice / Tversky term of the training loss, when on, as the side file `dice_step_<step>.npy` beside the size scores: four
+    float64 (lam, alpha, beta, smooth) (state of the run, not of the model, as the other options of the loss are)"""
+    d = getattr(net, "dice", None)
+    if d is not None:
+        np.save(output_path + DICE_SIDE + str(step) + ".npy", np.asarray(d, dtype=np.float64))
+
+
+def load_dice(net, former_model_path):
+    """set the quadruple that save_dice left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep or not hasattr(net, "set_dice"):
+        return
+    path = head + DICE_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        net.set_dice(tuple(np.load(path).tolist()))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Dice term (restored from " + path + "): " + _dice_str(net.dice))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
     """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights,
-    the focal gamma and the boundary weight of the loss when set (save_class_weights, save_focal_gamma, save_boundary_weight)."""
+    the focal gamma, the boundary weight and the Dice term of the loss when set (save_class_weights, save_focal_gamma,
+    save_boundary_weight, save_dice)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
     save_focal_gamma(net, output_path, step)
     save_boundary_weight(net, output_path, step)
+    save_dice(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -172,6 +201,7 @@ def load_checkpoint(net, former_model_path):
     load_class_weights(net, former_model_path)
     load_focal_gamma(net, former_model_path)
     load_boundary_weight(net, former_model_path)
+    load_dice(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -268,6 +298,23 @@ def setup_boundary_weight(net, boundary_weight, comm, say):
                                    if on else "a 0 (off: every pixel weighs one)") +
             ("" if restored is None or restored == bw else " -- replacing the triple restored from the checkpoint, " + _boundary_weight_str(restored)))
     return bw
+
+
+def setup_dice(net, dice, comm, say):
+    """The soft Dice / Tversky term of a training run (train's `dice`; patches.check_dice): every rank must hold the same quadruple
+    (lam, alpha, beta, smooth), asserted once over the ranks on the float64 bits.  Given, it replaces a quadruple restored from a
+    checkpoint's side file.  One log line names it; lam = 0 on a run that restored none is today's run and says nothing."""
+    d = P.check_dice(dice)
+    comm.agree([int(b) for b in np.asarray(d, dtype=np.float64).view(np.uint32)], "dice term")
+    restored = net.dice
+    net.set_dice(d)
+    on = d[0] != 0.0
+    if on or restored is not None:
+        say("Dice term: " + (_dice_str(d) + " (the loss is the cross-entropy part + lambda times the pixel-weighted mean over patches and "
+                                            "classes of 1 - Tversky index; class, focal and boundary weights do not weight it)"
+                             if on else "lambda 0 (off: the cross-entropy part alone)") +
+            ("" if restored is None or restored == d else " -- replacing the quadruple restored from the checkpoint, " + _dice_str(restored)))
+    return d
 
 
 def boundary_weight_map(labels, valid, a, sigma, R):
@@ -391,7 +438,7 @@ def train(training_data, training_labels, training_class_distribution, training_
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
           loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
-          scale_jitter=None, boundary_weight=None):
+          scale_jitter=None, boundary_weight=None, dice=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -409,6 +456,12 @@ def train(training_data, training_labels, training_class_distribution, training_
     scores with update_type="loss", is then the WEIGHTED one: its normaliser is unchanged, so it rises with the mean weight;
     accuracies, confusion matrices and validation are not weighted.  Given here, it replaces a triple restored from a checkpoint's
     side file; None keeps that.  Under data parallelism nothing is added: patches are independent and the normaliser is unchanged.
+    dice (opt-in; None or lam = 0 = today's run, bit for bit): (lam, alpha, beta, smooth), or fewer with the defaults of
+    patches.check_dice -- a soft Dice / Tversky term per patch is ADDED to the data term (setup_dice, DilatedNet.set_dice; DESIGN.md
+    3d), beside whatever form the cross-entropy has: class_weights, focal_gamma and boundary_weight do not weight it.  The loss this
+    loop prints, and that feeds the size scores with update_type="loss", is then the cross-entropy part + the Dice term; accuracies,
+    confusion matrices and validation do not change.  Given here, it replaces a quadruple restored from a checkpoint's side file; None
+    keeps that.  Under data parallelism nothing is added: the soft counts are per patch, and the normaliser is unchanged.
     scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
     log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
     their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
@@ -458,6 +511,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_focal_gamma(net, focal_gamma, comm, say)
     if boundary_weight is not None:
         setup_boundary_weight(net, boundary_weight, comm, say)
+    if dice is not None:
+        setup_dice(net, dice, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)

@@ -85,7 +85,7 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
           current_model, lr_initial, weight_decay, batch_size, niter, net_type, distribution_type, update_type, patch_acc_loss,
           patch_occur, patch_chosen_values, probs, values, *, num_classes, void_label=-1, side_names=None, device="cuda:0",
           comm=None, display_step=50, quiet_sizes=False, quantize_f16=False, flavour="isprs", class_weights=None,
-          focal_gamma=None, scale_jitter=None, boundary_weight=None):
+          focal_gamma=None, scale_jitter=None, boundary_weight=None, dice=None):
     """class_weights (opt-in; None = the reference's loss): "balanced" | "median" | K numbers, as loops.train takes them; the counts of
     the recipes leave the void label out.  The printed loss and the loss-based size scores are then the weighted ones.
     focal_gamma (opt-in; None or 0 = today's run): the focusing parameter of the focal loss, as loops.train takes it; the printed loss
@@ -93,6 +93,9 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
     boundary_weight (opt-in; None or a = 0 = today's run): (a, sigma, R), as loops.train takes it; the printed loss and the loss-based
     size scores are then the boundary-weighted ones.  Contest's void pixels are invalid for the weight map only where the step's
     validity mask says so; the loss mask keeps its meaning.
+    dice (opt-in; None or lam = 0 = today's run): (lam, alpha, beta, smooth), as loops.train takes it; the printed loss and the
+    loss-based size scores are then the cross-entropy part + the Dice term.  Contest's void pixels are outside the loss, so a patch
+    counts in the Dice term by its share of valid pixels.
     scale_jitter (opt-in; None = today's run): (lo, hi), as loops.train takes it -- every training patch resampled at a scale drawn
     log-uniformly from [lo, hi] by a generator of its own (patches.draw_scales), before the flip by index, coffee's float16 pass and
     contest's void mask; the test pass never jitters."""
@@ -132,6 +135,8 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
         loops.setup_focal_gamma(net, focal_gamma, comm, say)
     if boundary_weight is not None:
         loops.setup_boundary_weight(net, boundary_weight, comm, say)
+    if dice is not None:
+        loops.setup_dice(net, dice, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = loops.setup_scale_jitter(scale_jitter, seeds, comm, say)
@@ -142,6 +147,7 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
             loops.save_class_weights(net, output_path, step)
             loops.save_focal_gamma(net, output_path, step)
             loops.save_boundary_weight(net, output_path, step)
+            loops.save_dice(net, output_path, step)
             if sized:
                 np.save(output_path + side[0] + str(step) + ".npy", patch_acc_loss)
                 np.save(output_path + side[1] + str(step) + ".npy", patch_occur)

@@ -154,6 +154,7 @@ class DilatedNet(object):
         self._class_weights = None
         self._focal_gamma = 0.0
         self._boundary_weight = None
+        self._dice = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -283,6 +284,30 @@ class DilatedNet(object):
         """the triple (a, sigma, R) in use, or None when it is off (never set, or a == 0)"""
         bw = self._boundary_weight
         return None if bw is None or bw[0] == 0.0 else bw
+
+    # ------------------------------------------------------------------ soft Dice / Tversky term of the training loss
+    def set_dice(self, dice):
+        """Soft Dice / Tversky term of the training loss (opt-in): dice = (lam, alpha, beta, smooth) as
+        patches.check_dice takes it, or None / lam == 0 (the step as it is, bit for bit, no new launch).  train_step then adds
+        L_dice = inv_n * sum over patches b of n_b (lam / K) sum_c (1 - T_bc), T = (TP + eps) / (TP + alpha FP + beta FN + eps) with the
+        soft counts taken over the in-loss pixels of patch b alone (n_b of them), to its data term, and the matching term to the logit
+        gradients; alpha = beta = 0.5 is the Dice score.  The sums are per patch, so a sharded batch trains as the whole one does and
+        no collective is added.  Class weights, the focal factor and the boundary weight do not weight this term.  The loss train_step
+        reports is the cross-entropy part + L_dice; logits, pred, the confusion matrix, the L2 term and every forward pass do not
+        change.  State of the training run, not of the model: loops.save_checkpoint keeps it in a side file, and an inference twin does
+        not copy it."""
+        from .patches import check_dice
+        self._dice = None if dice is None else check_dice(dice)
+        self._dice_changed()
+
+    def _dice_changed(self):
+        pass
+
+    @property
+    def dice(self):
+        """the quadruple (lam, alpha, beta, smooth) in use, or None when the term is off (never set, or lam == 0)"""
+        d = self._dice
+        return None if d is None or d[0] == 0.0 else d
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

@@ -415,6 +415,46 @@ def parse_boundary_weight(text):
     return check_boundary_weight(tuple(vals))
 
 
+# ------------------------------------------------------------------- soft Dice / Tversky term of the training loss
+MAX_DICE_LAMBDA, MAX_DICE_SMOOTH = 64.0, float(1 << 20)     # the ranges drs_net_set_dice takes (include/drs.h)
+DEFAULT_DICE = (0.0, 0.5, 0.5, 1.0)                         # off; alpha = beta = 0.5 is the Dice score, smooth = 1
+
+
+def check_dice(dice):
+    """The soft Dice / Tversky term of the training loss as the library takes it: (lam, alpha, beta, smooth) -- or
+    (lam,), (lam, alpha, beta), or a bare number lam -- with lam finite in [0, 64] (0: off), alpha and beta in [0, 1] (default 0.5
+    each: Dice; they come as a pair) and smooth finite in (0, 2^20] (default 1).  Returns the quadruple of floats.  Anything else:
+    ValueError."""
+    t = tuple(dice) if isinstance(dice, (tuple, list)) else (dice,)
+    what = "dice weight %r: expected lam[, alpha, beta[, smooth]] with lam in [0, %g], alpha and beta in [0, 1], smooth in (0, %g]" % (
+        dice, MAX_DICE_LAMBDA, MAX_DICE_SMOOTH)
+    if len(t) not in (1, 3, 4) or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in t):
+        raise ValueError(what)
+    v = [float(x) for x in t] + list(DEFAULT_DICE[1:3] if len(t) == 1 else ()) + list(DEFAULT_DICE[3:] if len(t) < 4 else ())
+    lam, alpha, beta, smooth = v
+    if not math.isfinite(lam) or lam < 0.0 or lam > MAX_DICE_LAMBDA or not 0.0 <= alpha <= 1.0 or not 0.0 <= beta <= 1.0:
+        raise ValueError(what)
+    if not math.isfinite(smooth) or not 0.0 < smooth <= MAX_DICE_SMOOTH:
+        raise ValueError(what)
+    return lam, alpha, beta, smooth
+
+
+def parse_dice(text):
+    """The value of the command lines' --dice-weight option: `lam`, `lam,alpha,beta` or `lam,alpha,beta,smooth` as check_dice takes
+    them.  Anything else raises ValueError."""
+    vals = None
+    if text and text == text.strip():
+        parts = text.split(",")
+        try:
+            if len(parts) in (1, 3, 4) and all(q and q == q.strip() for q in parts):
+                vals = [float(q) for q in parts]
+        except ValueError:
+            vals = None
+    if vals is None:
+        raise ValueError("dice weight %r: expected lam[,alpha,beta[,smooth]] (numbers)" % (text,))
+    return check_dice(tuple(vals))
+
+
 # ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
 SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores (DESIGN.md 8a.4)
 

@@ -728,6 +728,17 @@ int drs_net_get_focal_gamma(const drs_net_t* net, float* gamma);
  * drs_net_get_boundary_weight: the triple in use (any pointer may be NULL); (0, 4, 12) when never set. */
 int drs_net_set_boundary_weight(drs_net_t* net, double a, double sigma, int R);
 int drs_net_get_boundary_weight(const drs_net_t* net, double* a, double* sigma, int* R);
+/* soft Dice / Tversky term of drs_train_step's loss (opt-in; the section "Training level: soft Dice / Tversky term" below states the
+ * rule): lam in [0, 64], lam == 0 (the default) switches it off -- no new launch, the step is the launches it was, bit for bit; alpha,
+ * beta in [0, 1]; smooth finite in (0, 2^20]; anything else DRS_ERR_ARG, also with lam == 0.  With lam != 0 the step, before its fused
+ * classifier launch, runs the classifier in its inference form into the bound buffer "logits", drs_patch_dice_coeffs(logits, labels,
+ * loss_mask if and only if DRS_USE_LOSS_MASK, ...) into the bound buffers "dice_coef" and "dice_loss", and the classifier as
+ * drs_classifier_loss_dice; all of it is accounted under the timing kind "classifier_loss".  The sum of "dice_loss" is added into
+ * "scalars"[0] before its all-reduce (count 1, as before) and its scaling by 1 / global pixels: "scalars"[0] is then the cross-entropy
+ * part (whatever form is active) + L_dice.  No collective, event or stream is added.  drs_forward and drs_forward_staged have no loss
+ * and ignore it.  drs_net_get_dice: the quadruple in use (any pointer may be NULL); (0, 0.5, 0.5, 1) when never set. */
+int drs_net_set_dice(drs_net_t* net, double lam, double alpha, double beta, double smooth);
+int drs_net_get_dice(const drs_net_t* net, double* lam, double* alpha, double* beta, double* smooth);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
@@ -851,6 +862,49 @@ int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, in
                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
                               const float* pixel_weight, float* logits, unsigned char* pred, float* gfeat, int ld_g, int coff_g,
                               float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf, void* stream);
+
+/* ==================================================================================================================
+ * Training level: soft Dice / Tversky term (opt-in; csrc/dice.hip, csrc/pointwise.hip).  A region-overlap term beside
+ * the pixel-wise cross-entropy (Milletari et al., V-Net, 2016; Salehi et al., Tversky loss, 2017), per PATCH, so that the loss stays a
+ * sum over patches: a sharded batch gives the single-rank loss and gradient with no collective.  NORMATIVE: this text and the numpy
+ * statement tests/dice_ref.py.
+ * Options: lam finite in (0, 64]; alpha, beta in [0, 1] (0.5, 0.5: Dice); smooth = eps finite in (0, 2^20].
+ * "In the loss" means what it means for the cross-entropy: loss_mask set where one is given, and label < K.
+ * For patch b and class c, every sum over the in-loss pixels of that patch only, p = softmax(logits):
+ *     TP = sum p_c [y = c]      SP = sum p_c      N = sum [y = c]      n_b = sum_c N
+ *     D  = TP + alpha (SP - TP) + beta (N - TP) + eps          T = (TP + eps) / D
+ *     L_dice = inv_n sum_b n_b (lam / K) sum_c (1 - T)          (inv_n: the step's 1 / global pixels in the loss)
+ *     With no mask that is lam times the mean over patches and classes of 1 - T; a patch counts by its share of the pixels in the
+ *     loss, and a patch with n_b = 0 contributes nothing (T = 1, coefficients 0).
+ * Gradient, for an in-loss pixel of patch b with softmax P and label y:
+ *     G_in[b][c]  = -(lam n_b / K) (D - (TP + eps)(1 - beta)) / D^2        G_out[b][c] = +(lam n_b / K) alpha (TP + eps) / D^2
+ *     g_c = [y = c] ? G_in[b][c] : G_out[b][c]        dL_dice / dlogit_k = inv_n P_k (g_k - sum_c P_c g_c)
+ *     It is ADDED to the logit gradient of whatever cross-entropy form is active.  Class weights, the focal factor and the pixel map
+ *     do NOT weight the Dice term.  Logits, arg-max and the confusion matrix are untouched.
+ *
+ * drs_patch_dice_coeffs: logits = float [B S S][K] (what the classifier's inference form writes), labels = uint8 [B S S], loss_mask =
+ *     uint8 [B S S] or NULL.  Out: stats_out = double [B][K][3] (TP, SP, N), may be NULL: it exists so that a wrong sum and a wrong
+ *     coefficient can be told apart; coef_out = float [B][K][2] (G_in, G_out), evaluated in fp64 and rounded once; patch_loss_out =
+ *     double [B], n_b (lam / K) sum_c (1 - T).  The softmax is fp32 in max-subtracted form, every sum fp64 in a fixed order: no
+ *     floating-point atomics, the same bits on every run.  One launch, one workgroup per patch, no scratch.
+ *     Ranges, else DRS_ERR_ARG (nothing is launched): logits, labels, coef_out, patch_loss_out not NULL; B, S >= 1, B S S < 2^24; K in
+ *     1..8; lam finite in (0, 64]; alpha, beta in [0, 1]; smooth finite in (0, 2^20].
+ * drs_classifier_loss_dice: the arguments of drs_classifier_loss_pixel plus dice_coef, DEVICE float [B][K][2] (8-byte aligned, else
+ *     DRS_ERR_ARG) or NULL.  With NULL, or with labels == NULL, it IS drs_classifier_loss_pixel: the same launches, every output bit
+ *     for bit.  Otherwise all three kernel forms add the term above to the pixel's logit gradients before gfeat, dw_partial and
+ *     db_partial are formed; loss_partial stays the cross-entropy sum.  The coefficients are device data and are not checked.
+ * drs_dice_loss_add: loss_sum[0] += the sum of patch_loss[0 .. B) (fp64, fixed order) -- how the step joins the patches' terms to the
+ *     cross-entropy sum.  patch_loss, loss_sum not NULL, B >= 1, else DRS_ERR_ARG. */
+int drs_patch_dice_coeffs(const float* logits, const unsigned char* labels, const unsigned char* loss_mask, int B, int S, int K,
+                          double lam, double alpha, double beta, double smooth, double* stats_out, float* coef_out,
+                          double* patch_loss_out, void* stream);
+int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                             const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                             const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                             const float* pixel_weight, const float* dice_coef, float* logits, unsigned char* pred, float* gfeat,
+                             int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
+                             void* stream);
+int drs_dice_loss_add(const double* patch_loss, int B, double* loss_sum, void* stream);
 
 #ifdef __cplusplus
 }
