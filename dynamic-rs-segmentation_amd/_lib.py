@@ -103,6 +103,8 @@ SIGNATURES = {
     "drs_classifier_loss_dice": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _p, _p, _i, _i, _p,
                                       _p, _p, _p, _p]),
     "drs_dice_loss_add": (_i, [_p, _i, _p, _p]),
+    # ---- training level: hard example mining (csrc/hard_mining.hip)
+    "drs_patch_hard_weight": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _i, _p, _p, _p, _p]),
     # ---- step level (csrc/engine.hip)
     "drs_net_create": (_i, [C.c_char_p, _i, _i, _f, _i, _i, _i, _f, C.POINTER(_p)]),
     "drs_net_destroy": (None, [_p]),
@@ -147,6 +149,8 @@ SIGNATURES = {
     "drs_net_get_boundary_weight": (_i, [_p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_i)]),
     "drs_net_set_dice": (_i, [_p, _d, _d, _d, _d]),
     "drs_net_get_dice": (_i, [_p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
+    "drs_net_set_hard_mining": (_i, [_p, _d, _i]),
+    "drs_net_get_hard_mining": (_i, [_p, C.POINTER(_d), C.POINTER(_i)]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),
     "drs_net_timing_summary": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),

@@ -50,6 +50,10 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     --focal-gamma and --boundary-weight, which do not weight it): lam times a soft Dice / Tversky term per patch is added to the loss;
     lam in [0, 64] (0: off), alpha and beta in [0, 1] (default 0.5,0.5: Dice), smooth in (0, 2^20] (default 1) (loops.train's dice;
     DESIGN.md 3d)
+  + optionally, anywhere, in all three flavours, `--hard-mining=keep[,min_keep]` (training; beside --class-weights, --focal-gamma,
+    --boundary-weight, which shape the terms it selects among, and --dice-weight, which it does not touch): online hard example
+    mining -- the cross-entropy runs over the max(ceil(keep n), min_keep) of a patch's n in-loss pixels with the largest plain
+    cross-entropy; keep in (0, 1] (1: off), min_keep an integer in [0, 2^24) (default 0) (loops.train's hard_mining)
   + optionally, anywhere, in all three flavours, `--scale-jitter=lo,hi` (training): every training patch is resampled at a scale
     drawn log-uniformly from [lo, hi], 0.25 <= lo <= hi <= 4 (loops.train's scale_jitter); validation and inference
     stay at scale 1
@@ -324,6 +328,18 @@ def parse_dice(argv):
             DICE_FLAG, P.MAX_DICE_LAMBDA, P.MAX_DICE_SMOOTH)))
 
 
+HARD_MINING_FLAG = "--hard-mining"
+
+
+def parse_hard_mining(argv):
+    """all flavours: the optional `--hard-mining=keep[,min_keep]` (anywhere in argv; training).  Returns (argv without the flag, (keep,
+    min_keep) with the default filled in), or (argv unchanged, None) without it.  A bare flag, a value outside the ranges of
+    patches.check_hard_mining, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, HARD_MINING_FLAG, lambda a, v: _or_expected(
+        P.parse_hard_mining, a, v, "%s=keep[,min_keep] (keep in (0, 1], min_keep an integer in [0, %d])" % (
+            HARD_MINING_FLAG, P.MAX_HARD_MIN_KEEP)))
+
+
 SCALE_JITTER_FLAG = "--scale-jitter"
 
 
@@ -404,6 +420,7 @@ def main(argv=None, device=None, comm=None):
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
         argv, dice = parse_dice(argv)
+        argv, hard_mining = parse_hard_mining(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -445,6 +462,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the training process only")
     if dice is not None and argv[16] != "training":
         sys.exit(DICE_FLAG + " applies to the training process only")
+    if hard_mining is not None and argv[16] != "training":
+        sys.exit(HARD_MINING_FLAG + " applies to the training process only")
     if scale_jitter is not None and argv[16] != "training":
         sys.exit(SCALE_JITTER_FLAG + " applies to the training process only")
     if comm.rank == 0:
@@ -497,7 +516,7 @@ def main(argv=None, device=None, comm=None):
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
                            class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter,
-                           boundary_weight=boundary_weight, dice=dice)
+                           boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -572,6 +591,7 @@ def main_coffee(argv=None, device=None, comm=None):
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
         argv, dice = parse_dice(argv)
+        argv, hard_mining = parse_hard_mining(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -591,7 +611,7 @@ def main_coffee(argv=None, device=None, comm=None):
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
                     quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma,     # coffee:293: training patches pass through float16
-                    scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice)
+                    scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining)
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -604,6 +624,7 @@ def main_contest(argv=None, device=None, comm=None):
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
         argv, dice = parse_dice(argv)
+        argv, hard_mining = parse_hard_mining(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -618,6 +639,8 @@ def main_contest(argv=None, device=None, comm=None):
         sys.exit(BOUNDARY_WEIGHT_FLAG + " applies to the train operation only")
     if dice is not None and operation != "train":
         sys.exit(DICE_FLAG + " applies to the train operation only")
+    if hard_mining is not None and operation != "train":
+        sys.exit(HARD_MINING_FLAG + " applies to the train operation only")
     if scale_jitter is not None and operation != "train":
         sys.exit(SCALE_JITTER_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
@@ -637,7 +660,7 @@ def main_contest(argv=None, device=None, comm=None):
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
                         void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
-                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice)
+                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

@@ -142,7 +142,7 @@ struct LayerPtrs {
 struct Ptrs {
   bool ok = false;
   float *params, *grads, *momentum, *bn, *partial, *gxh, *gz[2], *slab, *w0pad, *conv_ws, *bwd_means, *act, *gpool, *se_scratch;
-  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef;
+  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef, *hard_ce;
   size_t conv_ws_floats;
   double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch, *dice_loss;
   unsigned char *pred, *labels, *acc_mask, *loss_mask;
@@ -195,6 +195,8 @@ struct drs_net {
   double bw_a = 0.0, bw_sigma = 4.0;         // boundary weight of the training loss (drs_net_set_boundary_weight); a == 0: off, no launch
   int bw_R = 12;
   double dice_lam = 0.0, dice_alpha = 0.5, dice_beta = 0.5, dice_smooth = 1.0;      // soft Dice / Tversky term of the training loss (drs_net_set_dice); lam == 0: off, no launch
+  double hard_keep = 1.0;                   // hard example mining in the training loss (drs_net_set_hard_mining); keep == 1: off, no launch
+  int hard_min_keep = 0;
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -428,6 +430,7 @@ void list_buffers(drs_net* n) {
   n->add_buf("l2_scratch", 256, F64);
   n->add_buf("dice_coef", B * n->K * 2, F32);      // (G_in, G_out) per patch and class, and the patches' loss terms (drs_net_set_dice); untouched while it is off
   n->add_buf("dice_loss", B, F64);
+  n->add_buf("hard_ce", M, F32);             // the keys of hard example mining: a step's plain cross-entropy per pixel (drs_net_set_hard_mining); untouched while it is off
   n->add_buf("logits", M * n->K, F32);
   n->add_buf("pred", M, U8);
   n->add_buf("conf", (size_t)n->K * n->K, I32);
@@ -582,6 +585,7 @@ bool resolve(drs_net* n) {
   P.loss_mask = n->p<unsigned char>("loss_mask"); P.conf = n->p<unsigned int>("conf");
   P.pixel_weight = n->p<float>("pixel_weight");
   P.dice_coef = n->p<float>("dice_coef"); P.dice_loss = n->p<double>("dice_loss");
+  P.hard_ce = n->p<float>("hard_ce");
   const Slab& f = n->slabs[n->feat];
   P.feat_act = n->p<float>("act:" + f.name); P.feat_gact = n->p<float>("gact:" + f.name);
   P.L.assign(n->layers.size(), LayerPtrs());
@@ -1133,6 +1137,22 @@ int drs_net_get_dice(const drs_net_t* n, double* lam, double* alpha, double* bet
   return DRS_OK;
 }
 
+// Hard example mining in the training loss (drs_train_step only; include/drs.h, "Training level: hard example mining"): keep == 1
+// switches it off.  The step then runs the classifier in its inference form into "logits" (once, shared with the Dice pre-pass),
+// drs_patch_hard_weight over them into "pixel_weight", and the fused classifier with that map.
+int drs_net_set_hard_mining(drs_net_t* n, double keep, int min_keep) {
+  if (!n || !std::isfinite(keep) || !(keep > 0.0) || keep > 1.0 || min_keep < 0 || min_keep >= (1 << 24)) return DRS_ERR_ARG;
+  n->hard_keep = keep; n->hard_min_keep = min_keep;
+  return DRS_OK;
+}
+
+int drs_net_get_hard_mining(const drs_net_t* n, double* keep, int* min_keep) {
+  if (!n) return DRS_ERR_ARG;
+  if (keep) *keep = n->hard_keep;
+  if (min_keep) *min_keep = n->hard_min_keep;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1342,26 +1362,31 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   double* scalars = P.scalars;
   double* scratch = P.colsum_scratch;
   const bool dice = n->dice_lam != 0.0;
+  const bool hard = n->hard_keep != 1.0;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
     const bool bw = n->bw_a != 0.0;          // off: no launch, and drs_classifier_loss_pixel without a map is drs_classifier_loss_focal
     if (bw)
       DRS_TRY(drs_patch_boundary_weight(P.labels, (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, B, S, n->bw_R, n->bw_a,
                                         1.0 / (2.0 * n->bw_sigma * n->bw_sigma), nullptr, P.pixel_weight, st));
-    // the Dice term needs sums over whole patches before any gradient: the classifier once in its inference form (logits only), the
-    // coefficients of every (patch, class), then the fused launch with them.  Off: none of it, and drs_classifier_loss_dice without
-    // coefficients is drs_classifier_loss_pixel
-    if (dice) {
+    // the Dice term needs sums over whole patches before any gradient, hard example mining the rank of every pixel in its patch: the
+    // classifier once in its inference form (logits only) for both, the coefficients of every (patch, class) and / or the weight map
+    // that keeps the hardest pixels (times the boundary weight, in place), then the fused launch with them.  Off: none of it, and
+    // drs_classifier_loss_dice without coefficients is drs_classifier_loss_pixel
+    if (dice || hard)
       DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b, nullptr, nullptr,
                                         nullptr, 1.f, nullptr, 0.f, nullptr, P.logits, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
                                         nullptr, st));
+    if (dice)
       DRS_TRY(drs_patch_dice_coeffs(P.logits, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K, n->dice_lam,
                                     n->dice_alpha, n->dice_beta, n->dice_smooth, nullptr, P.dice_coef, P.dice_loss, st));
-    }
+    if (hard)
+      DRS_TRY(drs_patch_hard_weight(P.logits, P.hard_ce, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K,
+                                    n->hard_keep, n->hard_min_keep, bw ? P.pixel_weight : nullptr, P.pixel_weight, nullptr, st));
     DRS_TRY(drs_classifier_loss_dice(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
                                      P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
                                      (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                     n->has_wc ? n->wc : nullptr, n->focal_gamma, bw ? P.pixel_weight : nullptr,
+                                     n->has_wc ? n->wc : nullptr, n->focal_gamma, (bw || hard) ? P.pixel_weight : nullptr,
                                      dice ? P.dice_coef : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
                                      P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
   }

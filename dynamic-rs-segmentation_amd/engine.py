@@ -106,7 +106,7 @@ class EngineNet(DilatedNet):
         self.idx = [b.get("idx%d" % i) for i in range(nl)]
         self.mean_rstd = [b["mean_rstd%d" % i] for i in range(nl)]
         for n in ("sums", "partial", "gxh", "gz", "slab", "w0pad", "dw_partial", "db_partial", "loss_partial", "scalars", "logits", "pred", "conf",
-                  "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss"):
+                  "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss", "hard_ce"):
             setattr(self, n, b[n])
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
@@ -338,6 +338,19 @@ class EngineNet(DilatedNet):
         v = [C.c_double() for _ in range(4)]
         _lib.call("drs_net_get_dice", self.h, *[C.byref(x) for x in v])
         return None if v[0].value == 0.0 else tuple(float(x.value) for x in v)
+
+    def _hard_mining_changed(self):
+        """hand the pair to the library's net (drs_net_set_hard_mining: the step runs the mining pre-pass before its fused classifier)"""
+        from .patches import DEFAULT_HARD_MINING
+        keep, min_keep = self._hard_mining or DEFAULT_HARD_MINING
+        _lib.call("drs_net_set_hard_mining", self.h, float(keep), int(min_keep))
+
+    @property
+    def hard_mining(self):
+        """the pair (keep, min_keep) the library's net holds (drs_net_get_hard_mining), or None when it is off (keep == 1)"""
+        keep, min_keep = C.c_double(), C.c_int()
+        _lib.call("drs_net_get_hard_mining", self.h, C.byref(keep), C.byref(min_keep))
+        return None if keep.value == 1.0 else (float(keep.value), int(min_keep.value))
 
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always

@@ -171,15 +171,44 @@ def load_dice(net, former_model_path):
             print("Dice term (restored from " + path + "): " + _dice_str(net.dice))
 
 
+HARD_MINING_SIDE = "hard_mining_step_"
+
+
+def _hard_mining_str(h):
+    return "keep " + "{:.6g}".format(h[0]) + " min_keep " + str(int(h[1]))
+
+
+def save_hard_mining(net, output_path, step):
+    """hard example mining in the training loss, when on, as the side file `hard_mining_step_<step>.npy` beside the size scores: two
+    float64 (keep, min_keep) (state of the run, not of the model, as the other options of the loss are)"""
+    h = getattr(net, "hard_mining", None)
+    if h is not None:
+        np.save(output_path + HARD_MINING_SIDE + str(step) + ".npy", np.asarray(h, dtype=np.float64))
+
+
+def load_hard_mining(net, former_model_path):
+    """set the pair that save_hard_mining left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep or not hasattr(net, "set_hard_mining"):
+        return
+    path = head + HARD_MINING_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        keep, min_keep = np.load(path).tolist()
+        net.set_hard_mining((keep, int(min_keep)))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Hard mining (restored from " + path + "): " + _hard_mining_str(net.hard_mining))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
     """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights,
-    the focal gamma, the boundary weight and the Dice term of the loss when set (save_class_weights, save_focal_gamma,
-    save_boundary_weight, save_dice)."""
+    the focal gamma, the boundary weight, the Dice term and the hard mining of the loss when set (save_class_weights,
+    save_focal_gamma, save_boundary_weight, save_dice, save_hard_mining)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
     save_focal_gamma(net, output_path, step)
     save_boundary_weight(net, output_path, step)
     save_dice(net, output_path, step)
+    save_hard_mining(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -202,6 +231,7 @@ def load_checkpoint(net, former_model_path):
     load_focal_gamma(net, former_model_path)
     load_boundary_weight(net, former_model_path)
     load_dice(net, former_model_path)
+    load_hard_mining(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -315,6 +345,57 @@ def setup_dice(net, dice, comm, say):
                              if on else "lambda 0 (off: the cross-entropy part alone)") +
             ("" if restored is None or restored == d else " -- replacing the quadruple restored from the checkpoint, " + _dice_str(restored)))
     return d
+
+
+def setup_hard_mining(net, hard_mining, comm, say):
+    """Hard example mining of a training run (train's `hard_mining`; patches.check_hard_mining): every rank must hold the same pair
+    (keep, min_keep), asserted once over the ranks on the float64 bits of keep and on min_keep.  Given, it replaces a pair restored
+    from a checkpoint's side file.  One log line names it; keep = 1 on a run that restored none is today's run and says nothing."""
+    h = P.check_hard_mining(hard_mining)
+    comm.agree([int(b) for b in np.asarray([h[0]], dtype=np.float64).view(np.uint32)] + [h[1]], "hard mining")
+    restored = net.hard_mining
+    net.set_hard_mining(h)
+    on = h[0] != 1.0
+    if on or restored is not None:
+        say("Hard mining: " + (_hard_mining_str(h) + " (the cross-entropy part of the loss runs over the max(ceil(keep n), min_keep) of a patch's n "
+                                                    "in-loss pixels with the largest plain cross-entropy, each at the weight n / kept; the printed loss is the mined one)"
+                               if on else "keep 1 (off: every pixel in the loss)") +
+            ("" if restored is None or restored == h else " -- replacing the pair restored from the checkpoint, " + _hard_mining_str(restored)))
+    return h
+
+
+def hard_mining_weights(logits, labels, keep, min_keep, loss_mask=None, pixel_weight=None):
+    """The weight map drs_train_step makes of a step's logits when hard example mining is on, for inspection: logits
+    float32 [B, S, S, K] and labels uint8 [B, S, S] (tensors on the GPU, or anything np.asarray takes -- then on the current device),
+    loss_mask uint8 [B, S, S] or None, pixel_weight float32 [B, S, S] (the incoming map, e.g. boundary_weight_map's) or None.
+    Returns (weights float32 [B, S, S]: 0 where a pixel is left out, n_b / k_b times the incoming weight where it is kept; ce float32
+    [B, S, S]: the keys, the plain cross-entropy at in-loss pixels and 0 elsewhere; kept int32 [B]: k_b) as tensors on that device.
+    One launch of drs_patch_hard_weight."""
+    import torch
+    from . import _lib
+
+    def dev(x, dtype):
+        if x is None:
+            return None
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x))).cuda()
+        return x.to(dtype).contiguous()
+    lg, lab = dev(logits, torch.float32), dev(labels, torch.uint8)
+    if lg.dim() != 4 or lab.dim() != 3 or lg.shape[:3] != lab.shape or lab.shape[1] != lab.shape[2]:
+        raise ValueError("hard_mining_weights: logits [B, S, S, K] and labels [B, S, S] expected, got %r and %r" % (tuple(lg.shape), tuple(lab.shape)))
+    B, S, K = int(lab.shape[0]), int(lab.shape[1]), int(lg.shape[3])
+    keep, min_keep = P.check_hard_mining((keep, min_keep))
+    lm, pw = dev(loss_mask, torch.uint8), dev(pixel_weight, torch.float32)
+    for name, x in (("loss_mask", lm), ("pixel_weight", pw)):
+        if x is not None and x.shape != lab.shape:
+            raise ValueError("hard_mining_weights: %s must have the shape of labels" % name)
+    w = torch.empty(lab.shape, dtype=torch.float32, device=lab.device)
+    ce = torch.empty(lab.shape, dtype=torch.float32, device=lab.device)
+    kept = torch.empty(B, dtype=torch.int32, device=lab.device)
+    with torch.cuda.device(lab.device):
+        _lib.call("drs_patch_hard_weight", lg.data_ptr(), ce.data_ptr(), lab.data_ptr(), None if lm is None else lm.data_ptr(), B, S, K,
+                  keep, min_keep, None if pw is None else pw.data_ptr(), w.data_ptr(), kept.data_ptr(),
+                  torch.cuda.current_stream().cuda_stream)
+    return w, ce, kept
 
 
 def boundary_weight_map(labels, valid, a, sigma, R):
@@ -438,7 +519,7 @@ def train(training_data, training_labels, training_class_distribution, training_
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
           loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
-          scale_jitter=None, boundary_weight=None, dice=None):
+          scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -462,6 +543,14 @@ def train(training_data, training_labels, training_class_distribution, training_
     loop prints, and that feeds the size scores with update_type="loss", is then the cross-entropy part + the Dice term; accuracies,
     confusion matrices and validation do not change.  Given here, it replaces a quadruple restored from a checkpoint's side file; None
     keeps that.  Under data parallelism nothing is added: the soft counts are per patch, and the normaliser is unchanged.
+    hard_mining (opt-in; None or keep = 1 = today's run, bit for bit): (keep, min_keep), or keep alone with min_keep = 0 -- online
+    hard example mining / bootstrapped cross-entropy (setup_hard_mining, DilatedNet.set_hard_mining): the cross-entropy
+    part, in whatever form class_weights, focal_gamma and boundary_weight give it, runs over the max(ceil(keep n_b), min_keep)
+    in-loss pixels of every patch with the largest plain cross-entropy at that step, each at the weight n_b / kept; the Dice term is
+    not mined.  The loss this loop prints, and that feeds the size scores with update_type="loss", is then the MINED one: the mean of
+    the hardest pixels' terms, so it is larger than the loss over all pixels; accuracies, confusion matrices and validation do not
+    change.  Given here, it replaces a pair restored from a checkpoint's side file; None keeps that.  Under data parallelism nothing
+    is added: the selection is per patch, and the normaliser is unchanged.
     scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
     log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
     their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
@@ -513,6 +602,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_boundary_weight(net, boundary_weight, comm, say)
     if dice is not None:
         setup_dice(net, dice, comm, say)
+    if hard_mining is not None:
+        setup_hard_mining(net, hard_mining, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)
@@ -1192,7 +1283,13 @@ def _boundary_str(b):
 
 def _on_stream(dev, stream):
     """context in which torch's own operations run on the raw stream handle `stream` (None: torch's current stream on dev, as it is)"""
-    return contextlib.nullcontext() if stream is None else torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev))
+    # the handle of torch's current stream needs no context -- and must not get one when it is 0, the default stream: an ExternalStream
+    # made of a zero handle is a stream from torch's pool instead, unordered with the launches that wrote the caller's maps on stream 0
+    if stream is None or stream == torch.cuda.current_stream(dev).cuda_stream:
+        return contextlib.nullcontext()
+    if stream == 0:
+        return torch.cuda.stream(torch.cuda.default_stream(dev))
+    return torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev))
 
 
 def components(map_dev, h, w, connectivity, stream=None):

@@ -155,6 +155,7 @@ class DilatedNet(object):
         self._focal_gamma = 0.0
         self._boundary_weight = None
         self._dice = None
+        self._hard_mining = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -308,6 +309,30 @@ class DilatedNet(object):
         """the quadruple (lam, alpha, beta, smooth) in use, or None when the term is off (never set, or lam == 0)"""
         d = self._dice
         return None if d is None or d[0] == 0.0 else d
+
+    # ------------------------------------------------------------------ hard example mining in the training loss
+    def set_hard_mining(self, hard_mining):
+        """Online hard example mining / bootstrapped cross-entropy in the training loss (opt-in): hard_mining = (keep,
+        min_keep) as patches.check_hard_mining takes it, or None / keep == 1 (the step as it is, bit for bit, no new launch).
+        train_step then takes its cross-entropy -- whatever form is active: plain, class-weighted, focal, boundary-weighted -- over the
+        k_b = min(n_b, max(ceil(keep n_b), min_keep)) in-loss pixels of every patch b with the largest PLAIN cross-entropy at that step
+        (ties towards the lower pixel index), each at the weight n_b / k_b: the data term is inv_n sum_b (n_b / k_b) sum_{kept} term,
+        inv_n the unchanged 1 / global in-loss pixels.  The selection is per patch, so a sharded batch trains as the whole one does and
+        no collective is added; it is a constant in the gradient.  The Dice term, when on, is not mined.  The loss train_step reports is
+        the MINED one; logits, pred, the confusion matrix, the L2 term and every forward pass do not change.  State of the training
+        run, not of the model: loops.save_checkpoint keeps it in a side file, and an inference twin does not copy it."""
+        from .patches import check_hard_mining
+        self._hard_mining = None if hard_mining is None else check_hard_mining(hard_mining)
+        self._hard_mining_changed()
+
+    def _hard_mining_changed(self):
+        pass
+
+    @property
+    def hard_mining(self):
+        """the pair (keep, min_keep) in use, or None when mining is off (never set, or keep == 1)"""
+        h = self._hard_mining
+        return None if h is None or h[0] == 1.0 else h
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

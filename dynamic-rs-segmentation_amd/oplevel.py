@@ -105,6 +105,7 @@ class OpLevelNet(DilatedNet):
         self.pixel_weight = torch.zeros(M, **f32)      # boundary weight map of the step's labels (set_boundary_weight); untouched while it is off
         self.dice_coef = torch.zeros(B * p.K * 2, **f32)      # (G_in, G_out) per patch and class, and the patches' Dice terms (set_dice); untouched while it is off
         self.dice_loss = torch.zeros(B, **f64)
+        self.hard_ce = torch.zeros(M, **f32)           # the keys of hard example mining (set_hard_mining); untouched while it is off
 
     def workspace_bytes(self):
         tot = 0
@@ -347,18 +348,25 @@ class OpLevelNet(DilatedNet):
             _lib.call("drs_patch_boundary_weight", _ptr(self.labels), _ptr(self.acc_mask) if use_acc_mask else None, B, S, r_bw, a_bw,
                       1.0 / (2.0 * sigma_bw * sigma_bw), None, _ptr(self.pixel_weight), st)
         dice = self.dice                  # (lam, alpha, beta, smooth) or None: off, no launch, and the Dice form without coefficients is the pixel one
-        if dice is not None:
-            # the classifier once in its inference form (logits only), then the coefficients of every (patch, class) from them: timed
-            # under the kind the engine accounts them under (its bracket's work figure stays with the fused launch)
+        hard = self.hard_mining           # (keep, min_keep) or None: off, no launch
+        if dice is not None or hard is not None:
+            # the classifier once in its inference form (logits only) for both pre-passes, then the coefficients of every (patch, class)
+            # and / or the weight map of the hardest pixels from them: timed under the kind the engine accounts them under (its
+            # bracket's work figure stays with the fused launch)
             self._k("classifier_loss", 0.0, "drs_classifier_loss_pixel", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K, self.params[woff:].data_ptr(),
                       self.params[boff:].data_ptr(), None, None, None, 1.0, None, 0.0, None, _ptr(self.logits), None, None, 0, 0, None, None,
                       None, None, st)
+        if dice is not None:
             self._k("classifier_loss", 0.0, "drs_patch_dice_coeffs", _ptr(self.logits), _ptr(self.labels), _ptr(self.loss_mask) if use_loss_mask else None, B, S,
                       p.K, dice[0], dice[1], dice[2], dice[3], None, _ptr(self.dice_coef), _ptr(self.dice_loss), st)
+        if hard is not None:
+            self._k("classifier_loss", 0.0, "drs_patch_hard_weight", _ptr(self.logits), _ptr(self.hard_ce), _ptr(self.labels),
+                      _ptr(self.loss_mask) if use_loss_mask else None, B, S, p.K, hard[0], hard[1], None if bw is None else _ptr(self.pixel_weight),
+                      _ptr(self.pixel_weight), None, st)
         self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_dice", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
                 self.params[woff:].data_ptr(), self.params[boff:].data_ptr(), _ptr(self.labels), _ptr(self.loss_mask) if use_loss_mask else None,
                   _ptr(self.acc_mask) if use_acc_mask else None, 1.0 / n_glob, None if wc is None else wc.ctypes.data, float(self._focal_gamma),
-                  None if bw is None else _ptr(self.pixel_weight), None if dice is None else _ptr(self.dice_coef),
+                  None if bw is None and hard is None else _ptr(self.pixel_weight), None if dice is None else _ptr(self.dice_coef),
                   _ptr(self.logits) if want_logits else None,
                   _ptr(self.pred), _ptr(gfeat), ldg, cg, _ptr(self.dw_partial), _ptr(self.db_partial), _ptr(self.loss_partial),
                   _ptr(self.conf), st)

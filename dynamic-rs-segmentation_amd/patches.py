@@ -455,6 +455,48 @@ def parse_dice(text):
     return check_dice(tuple(vals))
 
 
+# ------------------------------------------------------------------- hard example mining in the training loss
+MAX_HARD_MIN_KEEP = (1 << 24) - 1      # the range drs_net_set_hard_mining takes (include/drs.h)
+DEFAULT_HARD_MINING = (1.0, 0)         # off: every pixel in the loss is kept
+
+
+def check_hard_mining(hard_mining):
+    """Online hard example mining in the training loss as the library takes it: (keep, min_keep) -- or (keep,), or a
+    bare number keep -- with keep finite in (0, 1] (1: off) and min_keep an integer in [0, 2^24) (default 0).  Returns (float, int).
+    Anything else: ValueError."""
+    t = tuple(hard_mining) if isinstance(hard_mining, (tuple, list)) else (hard_mining,)
+    what = "hard mining %r: expected keep[, min_keep] with keep in (0, 1] and min_keep an integer in [0, %d]" % (hard_mining, MAX_HARD_MIN_KEEP)
+    if len(t) not in (1, 2) or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in t):
+        raise ValueError(what)
+    keep = float(t[0])
+    min_keep = t[1] if len(t) == 2 else DEFAULT_HARD_MINING[1]
+    if not math.isfinite(keep) or not 0.0 < keep <= 1.0:
+        raise ValueError(what)
+    if isinstance(min_keep, (float, np.floating)):
+        if not math.isfinite(min_keep) or min_keep != int(min_keep):
+            raise ValueError(what)
+    min_keep = int(min_keep)
+    if not 0 <= min_keep <= MAX_HARD_MIN_KEEP:
+        raise ValueError(what)
+    return keep, min_keep
+
+
+def parse_hard_mining(text):
+    """The value of the command lines' --hard-mining option: `keep` or `keep,min_keep` as check_hard_mining takes them (min_keep in
+    decimal digits).  Anything else raises ValueError."""
+    vals = None
+    if text and text == text.strip():
+        parts = text.split(",")
+        try:
+            if len(parts) in (1, 2) and all(q and q == q.strip() for q in parts) and (len(parts) == 1 or parts[1].isdigit()):
+                vals = [float(parts[0])] + [int(q) for q in parts[1:]]
+        except ValueError:
+            vals = None
+    if vals is None:
+        raise ValueError("hard mining %r: expected keep[,min_keep] (a number and an integer)" % (text,))
+    return check_hard_mining(tuple(vals))
+
+
 # ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
 SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores (DESIGN.md 8a.4)
 

@@ -739,6 +739,20 @@ int drs_net_get_boundary_weight(const drs_net_t* net, double* a, double* sigma, 
  * and ignore it.  drs_net_get_dice: the quadruple in use (any pointer may be NULL); (0, 0.5, 0.5, 1) when never set. */
 int drs_net_set_dice(drs_net_t* net, double lam, double alpha, double beta, double smooth);
 int drs_net_get_dice(const drs_net_t* net, double* lam, double* alpha, double* beta, double* smooth);
+/* online hard example mining in drs_train_step's loss (opt-in; the section "Training level: hard example mining" below states the
+ * rule): keep finite in (0, 1], keep == 1 (the default) switches it off whatever min_keep is -- no new launch, the step is the launches
+ * it was, bit for bit, and the bound buffers "hard_ce" and "pixel_weight" are not touched; min_keep in [0, 2^24); anything else
+ * DRS_ERR_ARG, and the pair in use stays.  With keep < 1 the step runs, in this order: the boundary-weight launch if that option is on;
+ * the classifier in its inference form into the bound buffer "logits" (ONE such launch when the Dice term is on as well: the two
+ * pre-passes share it); drs_patch_dice_coeffs if on; drs_patch_hard_weight(logits, "hard_ce", labels, loss_mask if and only if
+ * DRS_USE_LOSS_MASK, ..., "pixel_weight" if the boundary weight is on else NULL, "pixel_weight", NULL); and the classifier as
+ * drs_classifier_loss_dice with "pixel_weight" as its pixel map.  All of it is accounted under the timing kind "classifier_loss".
+ * "scalars"[0] is then the mined loss: inv_n sum_b (n_b / k_b) sum over the kept pixels of patch b of whatever cross-entropy form is
+ * active (+ L_dice over ALL in-loss pixels when that term is on: it is not mined).  The normaliser is unchanged; no collective, event
+ * or stream is added.  drs_forward and drs_forward_staged have no loss and ignore it.  drs_net_get_hard_mining: the pair in use
+ * (either pointer may be NULL); (1, 0) when never set. */
+int drs_net_set_hard_mining(drs_net_t* net, double keep, int min_keep);
+int drs_net_get_hard_mining(const drs_net_t* net, double* keep, int* min_keep);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
@@ -905,6 +919,41 @@ int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int
                              int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
                              void* stream);
 int drs_dice_loss_add(const double* patch_loss, int B, double* loss_sum, void* stream);
+
+/* ==================================================================================================================
+ * Training level: hard example mining (opt-in; csrc/hard_mining.hip).  Online hard example mining, also called
+ * bootstrapped cross-entropy (Wu et al., Bridging category-level and instance-level semantic segmentation, 2016; Shrivastava et al.,
+ * 2016): the cross-entropy of a step runs over the hardest share of each PATCH's pixels only, as the net ranks them at that step.  Per
+ * patch, so that the loss stays a sum over patches: a sharded batch gives the single-rank loss and gradient with no collective.
+ * NORMATIVE: this text and the numpy statement tests/hard_mining_ref.py.
+ * Options: keep finite in (0, 1]; min_keep an integer in [0, 2^24).
+ * "In the loss" means what it means for the cross-entropy: loss_mask set where one is given, and label < K.
+ * For patch b, every quantity over that patch alone:
+ *     n_b = the number of in-loss pixels          k_b = min(n_b, max(ceil(keep n_b), min_keep))    (product and ceil in fp64)
+ *     key(p) = log(se) + (max - logit_y), fp32 from the fp32 logits, softmax max-subtracted: se >= 1, key >= +0 -- the PLAIN
+ *         cross-entropy: class weights, the focal factor and the pixel map do not move the ranking
+ *     kept = the k_b in-loss pixels with the largest keys, ties towards the lower pixel index (a total order: the selection is a
+ *         pure function of the keys)
+ *     weight_out[p] = kept ? (float)((double)n_b / (double)k_b) * w_in[p] : 0.f       w_in = pixel_weight_in, or 1 without one (one
+ *         fp32 multiply; with k_b == n_b the scale is exactly 1 and the map leaves as it came).  n_b == 0: all-zero weights, k_b = 0.
+ * The fused classifier multiplies weight_out into the pixel's loss term and gradient like any pixel map (drs_classifier_loss_pixel),
+ * so the data term becomes inv_n sum_b (n_b / k_b) sum_{kept p} term(p): each patch contributes the mean of its kept terms, counted
+ * by its share of in-loss pixels; inv_n stays 1 / global in-loss pixels.  The selection is a constant in the gradient.
+ *
+ * drs_patch_hard_weight: logits = float [B S S][K] (what the classifier's inference form writes) or NULL; ce = float [B S S]; labels =
+ *     uint8 [B S S]; loss_mask = uint8 [B S S] or NULL; pixel_weight_in = float [B S S] or NULL, and may be weight_out itself (each
+ *     element is read and written by the same thread); weight_out = float [B S S]; kept_out = int [B] (k_b) or NULL.
+ *     With logits, ce is WRITTEN: the key at in-loss pixels, +0 elsewhere.  With logits == NULL, ce is the INPUT: only in-loss entries
+ *     are read, and they must be >= +0 and not NaN -- device data, not checked; a violation gives an unspecified selection but no
+ *     access outside the buffers.
+ *     An exact radix select of the k_b-th largest key over the fp32 bit pattern (four passes of 8 bits, integer LDS atomics), then a
+ *     fixed-order prefix count over the ties: no floating-point atomics, the same bits on every run and every rank.  One launch, one
+ *     workgroup per patch, which reads and writes its own patch only; no scratch; any S with B S S < 2^24.
+ *     Ranges, else DRS_ERR_ARG (nothing is launched): ce, labels, weight_out not NULL; B, S >= 1, B S S < 2^24; K in 1..8; keep finite
+ *     in (0, 1] (1 is legal here: everything is kept, at scale 1); min_keep in [0, 2^24). */
+int drs_patch_hard_weight(const float* logits, float* ce, const unsigned char* labels, const unsigned char* loss_mask, int B, int S,
+                          int K, double keep, int min_keep, const float* pixel_weight_in, float* weight_out, int* kept_out,
+                          void* stream);
 
 #ifdef __cplusplus
 }
