@@ -105,6 +105,11 @@ SIGNATURES = {
     "drs_dice_loss_add": (_i, [_p, _i, _p, _p]),
     # ---- training level: hard example mining (csrc/hard_mining.hip)
     "drs_patch_hard_weight": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _i, _p, _p, _p, _p]),
+    # ---- training level: Lovasz-softmax term (csrc/lovasz.hip, csrc/pointwise.hip)
+    "drs_lovasz_scratch_bytes": (_sz, [_i, _i, _i]),
+    "drs_patch_lovasz_grad": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p, _sz, _p]),
+    "drs_classifier_loss_region": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _p, _p, _i, _i, _p,
+                                        _p, _p, _p, _p]),
     # ---- step level (csrc/engine.hip)
     "drs_net_create": (_i, [C.c_char_p, _i, _i, _f, _i, _i, _i, _f, C.POINTER(_p)]),
     "drs_net_destroy": (None, [_p]),
@@ -151,6 +156,8 @@ SIGNATURES = {
     "drs_net_get_dice": (_i, [_p, C.POINTER(_d), C.POINTER(_d), C.POINTER(_d), C.POINTER(_d)]),
     "drs_net_set_hard_mining": (_i, [_p, _d, _i]),
     "drs_net_get_hard_mining": (_i, [_p, C.POINTER(_d), C.POINTER(_i)]),
+    "drs_net_set_lovasz": (_i, [_p, _d]),
+    "drs_net_get_lovasz": (_i, [_p, C.POINTER(_d)]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),
     "drs_net_timing_summary": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),

@@ -142,9 +142,10 @@ struct LayerPtrs {
 struct Ptrs {
   bool ok = false;
   float *params, *grads, *momentum, *bn, *partial, *gxh, *gz[2], *slab, *w0pad, *conv_ws, *bwd_means, *act, *gpool, *se_scratch;
-  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef, *hard_ce;
+  float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef, *hard_ce, *lovasz_err, *region_grad;
   size_t conv_ws_floats;
-  double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch, *dice_loss;
+  double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch, *dice_loss, *lovasz_loss, *lovasz_scratch;
+  size_t lovasz_scratch_bytes;
   unsigned char *pred, *labels, *acc_mask, *loss_mask;
   unsigned int* conf;
   std::vector<LayerPtrs> L;
@@ -197,6 +198,7 @@ struct drs_net {
   double dice_lam = 0.0, dice_alpha = 0.5, dice_beta = 0.5, dice_smooth = 1.0;      // soft Dice / Tversky term of the training loss (drs_net_set_dice); lam == 0: off, no launch
   double hard_keep = 1.0;                   // hard example mining in the training loss (drs_net_set_hard_mining); keep == 1: off, no launch
   int hard_min_keep = 0;
+  double lovasz_lam = 0.0;                  // Lovasz-softmax term of the training loss (drs_net_set_lovasz); lam == 0: off, no launch
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -431,6 +433,12 @@ void list_buffers(drs_net* n) {
   n->add_buf("dice_coef", B * n->K * 2, F32);      // (G_in, G_out) per patch and class, and the patches' loss terms (drs_net_set_dice); untouched while it is off
   n->add_buf("dice_loss", B, F64);
   n->add_buf("hard_ce", M, F32);             // the keys of hard example mining: a step's plain cross-entropy per pixel (drs_net_set_hard_mining); untouched while it is off
+  // the Lovasz-softmax term (drs_net_set_lovasz): the error keys, the per-(pixel, class) map the fused classifier reads, the patches'
+  // loss terms and the pre-pass's scratch; untouched while it is off
+  n->add_buf("lovasz_err", M * n->K, F32);
+  n->add_buf("region_grad", M * n->K, F32);
+  n->add_buf("lovasz_loss", B, F64);
+  n->add_buf("lovasz_scratch", drs_lovasz_scratch_bytes(n->b_max, n->s_max, n->K) / 8, F64);
   n->add_buf("logits", M * n->K, F32);
   n->add_buf("pred", M, U8);
   n->add_buf("conf", (size_t)n->K * n->K, I32);
@@ -586,6 +594,8 @@ bool resolve(drs_net* n) {
   P.pixel_weight = n->p<float>("pixel_weight");
   P.dice_coef = n->p<float>("dice_coef"); P.dice_loss = n->p<double>("dice_loss");
   P.hard_ce = n->p<float>("hard_ce");
+  P.lovasz_err = n->p<float>("lovasz_err"); P.region_grad = n->p<float>("region_grad"); P.lovasz_loss = n->p<double>("lovasz_loss");
+  P.lovasz_scratch = n->p<double>("lovasz_scratch"); P.lovasz_scratch_bytes = drs_lovasz_scratch_bytes(n->b_max, n->s_max, n->K);
   const Slab& f = n->slabs[n->feat];
   P.feat_act = n->p<float>("act:" + f.name); P.feat_gact = n->p<float>("gact:" + f.name);
   P.L.assign(n->layers.size(), LayerPtrs());
@@ -1153,6 +1163,22 @@ int drs_net_get_hard_mining(const drs_net_t* n, double* keep, int* min_keep) {
   return DRS_OK;
 }
 
+// Lovasz-softmax term of the training loss (drs_train_step only; include/drs.h, "Training level: Lovasz-softmax term"): lam == 0
+// switches it off.  The step then runs the classifier in its inference form into "logits" (once, shared with the Dice and mining
+// pre-passes), drs_patch_lovasz_grad over them into "region_grad" (the Dice coefficients folded in when that term is on too), and the
+// fused classifier as drs_classifier_loss_region; the patches' terms join scalars[0] before its all-reduce.
+int drs_net_set_lovasz(drs_net_t* n, double lam) {
+  if (!n || !std::isfinite(lam) || lam < 0.0 || lam > 64.0) return DRS_ERR_ARG;
+  n->lovasz_lam = lam;
+  return DRS_OK;
+}
+
+int drs_net_get_lovasz(const drs_net_t* n, double* lam) {
+  if (!n) return DRS_ERR_ARG;
+  if (lam) *lam = n->lovasz_lam;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1363,6 +1389,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   double* scratch = P.colsum_scratch;
   const bool dice = n->dice_lam != 0.0;
   const bool hard = n->hard_keep != 1.0;
+  const bool lovasz = n->lovasz_lam != 0.0;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
     const bool bw = n->bw_a != 0.0;          // off: no launch, and drs_classifier_loss_pixel without a map is drs_classifier_loss_focal
@@ -1373,7 +1400,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     // classifier once in its inference form (logits only) for both, the coefficients of every (patch, class) and / or the weight map
     // that keeps the hardest pixels (times the boundary weight, in place), then the fused launch with them.  Off: none of it, and
     // drs_classifier_loss_dice without coefficients is drs_classifier_loss_pixel
-    if (dice || hard)
+    if (dice || hard || lovasz)
       DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b, nullptr, nullptr,
                                         nullptr, 1.f, nullptr, 0.f, nullptr, P.logits, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
                                         nullptr, st));
@@ -1383,12 +1410,26 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     if (hard)
       DRS_TRY(drs_patch_hard_weight(P.logits, P.hard_ce, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K,
                                     n->hard_keep, n->hard_min_keep, bw ? P.pixel_weight : nullptr, P.pixel_weight, nullptr, st));
-    DRS_TRY(drs_classifier_loss_dice(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
-                                     P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
-                                     (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
-                                     n->has_wc ? n->wc : nullptr, n->focal_gamma, (bw || hard) ? P.pixel_weight : nullptr,
-                                     dice ? P.dice_coef : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
-                                     P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    // the Lovasz-softmax term needs the order of every class's errors in every patch: its pre-pass leaves one value per (pixel, class),
+    // the Dice coefficients folded in, so the fused launch reads one map form only
+    if (lovasz) {
+      DRS_TRY(drs_patch_lovasz_grad(P.logits, P.lovasz_err, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K,
+                                    n->lovasz_lam, dice ? P.dice_coef : nullptr, nullptr, P.region_grad, P.lovasz_loss, P.lovasz_scratch,
+                                    P.lovasz_scratch_bytes, st));
+      DRS_TRY(drs_classifier_loss_region(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+                                         P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                         (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
+                                         n->has_wc ? n->wc : nullptr, n->focal_gamma, (bw || hard) ? P.pixel_weight : nullptr,
+                                         P.region_grad, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
+                                         P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    } else {
+      DRS_TRY(drs_classifier_loss_dice(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
+                                       P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                       (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
+                                       n->has_wc ? n->wc : nullptr, n->focal_gamma, (bw || hard) ? P.pixel_weight : nullptr,
+                                       dice ? P.dice_coef : nullptr, (flags & DRS_WANT_LOGITS) ? P.logits : nullptr,
+                                       P.pred, gfeat, f.C, 0, P.dw_partial, P.db_partial, P.loss_partial, conf, st));
+    }
   }
   // the classifier's slab reductions (its kernel / bias gradients, the cross-entropy sum) and the L2 term: seven launches of ~5 us that
   // nothing needs before the end of the step -- in the two-stream backward pass they go to the filter-gradient stream (below), off
@@ -1399,6 +1440,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     DRS_TRY(drs_rows_reduce_f32(P.db_partial, crow, n->K, grads + n->cls_b, scratch, s));
     DRS_TRY(drs_sum_f64(P.loss_partial, crow, scalars, s));
     if (dice) DRS_TRY(drs_dice_loss_add(P.dice_loss, B, scalars, s));      // (+ the patches' Dice terms: scalars[0] goes on to its all-reduce and 1 / n_glob as before)
+    if (lovasz) DRS_TRY(drs_dice_loss_add(P.lovasz_loss, B, scalars, s));  // (+ the patches' Lovasz terms, likewise)
     DRS_TRY(drs_l2_loss(params, n->n_decay, P.l2_scratch, scalars + 1, s));
     return DRS_OK;
   };

@@ -898,7 +898,10 @@ struct ClsArgs {
   float gamma;               // focusing parameter of the focal forms (CLS_FOCAL), by value; the other forms do not read it
   const float* pixel_weight; // [M] per-pixel weights of the CLS_PIXEL forms (the boundary weight map); the other forms do not read it
                              // (the CLS_DICE forms read it when it is not null)
-  const float* dice_coef;    // [B][K][2] (G_in, G_out) of the CLS_DICE forms (drs_patch_dice_coeffs); the other forms do not read it
+  union {                    // (one slot: the two flags are never combined, and the arguments keep the size they had)
+    const float* dice_coef;    // [B][K][2] (G_in, G_out) of the CLS_DICE forms (drs_patch_dice_coeffs); the other forms do not read it
+    const float* region_grad;  // [M][K] g_c(p) of the CLS_REGION forms (drs_patch_lovasz_grad); the other forms do not read it
+  };
 };
 
 // Loss mode of the three classifier forms (template argument LM).  CLS_PLAIN: the cross-entropy, the code the kernels always had;
@@ -911,12 +914,31 @@ struct ClsArgs {
 // g_c = [y == c] ? G_in[b][c] : G_out[b][c] from dice_coef; class weights, focal factor and pixel weight do not touch it, and the loss
 // sum stays the cross-entropy part.  The Dice forms always multiply a pixel weight in: pixel_weight[p], or 1 when there is no map
 // (x * 1 is x: the cross-entropy part is bit for bit that of the form without the flag), which halves the instantiations.
-constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2, CLS_PIXEL = 4, CLS_DICE = 8;
+// CLS_REGION is CLS_DICE with another source of g (never with CLS_DICE or CLS_PIXEL): g_c = region_grad[p][c], a value per (pixel,
+// class) that a pre-pass left (the Lovasz-softmax term, with the Dice coefficients folded in when both are on: include/drs.h, DESIGN.md
+// 3f).  The arithmetic on g is one device function per kernel family (cls_region_add, cls_mc_region_add) that both flags call.
+constexpr int CLS_PLAIN = 0, CLS_WEIGHTED = 1, CLS_FOCAL = 2, CLS_PIXEL = 4, CLS_DICE = 8, CLS_REGION = 16;
 constexpr int cls_base(int lm) { return lm & 3; }
-constexpr bool cls_has_pw(int lm) { return (lm & (CLS_PIXEL | CLS_DICE)) != 0; }
-// A pixel's Dice coefficients in the matrix-core forms: (G_in, G_out) of its patch for the lane's two class slots
+constexpr bool cls_has_pw(int lm) { return (lm & (CLS_PIXEL | CLS_DICE | CLS_REGION)) != 0; }
+constexpr bool cls_has_g(int lm) { return (lm & (CLS_DICE | CLS_REGION)) != 0; }
+// A pixel's Dice coefficients in the matrix-core forms: (G_in, G_out) of its patch for the lane's two class slots.  CLS_REGION: c0.x
+// and c1.x hold g of the pixel for the two slots, the .y halves are unused
 typedef float cls_f32x2 __attribute__((ext_vector_type(2)));
 struct ClsDice { cls_f32x2 c0, c1; };
+
+// The region term of a pixel in the vector-ALU form, added to its logit gradients: inv_n P_k (g_k - sum_c P_c g_c), P_k = ex[k] * inv,
+// the sum in ascending class order (a slot beyond K has ex = 0 and g = 0).  gk(k): the pixel's g for class slot k, from either source
+template <int KM, typename GK>
+__device__ __forceinline__ void cls_region_add(float inv_n, const float (&ex)[KM], float inv, GK&& gk, float (&dl)[KM]) {
+  float g[KM], s = 0.f;
+#pragma unroll
+  for (int k = 0; k < KM; ++k) {
+    g[k] = gk(k);
+    s += ex[k] * inv * g[k];
+  }
+#pragma unroll
+  for (int k = 0; k < KM; ++k) dl[k] += inv_n * (ex[k] * inv) * (g[k] - s);
+}
 
 // The weight of a pixel's label: a register select over the eight by-value weights (a label outside [0, K) never enters the loss:
 // whatever comes out for it is multiplied into nothing)
@@ -1074,7 +1096,7 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
     constexpr bool WT = LM != CLS_PLAIN;
     float wy = WT ? cls_weight<KM>(a, y) : 1.f;
     if constexpr ((LM & CLS_PIXEL) != 0) wy *= a.pixel_weight[p];
-    if constexpr ((LM & CLS_DICE) != 0) wy *= a.pixel_weight ? a.pixel_weight[p] : 1.f;
+    if constexpr (cls_has_g(LM)) wy *= a.pixel_weight ? a.pixel_weight[p] : 1.f;
     if constexpr (cls_base(LM) == CLS_FOCAL) {
       // every lane holds all the classes: so in ascending class order, then a few scalar-like operations per pixel
       float so = 0.f;
@@ -1104,14 +1126,13 @@ __global__ __launch_bounds__(256) void classifier_loss_kernel(const ClsArgs a) {
         int b, rem;
         divmod24(p, a.feat.S * a.feat.S, a.rcpSS, b, rem);
         const float* cf = a.dice_coef + (size_t)b * K * 2;
-        float g[KM], s = 0.f;
-#pragma unroll
-        for (int k = 0; k < KM; ++k) {
-          g[k] = k < K ? (k == y ? cf[2 * k] : cf[2 * k + 1]) : 0.f;
-          s += ex[k] * inv * g[k];
-        }
-#pragma unroll
-        for (int k = 0; k < KM; ++k) dl[k] += a.inv_n * (ex[k] * inv) * (g[k] - s);
+        cls_region_add<KM>(a.inv_n, ex, inv, [=](int k) { return k < K ? (k == y ? cf[2 * k] : cf[2 * k + 1]) : 0.f; }, dl);
+      }
+    }
+    if constexpr ((LM & CLS_REGION) != 0) {
+      if (in_loss) {          // (wave-uniform, as above)
+        const float* gp = a.region_grad + (size_t)p * K;
+        cls_region_add<KM>(a.inv_n, ex, inv, [=](int k) { return k < K ? gp[k] : 0.f; }, dl);
       }
     }
     if (a.gfeat) {
@@ -1258,6 +1279,18 @@ __device__ __forceinline__ void cls_mc_argmax_store(const ClsArgs& a, int K, int
 // of ex_k over k != y, and the label's logit) all use one exchange pattern, so that every lane of the pixel gets the same bits (a + b
 // == b + a bit for bit; the logit sum has one non-zero term: exact); the focal ex_y is recomputed from that logit, the same
 // instruction on the same operands as in the lane that owns class y.
+// The region term of a pixel in the matrix-core forms, added to the lane's two logit gradients: sum_c P_c g_c over the pixel's four
+// lanes by the exchange pattern of se; a slot beyond K has ex = 0 and adds nothing
+__device__ __forceinline__ void cls_mc_region_add(const ClsArgs& a, bool in_loss, float ex0, float ex1, float inv, float g0, float g1,
+                                                  float& dl0, float& dl1) {
+  const float pr0 = ex0 * inv, pr1 = ex1 * inv;
+  float s = pr0 * g0 + pr1 * g1;
+  s += __shfl_xor(s, 16);
+  s += __shfl_xor(s, 32);
+  dl0 += in_loss ? a.inv_n * pr0 * (g0 - s) : 0.f;
+  dl1 += in_loss ? a.inv_n * pr1 * (g1 - s) : 0.f;
+}
+
 template <int LM>
 __device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y, bool in_loss, float pw, const ClsDice& dc, int cls0,
                                                   int cls1, float lg0, float lg1, float mx, float& dl0, float& dl1, double& lsum) {
@@ -1289,16 +1322,12 @@ __device__ __forceinline__ void cls_mc_pixel_grad(const ClsArgs& a, int K, int y
     if (in_loss && cls1 == y) lsum += cls_loss_term<LM>(wy, se, mx, lg1, 0.f, 0.f);
   }
   if constexpr ((LM & CLS_DICE) != 0) {
-    // the Dice term (dc: the coefficients of the pixel's patch for this lane's two slots, unread otherwise): sum_c P_c g_c over the
-    // pixel's four lanes by the exchange pattern of se; a slot beyond K has ex = 0 and adds nothing
+    // the Dice term (dc: the coefficients of the pixel's patch for this lane's two slots, unread otherwise)
     const float g0 = cls0 == y ? dc.c0.x : dc.c0.y, g1 = cls1 == y ? dc.c1.x : dc.c1.y;
-    const float pr0 = ex0 * inv, pr1 = ex1 * inv;
-    float s = pr0 * g0 + pr1 * g1;
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    dl0 += in_loss ? a.inv_n * pr0 * (g0 - s) : 0.f;
-    dl1 += in_loss ? a.inv_n * pr1 * (g1 - s) : 0.f;
+    cls_mc_region_add(a, in_loss, ex0, ex1, inv, g0, g1, dl0, dl1);
   }
+  if constexpr ((LM & CLS_REGION) != 0)      // (dc.c0.x, dc.c1.x: g of the pixel for this lane's two slots)
+    cls_mc_region_add(a, in_loss, ex0, ex1, inv, dc.c0.x, dc.c1.x, dl0, dl1);
 }
 
 // The address of a pixel's Dice coefficients for class slot cls (slot 0's for a slot beyond K: loaded, never used)
@@ -1306,6 +1335,11 @@ __device__ __forceinline__ const cls_f32x2* cls_dice_at(const ClsArgs& a, int K,
   int b, rem;
   divmod24(pix, a.feat.S * a.feat.S, a.rcpSS, b, rem);
   return reinterpret_cast<const cls_f32x2*>(a.dice_coef) + (size_t)b * K + (cls < K ? cls : 0);
+}
+
+// The address of a pixel's region value for class slot cls (slot 0's for a slot beyond K: loaded, never used)
+__device__ __forceinline__ const float* cls_region_at(const ClsArgs& a, int K, int pix, int cls) {
+  return a.region_grad + (size_t)pix * K + (cls < K ? cls : 0);
 }
 
 // The workgroup's sums in wave order, into slab row blockIdx.x, and its confusion counts into a.conf.
@@ -1438,6 +1472,11 @@ __global__ __launch_bounds__(256) void classifier_mfma_kernel(const ClsArgs a) {
       dc.c0 = *cls_dice_at(a, K, pixc, cls0);
       dc.c1 = *cls_dice_at(a, K, pixc, cls1);
     }
+    if constexpr ((LM & CLS_REGION) != 0) {
+      if (a.pixel_weight) pw = a.pixel_weight[pixc];
+      dc.c0.x = *cls_region_at(a, K, pixc, cls0);
+      dc.c1.x = *cls_region_at(a, K, pixc, cls1);
+    }
     cls_mc_pixel_grad<LM>(a, K, y, in_loss, pw, dc, cls0, cls1, lg0, lg1, mx, dl0, dl1, lsum);
     db0 += dl0;
     db1 += dl1;
@@ -1561,6 +1600,13 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dc.c0) : "v"(cls_dice_at(a, K, pixc, cls0)) : "memory");
       asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(dc.c1) : "v"(cls_dice_at(a, K, pixc, cls1)) : "memory");
     }
+    // CLS_REGION: the same three loads, the two pairs narrowed to the pixel's two dwords of the map
+    float rg0 = 0.f, rg1 = 0.f;
+    if constexpr ((LM & CLS_REGION) != 0) {
+      asm volatile("global_load_dword %0, %1, off" : "=v"(vpw) : "v"(a.pixel_weight ? a.pixel_weight + pixc : a.region_grad) : "memory");
+      asm volatile("global_load_dword %0, %1, off" : "=v"(rg0) : "v"(cls_region_at(a, K, pixc, cls0)) : "memory");
+      asm volatile("global_load_dword %0, %1, off" : "=v"(rg1) : "v"(cls_region_at(a, K, pixc, cls1)) : "memory");
+    }
     if (TRAIN) {
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(ylab) : "v"(a.labels + pixc) : "memory");
       asm volatile("global_load_ubyte %0, %1, off" : "=v"(vlm) : "v"(lm + pixc) : "memory");
@@ -1594,6 +1640,12 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
       if constexpr ((LM & CLS_DICE) != 0) {      // (and the Dice loads: issued before the DMA, so older than the NI operations the wait leaves)
         asm volatile("" : "+v"(vpw), "+v"(dc.c0), "+v"(dc.c1) :: "memory");
         vpw = a.pixel_weight ? vpw : 1.f;
+      }
+      if constexpr ((LM & CLS_REGION) != 0) {      // (likewise)
+        asm volatile("" : "+v"(vpw), "+v"(rg0), "+v"(rg1) :: "memory");
+        vpw = a.pixel_weight ? vpw : 1.f;
+        dc.c0.x = rg0;
+        dc.c1.x = rg1;
       }
       const int y = (int)ylab;
       if (G == 0 && valid && a.conf && (!a.acc_mask || vam) && y < K) atomicAdd(&confs[y * 8 + am], 1u);
@@ -1654,7 +1706,7 @@ __global__ __launch_bounds__(256, 1) void classifier_dma_kernel(const ClsArgs a)
 
 // Run-time launch parameters onto template arguments, handed to a generic lambda as std::integral_constants.
 // cls_width: the width C / 64 = Q .. QMAX - 1, anything else QMAX.  cls_mode: (loss mode, labels present) onto <TRAIN, LM> -- the
-// weighted and focal modes, with or without CLS_PIXEL or CLS_DICE, exist for training only, so no TRAIN = false kernel is instantiated
+// weighted and focal modes, with or without CLS_PIXEL, CLS_DICE or CLS_REGION, exist for training only, so no TRAIN = false kernel is instantiated
 // with them.
 template <int Q, int QMAX, typename F>
 static void cls_width(int cq, F&& f) {
@@ -1664,7 +1716,9 @@ static void cls_width(int cq, F&& f) {
 }
 template <typename F>
 static void cls_mode(int lm, bool train, F&& f) {
-  if (lm == (CLS_FOCAL | CLS_DICE)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_DICE>{});
+  if (lm == (CLS_FOCAL | CLS_REGION)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_REGION>{});
+  else if (lm == (CLS_WEIGHTED | CLS_REGION)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_REGION>{});
+  else if (lm == (CLS_FOCAL | CLS_DICE)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_DICE>{});
   else if (lm == (CLS_WEIGHTED | CLS_DICE)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_DICE>{});
   else if (lm == (CLS_FOCAL | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_FOCAL | CLS_PIXEL>{});
   else if (lm == (CLS_WEIGHTED | CLS_PIXEL)) f(std::true_type{}, std::integral_constant<int, CLS_WEIGHTED | CLS_PIXEL>{});
@@ -2112,13 +2166,15 @@ int drs_debug_cls_variant(int v) { const int old = g_cls_variant; if (v >= 0) g_
 // NULL.  NULL or no labels: the dispatch above, unchanged; otherwise the CLS_PIXEL instantiations of the weighted form (the focal one
 // with gamma > 0), which multiply pixel_weight[p] into the class weight (ones when none are set).  dice_coef: DEVICE pointer to
 // B K 2 floats (8-byte aligned) or NULL.  NULL or no labels: the dispatch above, unchanged; otherwise the CLS_DICE instantiations of the
-// weighted form (the focal one with gamma > 0), which read the map when there is one.
-int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
-                             const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
-                             const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
-                             const float* pixel_weight, const float* dice_coef, float* logits, unsigned char* pred, float* gfeat,
-                             int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
-                             void* stream) {
+// weighted form (the focal one with gamma > 0), which read the map when there is one.  region_grad: DEVICE pointer to B S S K floats
+// or NULL (never beside dice_coef: the two entry points below pass one of them).  NULL or no labels: the dispatch above, unchanged;
+// otherwise the CLS_REGION instantiations, likewise.
+static int classifier_loss_any(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                               const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                               const float* pixel_weight, const float* dice_coef, const float* region_grad, float* logits,
+                               unsigned char* pred, float* gfeat, int ld_g, int coff_g, float* dw_partial, float* db_partial,
+                               double* loss_partial, unsigned int* conf, void* stream) {
   if (!feat || !w || !bias || K < 1 || K > 8 || C < 64 || C % 64 || C / 64 > 7) return DRS_ERR_ARG;
   if (B < 1 || S < 1 || P < 0 || !std::isfinite(inv_n) || inv_n < 0.f) return DRS_ERR_ARG;
   if (!std::isfinite(focal_gamma) || focal_gamma < 0.f || focal_gamma > 8.f) return DRS_ERR_ARG;
@@ -2140,7 +2196,9 @@ int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int
   const bool focal = focal_gamma > 0.f && labels;
   const bool px = pixel_weight && labels;
   const bool dice = dice_coef && labels;
-  const int lm = dice ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_DICE)
+  const bool region = region_grad && labels;
+  const int lm = region ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_REGION)
+                 : dice ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_DICE)
                       : px ? ((focal ? CLS_FOCAL : CLS_WEIGHTED) | CLS_PIXEL) : focal ? CLS_FOCAL : wt ? CLS_WEIGHTED : CLS_PLAIN;
   ClsArgs a;
   a.feat = mkview(const_cast<float*>(feat), S, P, ld, coff); a.C = C; a.K = K; a.M = (int)M; a.w = w; a.bias = bias;
@@ -2151,7 +2209,7 @@ int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int
   for (int k = 0; k < 8; ++k) a.wc[k] = wt && k < K ? class_weights[k] : 1.f;
   a.gamma = focal ? focal_gamma : 0.f;
   a.pixel_weight = px ? pixel_weight : nullptr;
-  a.dice_coef = dice ? dice_coef : nullptr;
+  a.dice_coef = region ? region_grad : dice ? dice_coef : nullptr;      // (one slot for both)
   const int nblk = drs_classifier_rows(B, S);
   a.rows_per_block = (int)(((M + nblk - 1) / nblk + 63) / 64 * 64);      // whole 16-pixel tiles per wave; trailing workgroups may be empty
   hipStream_t st = (hipStream_t)stream;
@@ -2191,6 +2249,29 @@ int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int
     });
   });
   return DRS_LAUNCH_CHECK();
+}
+
+int drs_classifier_loss_dice(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                             const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                             const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                             const float* pixel_weight, const float* dice_coef, float* logits, unsigned char* pred, float* gfeat,
+                             int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
+                             void* stream) {
+  return classifier_loss_any(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, class_weights, focal_gamma,
+                             pixel_weight, dice_coef, nullptr, logits, pred, gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf,
+                             stream);
+}
+
+int drs_classifier_loss_region(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                               const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                               const float* pixel_weight, const float* region_grad, float* logits, unsigned char* pred, float* gfeat,
+                               int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
+                               void* stream) {
+  if ((uintptr_t)region_grad % 4) return DRS_ERR_ARG;
+  return classifier_loss_any(feat, B, S, P, ld, coff, C, K, w, bias, labels, loss_mask, acc_mask, inv_n, class_weights, focal_gamma,
+                             pixel_weight, nullptr, region_grad, logits, pred, gfeat, ld_g, coff_g, dw_partial, db_partial, loss_partial, conf,
+                             stream);
 }
 
 int drs_classifier_loss_pixel(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,

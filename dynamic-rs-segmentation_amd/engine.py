@@ -106,7 +106,8 @@ class EngineNet(DilatedNet):
         self.idx = [b.get("idx%d" % i) for i in range(nl)]
         self.mean_rstd = [b["mean_rstd%d" % i] for i in range(nl)]
         for n in ("sums", "partial", "gxh", "gz", "slab", "w0pad", "dw_partial", "db_partial", "loss_partial", "scalars", "logits", "pred", "conf",
-                  "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss", "hard_ce"):
+                  "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss", "hard_ce", "lovasz_err",
+                  "region_grad", "lovasz_loss", "lovasz_scratch"):
             setattr(self, n, b[n])
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
@@ -351,6 +352,17 @@ class EngineNet(DilatedNet):
         keep, min_keep = C.c_double(), C.c_int()
         _lib.call("drs_net_get_hard_mining", self.h, C.byref(keep), C.byref(min_keep))
         return None if keep.value == 1.0 else (float(keep.value), int(min_keep.value))
+
+    def _lovasz_changed(self):
+        """hand lam to the library's net (drs_net_set_lovasz: the step runs the Lovasz pre-pass before its fused classifier)"""
+        _lib.call("drs_net_set_lovasz", self.h, float(self._lovasz or 0.0))
+
+    @property
+    def lovasz(self):
+        """lam the library's net holds (drs_net_get_lovasz), or None when the term is off (lam == 0)"""
+        lam = C.c_double()
+        _lib.call("drs_net_get_lovasz", self.h, C.byref(lam))
+        return None if lam.value == 0.0 else float(lam.value)
 
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always

@@ -199,16 +199,44 @@ def load_hard_mining(net, former_model_path):
             print("Hard mining (restored from " + path + "): " + _hard_mining_str(net.hard_mining))
 
 
+LOVASZ_SIDE = "lovasz_step_"
+
+
+def _lovasz_str(lam):
+    return "lambda " + "{:.6g}".format(lam)
+
+
+def save_lovasz(net, output_path, step):
+    """the Lovasz-softmax term of the training loss, when on, as the side file `lovasz_step_<step>.npy` beside the size scores: one
+    float64 (lam) (state of the run, not of the model, as the other options of the loss are)"""
+    lam = getattr(net, "lovasz", None)
+    if lam is not None:
+        np.save(output_path + LOVASZ_SIDE + str(step) + ".npy", np.asarray([lam], dtype=np.float64))
+
+
+def load_lovasz(net, former_model_path):
+    """set lam that save_lovasz left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep or not hasattr(net, "set_lovasz"):
+        return
+    path = head + LOVASZ_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        net.set_lovasz(float(np.load(path).reshape(-1)[0]))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Lovasz term (restored from " + path + "): " + _lovasz_str(net.lovasz))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
     """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights,
-    the focal gamma, the boundary weight, the Dice term and the hard mining of the loss when set (save_class_weights,
-    save_focal_gamma, save_boundary_weight, save_dice, save_hard_mining)."""
+    the focal gamma, the boundary weight, the Dice term, the hard mining and the Lovasz term of the loss when set (save_class_weights,
+    save_focal_gamma, save_boundary_weight, save_dice, save_hard_mining, save_lovasz)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
     save_focal_gamma(net, output_path, step)
     save_boundary_weight(net, output_path, step)
     save_dice(net, output_path, step)
     save_hard_mining(net, output_path, step)
+    save_lovasz(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -232,6 +260,7 @@ def load_checkpoint(net, former_model_path):
     load_boundary_weight(net, former_model_path)
     load_dice(net, former_model_path)
     load_hard_mining(net, former_model_path)
+    load_lovasz(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -362,6 +391,60 @@ def setup_hard_mining(net, hard_mining, comm, say):
                                if on else "keep 1 (off: every pixel in the loss)") +
             ("" if restored is None or restored == h else " -- replacing the pair restored from the checkpoint, " + _hard_mining_str(restored)))
     return h
+
+
+def setup_lovasz(net, lovasz, comm, say):
+    """The Lovasz-softmax term of a training run (train's `lovasz`; patches.check_lovasz): every rank must hold the same lam, asserted
+    once over the ranks on its float64 bits.  Given, it replaces a value restored from a checkpoint's side file.  One log line names
+    it; lam = 0 on a run that restored none is today's run and says nothing."""
+    lam = P.check_lovasz(lovasz)
+    comm.agree([int(b) for b in np.asarray([lam], dtype=np.float64).view(np.uint32)], "lovasz term")
+    restored = net.lovasz
+    net.set_lovasz(lam)
+    on = lam != 0.0
+    if on or restored is not None:
+        say("Lovasz term: " + (_lovasz_str(lam) + " (the loss is the cross-entropy part + lambda times the pixel-weighted mean over patches of the "
+                                                  "Lovasz-softmax loss over the classes present in the patch; class, focal, boundary and mining weights do not weight it)"
+                               if on else "lambda 0 (off: the cross-entropy part alone)") +
+            ("" if restored is None or restored == lam else " -- replacing the value restored from the checkpoint, " + _lovasz_str(restored)))
+    return lam
+
+
+def lovasz_grad(logits, labels, lam, loss_mask=None, dice_coef=None):
+    """The per-(pixel, class) map drs_train_step makes of a step's logits when the Lovasz-softmax term is on, for
+    inspection: logits float32 [B, S, S, K] and labels uint8 [B, S, S] (tensors on the GPU, or anything np.asarray takes -- then on
+    the current device), loss_mask uint8 [B, S, S] or None, dice_coef float32 [B, K, 2] (drs_patch_dice_coeffs' output, folded into the
+    map) or None.  Returns (grad float32 [B, S, S, K]: g_c(p), 0 where a pixel is not in the loss; rank int64 [B, S, S, K]: the 0-based
+    position of the pixel in the class's order, -1 where the pixel is not in the loss or the class is absent from the patch; err
+    float32 [B, S, S, K]: the error keys; patch_loss float64 [B]) as tensors on that device.  One call of drs_patch_lovasz_grad."""
+    import torch
+    from . import _lib
+
+    def dev(x, dtype):
+        if x is None:
+            return None
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x))).cuda()
+        return x.to(dtype).contiguous()
+    lg, lab = dev(logits, torch.float32), dev(labels, torch.uint8)
+    if lg.dim() != 4 or lab.dim() != 3 or lg.shape[:3] != lab.shape or lab.shape[1] != lab.shape[2]:
+        raise ValueError("lovasz_grad: logits [B, S, S, K] and labels [B, S, S] expected, got %r and %r" % (tuple(lg.shape), tuple(lab.shape)))
+    B, S, K = int(lab.shape[0]), int(lab.shape[1]), int(lg.shape[3])
+    lam = P.check_lovasz(lam)
+    lm, dc = dev(loss_mask, torch.uint8), dev(dice_coef, torch.float32)
+    if lm is not None and lm.shape != lab.shape:
+        raise ValueError("lovasz_grad: loss_mask must have the shape of labels")
+    if dc is not None and tuple(dc.shape) != (B, K, 2):
+        raise ValueError("lovasz_grad: dice_coef must be [B, K, 2]")
+    grad, err = torch.empty_like(lg), torch.empty_like(lg)
+    rank = torch.empty(lg.shape, dtype=torch.int32, device=lab.device)
+    loss = torch.empty(B, dtype=torch.float64, device=lab.device)
+    nbytes = _lib.query("drs_lovasz_scratch_bytes", B, S, K)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=lab.device)
+    with torch.cuda.device(lab.device):
+        _lib.call("drs_patch_lovasz_grad", lg.data_ptr(), err.data_ptr(), lab.data_ptr(), None if lm is None else lm.data_ptr(), B, S, K,
+                  lam, None if dc is None else dc.data_ptr(), rank.data_ptr(), grad.data_ptr(), loss.data_ptr(), scratch.data_ptr(), nbytes,
+                  torch.cuda.current_stream().cuda_stream)
+    return grad, rank.to(torch.int64), err, loss
 
 
 def hard_mining_weights(logits, labels, keep, min_keep, loss_mask=None, pixel_weight=None):
@@ -519,7 +602,7 @@ def train(training_data, training_labels, training_class_distribution, training_
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
           loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
-          scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None):
+          scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None, lovasz=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -551,6 +634,12 @@ def train(training_data, training_labels, training_class_distribution, training_
     the hardest pixels' terms, so it is larger than the loss over all pixels; accuracies, confusion matrices and validation do not
     change.  Given here, it replaces a pair restored from a checkpoint's side file; None keeps that.  Under data parallelism nothing
     is added: the selection is per patch, and the normaliser is unchanged.
+    lovasz (opt-in; None or lam = 0 = today's run, bit for bit): lam -- the Lovasz-softmax term per patch, over the classes present in
+    it, is ADDED to the data term (setup_lovasz, DilatedNet.set_lovasz), beside whatever form the cross-entropy has:
+    class_weights, focal_gamma, boundary_weight and hard_mining do not weight it, and it is not mined.  The loss this loop prints, and
+    that feeds the size scores with update_type="loss", is then the cross-entropy part + the Dice term (if on) + the Lovasz term;
+    accuracies, confusion matrices and validation do not change.  Given here, it replaces a value restored from a checkpoint's side
+    file; None keeps that.  Under data parallelism nothing is added: the order is per patch, and the normaliser is unchanged.
     scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
     log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
     their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
@@ -604,6 +693,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_dice(net, dice, comm, say)
     if hard_mining is not None:
         setup_hard_mining(net, hard_mining, comm, say)
+    if lovasz is not None:
+        setup_lovasz(net, lovasz, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)

@@ -156,6 +156,7 @@ class DilatedNet(object):
         self._boundary_weight = None
         self._dice = None
         self._hard_mining = None
+        self._lovasz = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -333,6 +334,31 @@ class DilatedNet(object):
         """the pair (keep, min_keep) in use, or None when mining is off (never set, or keep == 1)"""
         h = self._hard_mining
         return None if h is None or h[0] == 1.0 else h
+
+    # ------------------------------------------------------------------ Lovasz-softmax term of the training loss
+    def set_lovasz(self, lovasz):
+        """Lovasz-softmax term of the training loss (opt-in): lovasz = lam as patches.check_lovasz takes it, or None /
+        lam == 0 (the step as it is, bit for bit, no new launch).  train_step then adds L_lov = inv_n * sum over patches b of
+        (lam n_b / C_b) sum over the classes present in the patch of the Lovasz extension of the Jaccard loss -- the patch's in-loss
+        pixels (n_b of them) ordered by their error for the class, each error times the Jaccard increment at its position -- to its
+        data term, and the matching per-(pixel, class) term to the logit gradients.  The order is per patch, so a sharded batch trains
+        as the whole one does and no collective is added; it is a constant in the gradient.  Class weights, the focal factor, the
+        boundary weight and hard mining do not weight this term, and it is not mined.  The loss train_step reports is the cross-entropy
+        part + the Dice term (if on) + L_lov; logits, pred, the confusion matrix, the L2 term and every forward pass do not change.
+        State of the training run, not of the model: loops.save_checkpoint keeps it in a side file, and an inference twin does not
+        copy it."""
+        from .patches import check_lovasz
+        self._lovasz = None if lovasz is None else check_lovasz(lovasz)
+        self._lovasz_changed()
+
+    def _lovasz_changed(self):
+        pass
+
+    @property
+    def lovasz(self):
+        """lam in use, or None when the term is off (never set, or lam == 0)"""
+        v = self._lovasz
+        return None if v is None or v == 0.0 else v
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

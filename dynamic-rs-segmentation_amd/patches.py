@@ -497,6 +497,37 @@ def parse_hard_mining(text):
     return check_hard_mining(tuple(vals))
 
 
+# ------------------------------------------------------------------- Lovasz-softmax term of the training loss
+MAX_LOVASZ_LAMBDA = 64.0               # the range drs_net_set_lovasz takes (include/drs.h)
+DEFAULT_LOVASZ = 0.0                   # off
+
+
+def check_lovasz(lovasz):
+    """The Lovasz-softmax term of the training loss as the library takes it: a number lam -- or (lam,) -- finite in
+    [0, 64] (0: off).  Returns the float.  Anything else: ValueError."""
+    t = tuple(lovasz) if isinstance(lovasz, (tuple, list)) else (lovasz,)
+    what = "lovasz weight %r: expected lam in [0, %g]" % (lovasz, MAX_LOVASZ_LAMBDA)
+    if len(t) != 1 or isinstance(t[0], (bool, np.bool_)) or not isinstance(t[0], (int, float, np.integer, np.floating)):
+        raise ValueError(what)
+    lam = float(t[0])
+    if not math.isfinite(lam) or lam < 0.0 or lam > MAX_LOVASZ_LAMBDA:
+        raise ValueError(what)
+    return lam
+
+
+def parse_lovasz(text):
+    """The value of the command lines' --lovasz-weight option: `lam` as check_lovasz takes it.  Anything else raises ValueError."""
+    val = None
+    if text and text == text.strip() and "," not in text:
+        try:
+            val = float(text)
+        except ValueError:
+            val = None
+    if val is None:
+        raise ValueError("lovasz weight %r: expected lam (a number)" % (text,))
+    return check_lovasz(val)
+
+
 # ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
 SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores (DESIGN.md 8a.4)
 

@@ -753,6 +753,21 @@ int drs_net_get_dice(const drs_net_t* net, double* lam, double* alpha, double* b
  * (either pointer may be NULL); (1, 0) when never set. */
 int drs_net_set_hard_mining(drs_net_t* net, double keep, int min_keep);
 int drs_net_get_hard_mining(const drs_net_t* net, double* keep, int* min_keep);
+/* Lovasz-softmax term of drs_train_step's loss (opt-in; the section "Training level: Lovasz-softmax term" below states the rule): lam
+ * finite in [0, 64], lam == 0 (the default) switches it off -- no new launch, the step is the launches it was, bit for bit (the
+ * CLS_DICE path included when only the Dice term is on), and the bound buffers "lovasz_err", "region_grad", "lovasz_loss" and
+ * "lovasz_scratch" are not touched; anything else DRS_ERR_ARG, and the value in use stays.  With lam > 0 the step runs, in this order:
+ * the boundary-weight launch if that option is on; the classifier in its inference form into the bound buffer "logits" (ONE such
+ * launch, shared with the Dice and mining pre-passes); drs_patch_dice_coeffs if on; drs_patch_hard_weight if on;
+ * drs_patch_lovasz_grad(logits, "lovasz_err", labels, loss_mask if and only if DRS_USE_LOSS_MASK, ..., "dice_coef" if the Dice term
+ * is on else NULL, NULL, "region_grad", "lovasz_loss", "lovasz_scratch", ...); and the classifier as drs_classifier_loss_region with
+ * the pixel map, if any, and "region_grad".  All of it is accounted under the timing kind "classifier_loss".  The sums of "dice_loss"
+ * (if on) and of "lovasz_loss" are added into "scalars"[0] before its all-reduce: it is then the cross-entropy part (whatever form is
+ * active, mined or not) + L_dice (if on) + L_lov; the term itself is never mined or weighted.  No collective, event or stream is
+ * added.  drs_forward and drs_forward_staged have no loss and ignore it.  drs_net_get_lovasz: the value in use (the pointer may be
+ * NULL); 0 when never set. */
+int drs_net_set_lovasz(drs_net_t* net, double lam);
+int drs_net_get_lovasz(const drs_net_t* net, double* lam);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
@@ -954,6 +969,74 @@ int drs_dice_loss_add(const double* patch_loss, int B, double* loss_sum, void* s
 int drs_patch_hard_weight(const float* logits, float* ce, const unsigned char* labels, const unsigned char* loss_mask, int B, int S,
                           int K, double keep, int min_keep, const float* pixel_weight_in, float* weight_out, int* kept_out,
                           void* stream);
+
+/* ==================================================================================================================
+ * Training level: Lovasz-softmax term (opt-in; csrc/lovasz.hip, csrc/pointwise.hip).  The convex surrogate of the
+ * Jaccard loss itself (Berman, Triki, Blaschko, The Lovasz-softmax loss, CVPR 2018; the paper's classes = 'present'), per PATCH, so
+ * that the loss stays a sum over patches: a sharded batch gives the single-rank loss and gradient with no collective.  NORMATIVE: this
+ * text and the numpy statement tests/lovasz_ref.py.
+ * Option: lam finite in (0, 64].
+ * "In the loss" means what it means for the cross-entropy: loss_mask set where one is given, and label < K.
+ * Every quantity is per patch b, over its n_b in-loss pixels only.
+ *     Error key of class c, fp32 from the fp32 logits: mx = the maximum logit, ex_k = expf(lg_k - mx), se = sum of ex_k in ascending k;
+ *         at a pixel with y = c: e_c = (sum_{k != c} ex_k, ascending k) / se  (1 - p_c, never formed by subtraction);
+ *         at a pixel with y != c: e_c = ex_c / se.  A true division; 0 <= e <= 1, so a key orders as its bit pattern does.
+ *     N_c = #{y = c}; class c is PRESENT in the patch when N_c > 0; C_b = the number of present classes.  Absent classes contribute
+ *         nothing.
+ *     Order, for a present class: the in-loss pixels by e_c descending, ties towards the lower pixel index (a total order, a pure
+ *         function of (key, index)).  For the pixel at 0-based position r: F = the foreground (y = c) pixels before it, Bg = the
+ *         background ones; U = N_c + Bg, I = N_c - F (integers).
+ *     Jaccard increment at that position, in fp64 from the exact integers: dJ = 1 / U at a foreground pixel, I / (U (U + 1)) at a
+ *         background one (J_r - J_{r-1} of the paper's Algorithm 1 without the cancellation; dJ >= 0, and a present class's
+ *         increments sum to 1).
+ *     Loss_bc = sum_r e_(r) dJ_r (fp64, fixed order)        L_lov = inv_n sum_b (lam n_b / C_b) sum_{c present} Loss_bc
+ *         (inv_n: the step's 1 / global pixels in the loss, as for the Dice term)
+ * Gradient (the order is a constant): g_c(p) = (lam n_b / C_b) (y_p == c ? -dJ : +dJ); 0 for an absent class and at a pixel not in the
+ *     loss; dL_lov / dlogit_k = inv_n P_k (g_k - sum_c P_c g_c), ADDED to the logit gradient of whatever cross-entropy form is active.
+ *     Class weights, the focal factor, the boundary map and the mining map do NOT weight the term, and it is not mined.  Logits,
+ *     arg-max and the confusion matrix are untouched.
+ *
+ * drs_lovasz_scratch_bytes: the scratch drs_patch_lovasz_grad needs for (B, S, K) (a multiple of 16, monotone in each argument; 0 for
+ *     arguments outside the ranges below): B (K + 1) doubles, and 16 bytes per (pixel, class) where a patch has more pixels than a
+ *     workgroup's LDS holds (S > 99).
+ * drs_patch_lovasz_grad: logits = float [B S S][K] (what the classifier's inference form writes) or NULL; err = float [B S S][K];
+ *     labels = uint8 [B S S]; loss_mask = uint8 [B S S] or NULL.
+ *     With logits, err is WRITTEN: the key at in-loss pixels for every class < K, +0 elsewhere.  With logits == NULL, err is the INPUT:
+ *     only in-loss entries are read, and they must be in [+0, 1] and not NaN -- device data, not checked; a violation gives an
+ *     unspecified order but no access outside the buffers.
+ *     dice_coef = float [B][K][2] (drs_patch_dice_coeffs' output, 8-byte aligned) or NULL.  Given, the Dice coefficient is folded in
+ *     with one fp32 add: grad_out[p][c] = (float)g_c(p) + (y_p == c ? G_in[b][c] : G_out[b][c]) at in-loss pixels, so that the
+ *     classifier needs one map form only.
+ *     grad_out = float [B S S][K]: g evaluated in fp64 as ((lam n_b) / C_b) dJ and rounded once; exactly +0 at pixels not in the loss;
+ *     at absent classes +0 plus the Dice part, if any.  rank_out = uint32 [B S S][K] or NULL: the 0-based position r, 0xFFFFFFFF where
+ *     the pixel is not in the loss or the class is absent -- it exists so that a wrong order and a wrong coefficient can be told
+ *     apart.  patch_loss_out = double [B]: (lam n_b / C_b) sum_c Loss_bc, the classes in ascending order; 0 for n_b = 0.
+ *     One workgroup per (patch, class), which reads and writes its own patch only: an exact, stable least-significant-digit radix sort
+ *     over the key's bit pattern (four passes of 8 bits) carrying the pixel index and the foreground bit; histograms by integer LDS
+ *     atomics, positions by ballots and prefix scans in element order, F by a prefix count in sorted order; no floating-point atomics,
+ *     every fp64 sum in a fixed order: the same bits on every run and every rank.  Keys and payload stay in LDS up to 9856 pixels per
+ *     patch (S <= 99) and ping-pong through scratch above that; any S with B S S < 2^24.  A second, tiny launch joins the classes'
+ *     sums.  Scratch is never read before it is written.
+ *     Ranges, else DRS_ERR_ARG (nothing is launched): err, labels, grad_out, patch_loss_out not NULL; B, S >= 1, B S S < 2^24; K in
+ *     1..8; lam finite in (0, 64]; scratch not NULL, 8-byte aligned, scratch_bytes >= drs_lovasz_scratch_bytes(B, S, K); dice_coef
+ *     8-byte aligned.
+ * drs_classifier_loss_region: the arguments of drs_classifier_loss_pixel plus region_grad, DEVICE float [B S S][K] (4-byte aligned,
+ *     else DRS_ERR_ARG) or NULL.  With NULL, or with labels == NULL, it IS drs_classifier_loss_pixel: the same launches, every output
+ *     bit for bit.  Otherwise all three kernel forms add inv_n P_k (g_k - sum_c P_c g_c), g_c = region_grad[p][c], to the in-loss
+ *     pixels' logit gradients before gfeat, dw_partial and db_partial are formed -- the arithmetic of drs_classifier_loss_dice with
+ *     another source of g: a map that is the Dice coefficients expanded per pixel gives that entry point's outputs bit for bit.
+ *     loss_partial stays the cross-entropy sum.  The map is device data and is not checked.
+ * The step joins the patches' terms to the cross-entropy sum with drs_dice_loss_add. */
+size_t drs_lovasz_scratch_bytes(int B, int S, int K);
+int drs_patch_lovasz_grad(const float* logits, float* err, const unsigned char* labels, const unsigned char* loss_mask, int B, int S,
+                          int K, double lam, const float* dice_coef, unsigned int* rank_out, float* grad_out, double* patch_loss_out,
+                          void* scratch, size_t scratch_bytes, void* stream);
+int drs_classifier_loss_region(const float* feat, int B, int S, int P, int ld, int coff, int C, int K, const float* w,
+                               const float* bias, const unsigned char* labels, const unsigned char* loss_mask,
+                               const unsigned char* acc_mask, float inv_n, const float* class_weights, float focal_gamma,
+                               const float* pixel_weight, const float* region_grad, float* logits, unsigned char* pred, float* gfeat,
+                               int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
+                               void* stream);
 
 #ifdef __cplusplus
 }
