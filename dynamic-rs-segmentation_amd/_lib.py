@@ -94,6 +94,11 @@ SIGNATURES = {
     "drs_object_scratch_bytes": (_sz, [_i, _i]),
     "drs_object_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "drs_object_table": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    # ---- whole-map level: exact distance transform and surface-distance table (csrc/distance.hip)
+    "drs_distance_scratch_bytes": (_sz, [_i, _i]),
+    "drs_distance_transform": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),
+    "drs_surface_scratch_bytes": (_sz, [_i, _i]),
+    "drs_surface_histogram": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _sz, _p]),
     # ---- training level: boundary-weighted cross-entropy (csrc/boundary.hip, csrc/pointwise.hip)
     "drs_patch_boundary_weight": (_i, [_p, _p, _i, _i, _i, _d, _d, _p, _p, _p]),
     "drs_classifier_loss_pixel": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _p, _i, _i, _p, _p,

@@ -38,6 +38,11 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     a truth object and a predicted one match when their IoU exceeds 1/2 --: per class the truth / predicted / matched counts, detection
     precision, recall and F1, the mean IoU of the matched objects (SQ) and the panoptic quality PQ (loops.validate_test's
     object_scores)
+  + optionally, anywhere, `--surface-scores[=t0,t1,...]` (validate_test; any inference path, with or without --crf / --sieve): one
+    more line per map and for all maps with surface-distance scores from an exact, unbounded distance transform -- per class the
+    average symmetric surface distance, the Hausdorff distance at the 95th percentile and at the maximum, and the normalised surface
+    Dice at the tolerances given (pixels; 1 to 8 ascending integers in 1..255; the bare flag means 1,2,4,8) (loops.validate_test's
+    surface_scores)
   + optionally, anywhere, in all three flavours, `--class-weights=balanced|median|w0,w1,...` (training): per-class weights of the
     cross-entropy, from the training labels' pixel counts or as given, one per class (loops.train's class_weights)
   + optionally, anywhere, in all three flavours, `--focal-gamma=G` (training; with or without --class-weights): the focusing parameter
@@ -278,6 +283,18 @@ def parse_object_scores(argv):
         bare=P.OBJECT_CONNECTIVITY)
 
 
+SURFACE_SCORES_FLAG = "--surface-scores"
+
+
+def parse_surface_scores(argv):
+    """isprs flavour: the optional `--surface-scores[=t0,t1,...]` (anywhere in argv; validate_test, which main checks).  Returns (argv
+    without the flag, tuple of tolerances; patches.parse_surface_scores) -- patches.SURFACE_DEFAULT for the bare flag --, or (argv
+    unchanged, None) without it.  A malformed or invalid list, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, SURFACE_SCORES_FLAG, lambda a, v: _or_expected(
+        P.parse_surface_scores, a, v, "%s or %s=t0,t1,... (1 to %d ascending integers in 1..%d, such as 1,2,4,8)"
+        % (SURFACE_SCORES_FLAG, SURFACE_SCORES_FLAG, P.SURFACE_MAX_TOLERANCES, P.SURFACE_MAX_TOLERANCE)), bare=P.SURFACE_DEFAULT)
+
+
 CLASS_WEIGHTS_FLAG = "--class-weights"
 
 
@@ -430,6 +447,7 @@ def main(argv=None, device=None, comm=None):
         argv, boundary = parse_boundary_scores(argv)
         argv, sieve = parse_sieve(argv, 6)
         argv, objects = parse_object_scores(argv)
+        argv, surface = parse_surface_scores(argv)
         argv, class_weights = parse_class_weights(argv, 6)
         argv, focal_gamma = parse_focal_gamma(argv)
         argv, boundary_weight = parse_boundary_weight(argv)
@@ -469,6 +487,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(SIEVE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if objects is not None and argv[16] != "validate_test":
         sys.exit(OBJECT_SCORES_FLAG + " applies to the validate_test process only")
+    if surface is not None and argv[16] != "validate_test":
+        sys.exit(SURFACE_SCORES_FLAG + " applies to the validate_test process only")
     if class_weights is not None and argv[16] != "training":
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the training process only")
     if focal_gamma is not None and argv[16] != "training":
@@ -556,6 +576,7 @@ def main(argv=None, device=None, comm=None):
     boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
     sieve_kw = {} if sieve is None else dict(sieve=sieve)
     objects_kw = {} if objects is None else dict(object_scores=objects)
+    surface_kw = {} if surface is None else dict(surface_scores=surface)
     if process == "validate_test":
         crop = (loops.select_best_patch_size(distribution_type, values, patch_acc_loss, patch_occur, update_type, debug=True)
                 if sized else int(values[0]))
@@ -570,7 +591,7 @@ def main(argv=None, device=None, comm=None):
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
                                    step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                   **boundary_kw, **sieve_kw, **objects_kw)
+                                   **boundary_kw, **sieve_kw, **objects_kw, **surface_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,

@@ -1515,6 +1515,81 @@ def _objects_str(connectivity, o):
             " SQ= " + "{:.6f}".format(o["all"]["sq"]) + " PQ= " + "{:.6f}".format(o["all"]["pq"]))
 
 
+DT_MODES = {"class": 0, "not_class": 1, "contour": 2}          # DRS_DT_* of include/drs.h
+
+
+def _byte_map(name, what, m, h, w):
+    if m.dtype != torch.uint8 or m.numel() != h * w or not m.is_contiguous():
+        raise ValueError("%s: the %s must be a contiguous uint8 tensor of %d x %d elements" % (name, what, h, w))
+
+
+def distance_transform(map_dev, h, w, mode, cls, veil=None, veil_label=None, stream=None):
+    """The exact squared Euclidean distance transform of a uint8 device map [h][w] (drs_distance_transform; include/drs.h; DESIGN.md
+    8a.10): int32 device tensor [h, w], the squared distance of every pixel to the nearest site, 0x7fffffff everywhere without a site;
+    no window.  mode: 0 / "class" (sites: byte == cls), 1 / "not_class" (byte != cls), 2 / "contour" (byte == cls with a 4-neighbour
+    inside the map of another byte).  veil (a uint8 device map [h][w]) with veil_label: the byte read is veil_label wherever the veil
+    carries it.  h, w <= 32768, h w <= 2^28.  stream: a raw stream handle (default: torch's current stream on the map's device)."""
+    from . import _lib
+    mode = DT_MODES.get(mode, mode)
+    if isinstance(mode, bool) or mode not in (0, 1, 2):
+        raise ValueError("distance_transform: mode %r, expected 0..2 or one of %s" % (mode, ", ".join(sorted(DT_MODES))))
+    _byte_map("distance_transform", "map", map_dev, h, w)
+    if (veil is None) != (veil_label is None):
+        raise ValueError("distance_transform: veil and veil_label go together")
+    if veil is not None:
+        _byte_map("distance_transform", "veil", veil, h, w)
+    need = _lib.query("drs_distance_scratch_bytes", int(h), int(w))
+    if need == 0:
+        raise ValueError("distance_transform: a map of %d x %d is outside 1 <= h, w <= 32768, h w <= 2^28" % (h, w))
+    dev = map_dev.device
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        d2 = torch.empty((h, w), dtype=torch.int32, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call("drs_distance_transform", map_dev.data_ptr(), None if veil is None else veil.data_ptr(),
+                  0 if veil_label is None else int(veil_label), int(h), int(w), mode, int(cls), d2.data_ptr(), scratch.data_ptr(), need, st)
+    return d2
+
+
+def surface_histogram(truth_dev, pred_dev, h, w, K, ignore_label, table=None, stream=None):
+    """The surface-distance table of one (truth, prediction) pair of uint8 device maps [h][w] (drs_surface_histogram; include/drs.h;
+    DESIGN.md 8a.10): int64 device tensor [2][K][metrics.SURFACE_BINS + 2]: per direction (0: the truth's contour pixels against the
+    prediction's contour, 1: the reverse) and class, the pixels by ceil(4 distance), the sum of floor(1024 distance) and the pixels
+    whose counterpart contour is empty.  `table` (such a tensor) is ADDED to and returned, so the maps of a split accumulate; without
+    it a zeroed one is made.  ignore_label: None or -1 for none.  stream: a raw stream handle (default: torch's current stream on the
+    maps' device); everything is enqueued there and nothing waits.  metrics.surface_scores turns the table into scores."""
+    from . import _lib
+    _byte_map("surface_histogram", "truth", truth_dev, h, w)
+    _byte_map("surface_histogram", "prediction", pred_dev, h, w)
+    shape = (2, K, MT.SURFACE_BINS + 2)
+    if table is not None and (table.dtype != torch.int64 or tuple(table.shape) != shape or not table.is_contiguous()):
+        raise ValueError("surface_histogram: table must be a contiguous int64 tensor [2][%d][%d]" % (K, shape[2]))
+    need = _lib.query("drs_surface_scratch_bytes", int(h), int(w))
+    if need == 0:
+        raise ValueError("surface_histogram: a map of %d x %d is outside 1 <= h, w <= 32768, h w <= 2^28" % (h, w))
+    dev = truth_dev.device
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if table is None:
+            table = torch.zeros(shape, dtype=torch.int64, device=dev)
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.call("drs_surface_histogram", truth_dev.data_ptr(), pred_dev.data_ptr(), int(h), int(w), int(K),
+                  -1 if ignore_label is None else int(ignore_label), table.data_ptr(), scratch.data_ptr(), need, st)
+    return table
+
+
+def _surface_str(s):
+    """the Surface line's text from metrics.surface_scores' dict"""
+    ints = lambda v: "[" + " ".join(str(int(x)) for x in v) + "]"
+    vals = lambda v: "[" + " ".join("{:.6f}".format(x) for x in v) + "]"
+    return ("Surface tau= " + " ".join(str(t) for t in s["tolerances"]) + " Truth Contour= " + ints(s["n_truth"]) +
+            " Predicted Contour= " + ints(s["n_pred"]) + " Unsited= " + ints(s["unsited_truth"]) + " " + ints(s["unsited_pred"]) +
+            " ASSD= " + vals(s["assd"]) + " HD95= " + vals(s["hd95"]) + " Saturated= " + ints(s["saturated"]) +
+            " HD100= " + vals(s["hd100"]) + " NSD= " + " ".join(vals(row) for row in s["nsd"]) +
+            " Mean ASSD= " + "{:.6f}".format(s["mean_assd"]) + " Mean HD95= " + "{:.6f}".format(s["mean_hd95"]) +
+            " Mean NSD= " + " ".join("{:.6f}".format(v) for v in s["mean_nsd"]))
+
+
 FIT_RESIDENT_BYTES = 32 << 30       # default cap on the accumulators fit_temperature keeps on the device
 
 
@@ -1566,7 +1641,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
                   dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None,
-                  boundary_scores=None, sieve=None, object_scores=None):
+                  boundary_scores=None, sieve=None, surface_scores=None, object_scores=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1612,7 +1687,16 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     Recall= [..] F1= [..] SQ= [..] PQ= [..] Mean F1= ... Mean SQ= ... Mean PQ= ... All Objects F1= ... SQ= ... PQ= ...` follows the
     map's other lines, and one for all maps, from the summed table, the all-maps lines.  Returns (all-maps confusion matrix, label
     maps, extra) with extra["objects"] = metrics.object_scores of the all-maps table, plus "connectivity", "table" (the int64 numpy
-    table [K][4][32]) and "per_map": [the same per map, each with its "table"].  Without object_scores nothing changes."""
+    table [K][4][32]) and "per_map": [the same per map, each with its "table"].  Without object_scores nothing changes.
+    surface_scores (opt-in; any inference path; a tuple of tolerances in pixels, patches.check_surface_tolerances, e.g.
+    patches.SURFACE_DEFAULT): surface-distance scores of every map and of all maps: per map, one surface_histogram
+    call on the labels and the map that drs_confusion scored -- the sieved refined map with crf / sieve --, with the ignore label the
+    boundary scores pass; the distances are exact and unbounded.  Every rank scores the whole map itself and gets the same bits; no
+    collective is added.  One line `---- Iter N -- Test Map M: Surface tau= ... Truth Contour= [..] Predicted Contour= [..] Unsited=
+    [..] [..] ASSD= [..] HD95= [..] Saturated= [..] HD100= [..] NSD= [..] ... Mean ASSD= ... Mean HD95= ... Mean NSD= ...` follows the
+    map's other lines, and one for all maps, from the summed table, the all-maps lines.  Returns (all-maps confusion matrix, label
+    maps, extra) with extra["surface"] = metrics.surface_scores of the all-maps table, plus "table" (the int64 numpy table [2][K][4098])
+    and "per_map": [the same per map, each with its "table"].  Without surface_scores nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
@@ -1622,6 +1706,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     bdist = None if boundary_scores is None else P.check_boundary_distances(boundary_scores)
     sieve = None if sieve is None else P.check_sieve(sieve)
     oconn = None if object_scores is None else P.check_object_scores(object_scores)
+    stol = None if surface_scores is None else P.check_surface_tolerances(surface_scores)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
     kinds = None
     if score_maps is not None:
@@ -1645,6 +1730,9 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     if oconn is not None:
         all_otable = np.zeros((K, 4, 32), dtype=np.int64)
         object_list = []
+    if stol is not None:
+        all_stable = np.zeros((2, K, MT.SURFACE_BINS + 2), dtype=np.int64)
+        surface_list = []
     for k in range(len(testing_data)):
         pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
@@ -1697,6 +1785,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             object_list.append(dict(MT.object_scores(otable), table=otable))
             if comm.rank == 0:
                 print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _objects_str(oconn, object_list[-1]))
+        if stol is not None:
+            stable = surface_histogram(lab, pred, h, w, K, ignore_label, stream=net._stream()).cpu().numpy()
+            all_stable += stable
+            surface_list.append(dict(MT.surface_scores(stable, stol), table=stable))
+            if comm.rank == 0:
+                print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _surface_str(surface_list[-1]))
     total, oa, na = MT.overall_and_normalized(all_cm)
     if comm.rank == 0:
         print("---- Iter " + str(step) +
@@ -1738,7 +1832,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _objects_str(oconn, obj))
         extra = dict(extra if kinds is not None or bdist is not None or sieve is not None else {}, objects=obj)
-    if kinds is not None or bdist is not None or sieve is not None or oconn is not None:
+    if stol is not None:
+        srf = dict(MT.surface_scores(all_stable, stol), table=all_stable, per_map=surface_list)
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _surface_str(srf))
+        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None or oconn is not None else {}, surface=srf)
+    if kinds is not None or bdist is not None or sieve is not None or oconn is not None or stol is not None:
         return all_cm, maps, extra
     return all_cm, maps
 

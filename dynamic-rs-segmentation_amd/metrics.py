@@ -134,6 +134,59 @@ def object_scores(table):
     return out
 
 
+SURFACE_BINS = 4096          # DRS_SURFACE_BINS of include/drs.h: quarter-pixel bins, the last one open
+
+
+def surface_scores(table, tolerances):
+    """Surface-distance scores from the table of drs_surface_histogram (include/drs.h): table [2][K][BINS + 2]
+    integers; direction 0 walks the contour pixels of a class in the truth with their distance d to the class's contour in the
+    prediction, direction 1 the reverse.  Of [dir][c]: entry b < BINS counts the pixels with ceil(4 d) = b (the last bin: everything
+    from (BINS - 1) / 4 pixels on), entry BINS is the sum of floor(1024 d), entry BINS + 1 the pixels whose counterpart contour is
+    empty (unsited).  Per class, in fp64, with n_dir the sited pixels of a direction:
+      assd   = (sum_0 + sum_1) / 1024 / (n_0 + n_1)                  average symmetric surface distance, in pixels
+      hd95   = max over the directions of b / 4, b the bin that holds the ceil(0.95 n_dir)-th smallest distance: the Hausdorff
+               distance at the 95th percentile, rounded UP to a quarter pixel; nan when either direction has no sited pixel;
+               `saturated` says that b is the last bin: the value is then a lower bound
+      hd100  = likewise with the largest distance
+      nsd[i] = (pixels of both directions with b <= 4 tolerances[i]) / (all walked pixels of both directions, unsited included): the
+               normalised surface Dice at that tolerance, exact for integer tolerances
+    A score a class does not have is nan; a mean runs over the classes that have it (nan without any).  Returns {"tolerances",
+    "n_truth", "n_pred" (the contour pixels, unsited included), "unsited_truth", "unsited_pred" (K ints each), "assd", "hd95", "hd100"
+    (K values), "saturated" (K bools), "nsd" ([len(tolerances)][K]), "mean_assd", "mean_hd95", "mean_hd100", "mean_nsd" (one per
+    tolerance)}.  A table of another shape, of a non-integer dtype or with a negative entry raises ValueError."""
+    t = np.asarray(table)
+    B = SURFACE_BINS
+    if t.ndim != 3 or t.shape[0] != 2 or t.shape[1] < 1 or t.shape[2] != B + 2 or not np.issubdtype(t.dtype, np.integer) or np.any(t < 0):
+        raise ValueError("surface table: expected [2][K][%d] non-negative integers, not %s of shape %r" % (B + 2, t.dtype, t.shape))
+    t = t.astype(np.int64)
+    K = t.shape[1]
+    bins, fsum, unsited = t[:, :, :B], t[:, :, B], t[:, :, B + 1]
+    cum = np.cumsum(bins, axis=2)
+    n = cum[:, :, -1]                                                     # [2][K] sited pixels
+    walked = n + unsited
+    both = n.sum(axis=0)
+    nan = np.full(K, np.nan)
+    assd = np.where(both > 0, fsum.sum(axis=0) / 1024.0 / np.where(both > 0, both, 1), nan)
+
+    def quantile_bin(rank):
+        """[2][K]: the first bin whose cumulative count reaches rank (>= 1 where n > 0)"""
+        return np.array([[int(np.searchsorted(cum[d, c], rank[d, c], side="left")) if n[d, c] > 0 else 0 for c in range(K)]
+                         for d in range(2)])
+    have = (n > 0).all(axis=0)
+    b95, b100 = quantile_bin((95 * n + 99) // 100).max(axis=0), quantile_bin(n).max(axis=0)
+    out = {"tolerances": tuple(int(v) for v in tolerances), "n_truth": walked[0], "n_pred": walked[1], "unsited_truth": unsited[0],
+           "unsited_pred": unsited[1], "assd": assd, "hd95": np.where(have, b95 / 4.0, nan), "hd100": np.where(have, b100 / 4.0, nan),
+           "saturated": have & (b95 == B - 1)}
+    total = walked.sum(axis=0)
+    out["nsd"] = np.array([np.where(total > 0, cum[:, :, min(4 * int(tol), B - 1)].sum(axis=0) / np.where(total > 0, total, 1), nan)
+                           for tol in tolerances]).reshape(len(out["tolerances"]), K)
+    mean = lambda v: float(v[~np.isnan(v)].mean()) if (~np.isnan(v)).any() else float("nan")
+    for key in ("assd", "hd95", "hd100"):
+        out["mean_" + key] = mean(out[key])
+    out["mean_nsd"] = [mean(row) for row in out["nsd"]]
+    return out
+
+
 def cohen_kappa(cm):
     """sklearn cohen_kappa_score(y_true, y_pred) from the confusion matrix."""
     cm = np.asarray(cm, dtype=np.float64)

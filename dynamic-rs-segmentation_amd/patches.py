@@ -769,6 +769,39 @@ def parse_object_scores(text):
     return check_object_scores(int(text))
 
 
+# ------------------------------------------------------------------- surface-distance scores of validation
+SURFACE_DEFAULT = (1, 2, 4, 8)
+SURFACE_MAX_TOLERANCES, SURFACE_MAX_TOLERANCE = 8, 255
+
+
+def check_surface_tolerances(v):
+    """The tolerances of the normalised surface Dice, in pixels, as a tuple of ints: 1 to 8 integers in 1..255, strictly ascending.
+    Anything else raises ValueError naming the offending value."""
+    form = "1 to %d integers in 1..%d, strictly ascending" % (SURFACE_MAX_TOLERANCES, SURFACE_MAX_TOLERANCE)
+    if isinstance(v, (str, bytes)) or not isinstance(v, (tuple, list, np.ndarray)) or not 1 <= len(v) <= SURFACE_MAX_TOLERANCES:
+        raise ValueError("surface tolerances %r: expected %s" % (v, form))
+    out = []
+    for d in v:
+        if not isinstance(d, (int, np.integer)) or isinstance(d, bool) or not 1 <= int(d) <= SURFACE_MAX_TOLERANCE:
+            raise ValueError("surface tolerance %r of %r: expected %s" % (d, tuple(v), form))
+        if out and int(d) <= out[-1]:
+            raise ValueError("surface tolerance %r of %r does not exceed the one before it: expected %s" % (d, tuple(v), form))
+        out.append(int(d))
+    return tuple(out)
+
+
+def parse_surface_scores(text):
+    """The value of the command line's --surface-scores option: "1,2,4,8" as a tuple of ints (check_surface_tolerances).  An empty
+    value, blanks, or anything that is not a plain decimal integer raise ValueError."""
+    parts = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else []
+    for t in parts:
+        if not (t.isascii() and t.isdigit()):
+            raise ValueError("surface tolerance %r of %r: expected integers, comma-separated (e.g. 1,2,4,8)" % (t, text))
+    if not parts:
+        raise ValueError("surface tolerances %r: expected integers, comma-separated (e.g. 1,2,4,8)" % (text,))
+    return check_surface_tolerances([int(t) for t in parts])
+
+
 # ---------------------------------------------------------------------------------------- augmentation draws
 def rotation_params(angle_deg, S):
     """(m00, m01, m10, m11, off0, off1) that scipy.ndimage.rotate(reshape=False) hands to its

@@ -853,6 +853,50 @@ int drs_object_match(const unsigned char* truth, const unsigned char* pred, cons
 int drs_object_table(const unsigned char* truth, const int* tlabel, const unsigned int* tsize, const unsigned char* pred, const int* plabel,
                      const unsigned int* psize, const int* match, const unsigned int* inter, const unsigned int* cover, int h, int w, int K,
                      int ignore_label, unsigned long long* table, void* stream);
+/* Exact Euclidean distance transform of a byte map, and the surface-distance table of a (truth, prediction) pair of label maps on top
+ * of it (opt-in; csrc/distance.hip): what the Hausdorff distance at the 95th percentile (HD95), the average symmetric
+ * surface distance (ASSD) and the normalised surface Dice at a tolerance (NSD; Nikolov et al. 2018) are sums of.  Unlike
+ * drs_boundary_*, whose field is searched inside a window of at most 33 x 33, the transform is UNBOUNDED: a contour 170 pixels off
+ * scores as 170 pixels off.  NORMATIVE: this text and the numpy statement tests/surface_ref.py.  Everything is integer arithmetic;
+ * nothing is rounded except where stated.
+ * Byte read through the veil: b[p] = veil_label where veil != NULL and veil[p] == veil_label, else b[p] = map[p]; veil == NULL: no veil.
+ * Sites, by mode: DRS_DT_CLASS: b[p] == cls.  DRS_DT_NOT_CLASS: b[p] != cls.  DRS_DT_CONTOUR: b[p] == cls and at least one of p's four
+ *     edge neighbours INSIDE THE MAP has b[q] != cls.  The edge of the map is not a boundary and a byte is just a byte, as in
+ *     drs_boundary_*.
+ * Distance: d2[y][x] = min over the sites q of (y - qy)^2 + (x - qx)^2, uint32 [h][w] on the device; DRS_DT_INF everywhere when there
+ *     is no site.  Exact, with no window: h, w <= 32768 keeps d2 < 2^31.
+ * Surface table: table = [2][K][DRS_SURFACE_BINS + 2] 64-bit device counters, ADDED to (integer atomics: exact and order-free), so
+ *     the maps of a run accumulate.  pred' = pred veiled by truth at ignore_label (no veil when ignore_label == -1).  For every
+ *     class c < K, c != ignore_label: S_t(c) = the DRS_DT_CONTOUR set of c in truth, S_p(c) = that of c in pred'.  Direction 0 walks
+ *     the pixels of S_t(c) with their squared distance D to S_p(c); direction 1 walks S_p(c) with D to S_t(c).  Per walked pixel:
+ *         the counterpart set is empty:  table[dir][c][BINS + 1] += 1                                       (unsited)
+ *         otherwise:                     table[dir][c][min(b, BINS - 1)] += 1  and  table[dir][c][BINS] += f
+ *     with b = the smallest integer with 16 D <= b^2 (= ceil(4 d): for an integer tolerance tau, d <= tau iff b <= 4 tau, exactly) and
+ *     f = floor(sqrt(D 2^20)) (= floor(1024 d); the operand is below 2^51, a double square root and an integer fix-up give it
+ *     exactly).  Bytes >= K in either map are just bytes: they draw contours for their neighbours and have no row of their own.
+ * Scores (the host's, metrics.surface_scores, fp64): ASSD = (f of both directions) / 1024 / (sited pixels of both); HD95 = the larger
+ *     of the two directions' 95th-percentile bins / 4, rounded UP to a quarter pixel, saturating at (BINS - 1) / 4; NSD at tau =
+ *     (pixels of both directions with b <= 4 tau) / (all walked pixels, unsited included).
+ *
+ * drs_distance_scratch_bytes / drs_surface_scratch_bytes: bytes of scratch for an h x w map (about 10 h w and 31 h w); 0 outside the
+ *     ranges.  Every byte of scratch and of d2 that a call reads was written by the same call: results do not depend on what they held.
+ * drs_distance_transform: three launches (sites and strip ends down the columns; the distance along the column; the lower envelope of
+ *     the parabolas along the rows, Meijster et al. 2000, exact integer separators, columns without a site skipped).
+ * drs_surface_histogram: the contours of both maps once, then per class the two transforms in shared launches and one gather;
+ *     classes with an empty contour set in either map run no transform (the launches leave at once).  No entry point synchronises.
+ * Ranges, else DRS_ERR_ARG (nothing is launched): map / truth, pred, d2, table and scratch not NULL; 1 <= h, w <= 32768, h w <= 2^28;
+ * mode 0..2; cls 0..255; veil_label 0..255 when veil is given; scratch_bytes >= the matching query; 2 <= K <= 8; -1 <= ignore_label <= 255. */
+#define DRS_DT_CLASS 0
+#define DRS_DT_NOT_CLASS 1
+#define DRS_DT_CONTOUR 2
+#define DRS_DT_INF 0x7fffffff
+#define DRS_SURFACE_BINS 4096
+size_t drs_distance_scratch_bytes(int h, int w);
+int drs_distance_transform(const unsigned char* map, const unsigned char* veil, int veil_label, int h, int w, int mode, int cls,
+                           unsigned int* d2, void* scratch, size_t scratch_bytes, void* stream);
+size_t drs_surface_scratch_bytes(int h, int w);
+int drs_surface_histogram(const unsigned char* truth, const unsigned char* pred, int h, int w, int K, int ignore_label,
+                          unsigned long long* table, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ==================================================================================================================
  * Training level: boundary-weighted cross-entropy (opt-in; csrc/boundary.hip, csrc/pointwise.hip).  A per-pixel weight
