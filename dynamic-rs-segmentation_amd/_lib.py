@@ -115,6 +115,9 @@ SIGNATURES = {
     "drs_patch_lovasz_grad": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _p, _p, _p, _p, _p, _sz, _p]),
     "drs_classifier_loss_region": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _f, _p, _p, _p, _p, _p, _i, _i, _p,
                                         _p, _p, _p, _p]),
+    # ---- training level: boundary (surface) loss (csrc/surface_loss.hip)
+    "drs_surface_loss_scratch_bytes": (_sz, [_i, _i, _i]),
+    "drs_patch_surface_loss": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _p, _i, _p, _p, _p, _p, _sz, _p]),
     # ---- step level (csrc/engine.hip)
     "drs_net_create": (_i, [C.c_char_p, _i, _i, _f, _i, _i, _i, _f, C.POINTER(_p)]),
     "drs_net_destroy": (None, [_p]),
@@ -163,6 +166,8 @@ SIGNATURES = {
     "drs_net_get_hard_mining": (_i, [_p, C.POINTER(_d), C.POINTER(_i)]),
     "drs_net_set_lovasz": (_i, [_p, _d]),
     "drs_net_get_lovasz": (_i, [_p, C.POINTER(_d)]),
+    "drs_net_set_surface_loss": (_i, [_p, _d, _d]),
+    "drs_net_get_surface_loss": (_i, [_p, C.POINTER(_d), C.POINTER(_d)]),
     "drs_net_timing": (_i, [_p, _i]),
     "drs_net_num_timing_kinds": (_i, []),
     "drs_net_timing_summary": (_i, [_p, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_d), C.POINTER(_d)]),

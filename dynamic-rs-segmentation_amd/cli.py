@@ -58,6 +58,11 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
   + optionally, anywhere, in all three flavours, `--lovasz-weight=lam` (training; beside --class-weights, --focal-gamma,
     --boundary-weight and --hard-mining, which do not weight it, and --dice-weight): lam times the Lovasz-softmax loss per patch, over
     the classes present in it, is added to the loss; lam in [0, 64] (0: off) (loops.train's lovasz)
+  + optionally, anywhere, in all three flavours, `--surface-loss=lam[,clip]` (training; beside --class-weights, --focal-gamma,
+    --boundary-weight and --hard-mining, which do not weight it, --dice-weight and --lovasz-weight): the boundary (surface) loss per
+    patch -- the softmax probabilities against lam times the signed Euclidean distance maps of the patch's labels, clipped to +-clip
+    pixels when clip > 0 -- is added to the loss; lam in [0, 64] (0: off), clip 0 (none, the default) or in [1, 32768]
+    (loops.train's surface_loss)
   + optionally, anywhere, in all three flavours, `--hard-mining=keep[,min_keep]` (training; beside --class-weights, --focal-gamma,
     --boundary-weight, which shape the terms it selects among, and --dice-weight, which it does not touch): online hard example
     mining -- the cross-entropy runs over the max(ceil(keep n), min_keep) of a patch's n in-loss pixels with the largest plain
@@ -371,6 +376,18 @@ def parse_lovasz(argv):
         P.parse_lovasz, a, v, "%s=lam (lam in [0, %g])" % (LOVASZ_FLAG, P.MAX_LOVASZ_LAMBDA)))
 
 
+SURFACE_LOSS_FLAG = "--surface-loss"
+
+
+def parse_surface_loss(argv):
+    """all flavours: the optional `--surface-loss=lam[,clip]` (anywhere in argv; training).  Returns (argv without the flag, (lam, clip)
+    with the default filled in), or (argv unchanged, None) without it.  A bare flag, a value outside the ranges of
+    patches.check_surface_loss, or the flag given twice, raises ValueError."""
+    return _take_flag(argv, SURFACE_LOSS_FLAG, lambda a, v: _or_expected(
+        P.parse_surface_loss, a, v, "%s=lam[,clip] (lam in [0, %g], clip 0 or in [1, %g])" % (
+            SURFACE_LOSS_FLAG, P.MAX_SURFACE_LAMBDA, P.MAX_SURFACE_CLIP)))
+
+
 SCALE_JITTER_FLAG = "--scale-jitter"
 
 
@@ -454,6 +471,7 @@ def main(argv=None, device=None, comm=None):
         argv, dice = parse_dice(argv)
         argv, hard_mining = parse_hard_mining(argv)
         argv, lovasz = parse_lovasz(argv)
+        argv, surface_loss = parse_surface_loss(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -501,6 +519,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(HARD_MINING_FLAG + " applies to the training process only")
     if lovasz is not None and argv[16] != "training":
         sys.exit(LOVASZ_FLAG + " applies to the training process only")
+    if surface_loss is not None and argv[16] != "training":
+        sys.exit(SURFACE_LOSS_FLAG + " applies to the training process only")
     if scale_jitter is not None and argv[16] != "training":
         sys.exit(SCALE_JITTER_FLAG + " applies to the training process only")
     if comm.rank == 0:
@@ -553,7 +573,8 @@ def main(argv=None, device=None, comm=None):
                            distribution_type, values, patch_acc_loss, patch_occur, patch_chosen_values, probs, resample_batch,
                            output_path, display_step, net_type, dataset, former_model_path, device=device, comm=comm,
                            class_weights=class_weights, focal_gamma=focal_gamma, scale_jitter=scale_jitter,
-                           boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz)
+                           boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz,
+                           surface_loss=surface_loss)
     from .net import DilatedNet
     step = loops.step_from_model_path(former_model_path)
     sized = distribution_type in ("multi_fixed", "uniform", "multinomial")
@@ -631,6 +652,7 @@ def main_coffee(argv=None, device=None, comm=None):
         argv, dice = parse_dice(argv)
         argv, hard_mining = parse_hard_mining(argv)
         argv, lovasz = parse_lovasz(argv)
+        argv, surface_loss = parse_surface_loss(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -650,7 +672,8 @@ def main_coffee(argv=None, device=None, comm=None):
                     int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=2,
                     side_names=("errorAcc_step_", "errorOccur_step_", "chosenValues_step_"), device=device, comm=comm,
                     quantize_f16=True, class_weights=class_weights, focal_gamma=focal_gamma,     # coffee:293: training patches pass through float16
-                    scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz)
+                    scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz,
+                           surface_loss=surface_loss)
 
 
 def main_contest(argv=None, device=None, comm=None):
@@ -665,6 +688,7 @@ def main_contest(argv=None, device=None, comm=None):
         argv, dice = parse_dice(argv)
         argv, hard_mining = parse_hard_mining(argv)
         argv, lovasz = parse_lovasz(argv)
+        argv, surface_loss = parse_surface_loss(argv)
         argv, scale_jitter = parse_scale_jitter(argv)
     except ValueError as e:
         sys.exit(str(e))
@@ -683,6 +707,8 @@ def main_contest(argv=None, device=None, comm=None):
         sys.exit(HARD_MINING_FLAG + " applies to the train operation only")
     if lovasz is not None and operation != "train":
         sys.exit(LOVASZ_FLAG + " applies to the train operation only")
+    if surface_loss is not None and operation != "train":
+        sys.exit(SURFACE_LOSS_FLAG + " applies to the train operation only")
     if scale_jitter is not None and operation != "train":
         sys.exit(SCALE_JITTER_FLAG + " applies to the train operation only")
     values = [int(i) for i in pv.split(",")]
@@ -702,7 +728,8 @@ def main_contest(argv=None, device=None, comm=None):
         return LI.train(train_x, train_y, test_x, test_y, cd, mean_full, std_full, output_path, current_model, float(lr), float(wd),
                         int(bs), int(niter), net_type, dist, update_type, acc, occ, chosen, probs, values, num_classes=7,
                         void_label=7, device=device, comm=comm, flavour="contest", class_weights=class_weights,
-                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz)
+                        focal_gamma=focal_gamma, scale_jitter=scale_jitter, boundary_weight=boundary_weight, dice=dice, hard_mining=hard_mining, lovasz=lovasz,
+                           surface_loss=surface_loss)
     if class_weights is not None:
         sys.exit(CLASS_WEIGHTS_FLAG + " applies to the train operation only")
     if operation == "test":

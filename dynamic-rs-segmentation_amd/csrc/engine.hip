@@ -143,6 +143,8 @@ struct Ptrs {
   bool ok = false;
   float *params, *grads, *momentum, *bn, *partial, *gxh, *gz[2], *slab, *w0pad, *conv_ws, *bwd_means, *act, *gpool, *se_scratch;
   float *dw_partial, *db_partial, *logits, *feat_act, *feat_gact, *pixel_weight, *dice_coef, *hard_ce, *lovasz_err, *region_grad;
+  double *surface_loss, *surface_scratch;
+  size_t surface_scratch_bytes;
   size_t conv_ws_floats;
   double *sums, *scalars, *colsum_scratch, *loss_partial, *l2_scratch, *dice_loss, *lovasz_loss, *lovasz_scratch;
   size_t lovasz_scratch_bytes;
@@ -199,6 +201,7 @@ struct drs_net {
   double hard_keep = 1.0;                   // hard example mining in the training loss (drs_net_set_hard_mining); keep == 1: off, no launch
   int hard_min_keep = 0;
   double lovasz_lam = 0.0;                  // Lovasz-softmax term of the training loss (drs_net_set_lovasz); lam == 0: off, no launch
+  double surface_lam = 0.0, surface_clip = 0.0;      // boundary (surface) loss of the training loss (drs_net_set_surface_loss); lam == 0: off, no launch
   int two_stream_mode;                      // -1 by the rule in train_step_impl, 0 never, 1 always (drs_net_set_two_streams)
   // per-slab (B, S) of the pooling call that last zeroed its halo (the halo of a slab one block owns stays zero)
   std::vector<long long> halo_ok;
@@ -440,6 +443,10 @@ void list_buffers(drs_net* n) {
   n->add_buf("lovasz_loss", B, F64);
   n->add_buf("lovasz_scratch", drs_lovasz_scratch_bytes(n->b_max, n->s_max, n->K) / 8, F64);
   n->add_buf("logits", M * n->K, F32);
+  // the boundary (surface) loss (drs_net_set_surface_loss): the patches' loss terms and the pre-pass's scratch (its map goes to
+  // "region_grad"); untouched while it is off
+  n->add_buf("surface_loss", B, F64);
+  n->add_buf("surface_scratch", drs_surface_loss_scratch_bytes(n->b_max, n->s_max, n->K) / 8, F64);
   n->add_buf("pred", M, U8);
   n->add_buf("conf", (size_t)n->K * n->K, I32);
   n->add_buf("labels", M, U8);
@@ -596,6 +603,8 @@ bool resolve(drs_net* n) {
   P.hard_ce = n->p<float>("hard_ce");
   P.lovasz_err = n->p<float>("lovasz_err"); P.region_grad = n->p<float>("region_grad"); P.lovasz_loss = n->p<double>("lovasz_loss");
   P.lovasz_scratch = n->p<double>("lovasz_scratch"); P.lovasz_scratch_bytes = drs_lovasz_scratch_bytes(n->b_max, n->s_max, n->K);
+  P.surface_loss = n->p<double>("surface_loss"); P.surface_scratch = n->p<double>("surface_scratch");
+  P.surface_scratch_bytes = drs_surface_loss_scratch_bytes(n->b_max, n->s_max, n->K);
   const Slab& f = n->slabs[n->feat];
   P.feat_act = n->p<float>("act:" + f.name); P.feat_gact = n->p<float>("gact:" + f.name);
   P.L.assign(n->layers.size(), LayerPtrs());
@@ -1179,6 +1188,26 @@ int drs_net_get_lovasz(const drs_net_t* n, double* lam) {
   return DRS_OK;
 }
 
+// Boundary (surface) loss of the training loss (drs_train_step only; include/drs.h, "Training level: boundary (surface) loss"): lam == 0
+// switches it off.  The step then runs the classifier in its inference form into "logits" (once, shared with the other pre-passes),
+// drs_patch_surface_loss over the labels and them into "region_grad" (added onto the Lovasz map when that term is on, else the Dice
+// coefficients folded in when that term is on), and the fused classifier as drs_classifier_loss_region; the patches' terms join
+// scalars[0] before its all-reduce.
+int drs_net_set_surface_loss(drs_net_t* n, double lam, double clip) {
+  if (!n || !std::isfinite(lam) || lam < 0.0 || lam > 64.0) return DRS_ERR_ARG;
+  if (!std::isfinite(clip) || !(clip == 0.0 || (clip >= 1.0 && clip <= 32768.0))) return DRS_ERR_ARG;
+  n->surface_lam = lam;
+  n->surface_clip = clip;
+  return DRS_OK;
+}
+
+int drs_net_get_surface_loss(const drs_net_t* n, double* lam, double* clip) {
+  if (!n) return DRS_ERR_ARG;
+  if (lam) *lam = n->surface_lam;
+  if (clip) *clip = n->surface_clip;
+  return DRS_OK;
+}
+
 int drs_net_timing(drs_net_t* n, int enable) {
   if (!n) return DRS_ERR_ARG;
   n->timing = enable != 0;
@@ -1390,6 +1419,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
   const bool dice = n->dice_lam != 0.0;
   const bool hard = n->hard_keep != 1.0;
   const bool lovasz = n->lovasz_lam != 0.0;
+  const bool surface = n->surface_lam != 0.0;
   {
     Timed t(n, st, K_CLS, M * n->c_last * 8.0);
     const bool bw = n->bw_a != 0.0;          // off: no launch, and drs_classifier_loss_pixel without a map is drs_classifier_loss_focal
@@ -1400,7 +1430,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     // classifier once in its inference form (logits only) for both, the coefficients of every (patch, class) and / or the weight map
     // that keeps the hardest pixels (times the boundary weight, in place), then the fused launch with them.  Off: none of it, and
     // drs_classifier_loss_dice without coefficients is drs_classifier_loss_pixel
-    if (dice || hard || lovasz)
+    if (dice || hard || lovasz || surface)
       DRS_TRY(drs_classifier_loss_pixel(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b, nullptr, nullptr,
                                         nullptr, 1.f, nullptr, 0.f, nullptr, P.logits, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr,
                                         nullptr, st));
@@ -1412,10 +1442,18 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
                                     n->hard_keep, n->hard_min_keep, bw ? P.pixel_weight : nullptr, P.pixel_weight, nullptr, st));
     // the Lovasz-softmax term needs the order of every class's errors in every patch: its pre-pass leaves one value per (pixel, class),
     // the Dice coefficients folded in, so the fused launch reads one map form only
-    if (lovasz) {
+    if (lovasz)
       DRS_TRY(drs_patch_lovasz_grad(P.logits, P.lovasz_err, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr, B, S, n->K,
                                     n->lovasz_lam, dice ? P.dice_coef : nullptr, nullptr, P.region_grad, P.lovasz_loss, P.lovasz_scratch,
                                     P.lovasz_scratch_bytes, st));
+    // the boundary (surface) loss needs the signed distance map of every (patch, class) of the step's labels: its pre-pass adds its
+    // map onto the Lovasz one, or writes it with the Dice coefficients folded in, so the fused launch still reads one map form
+    if (surface)
+      DRS_TRY(drs_patch_surface_loss(P.logits, P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
+                                     (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, B, S, n->K, n->surface_lam, n->surface_clip,
+                                     (dice && !lovasz) ? P.dice_coef : nullptr, lovasz ? 1 : 0, nullptr, P.region_grad, P.surface_loss,
+                                     P.surface_scratch, P.surface_scratch_bytes, st));
+    if (lovasz || surface) {
       DRS_TRY(drs_classifier_loss_region(P.feat_act, B, S, f.P, f.C, 0, n->c_last, n->K, params + n->cls_w, params + n->cls_b,
                                          P.labels, (flags & DRS_USE_LOSS_MASK) ? P.loss_mask : nullptr,
                                          (flags & DRS_USE_ACC_MASK) ? P.acc_mask : nullptr, (float)(1.0 / n_glob),
@@ -1441,6 +1479,7 @@ static int train_step_impl(drs_net_t* n, int B, int S, float lr0, int flags, dou
     DRS_TRY(drs_sum_f64(P.loss_partial, crow, scalars, s));
     if (dice) DRS_TRY(drs_dice_loss_add(P.dice_loss, B, scalars, s));      // (+ the patches' Dice terms: scalars[0] goes on to its all-reduce and 1 / n_glob as before)
     if (lovasz) DRS_TRY(drs_dice_loss_add(P.lovasz_loss, B, scalars, s));  // (+ the patches' Lovasz terms, likewise)
+    if (surface) DRS_TRY(drs_dice_loss_add(P.surface_loss, B, scalars, s));  // (+ the patches' boundary (surface) terms, likewise)
     DRS_TRY(drs_l2_loss(params, n->n_decay, P.l2_scratch, scalars + 1, s));
     return DRS_OK;
   };

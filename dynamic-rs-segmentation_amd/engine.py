@@ -107,8 +107,9 @@ class EngineNet(DilatedNet):
         self.mean_rstd = [b["mean_rstd%d" % i] for i in range(nl)]
         for n in ("sums", "partial", "gxh", "gz", "slab", "w0pad", "dw_partial", "db_partial", "loss_partial", "scalars", "logits", "pred", "conf",
                   "labels", "acc_mask", "loss_mask", "pixel_weight", "dice_coef", "dice_loss", "hard_ce", "lovasz_err",
-                  "region_grad", "lovasz_loss", "lovasz_scratch"):
+                  "region_grad", "lovasz_loss", "lovasz_scratch", "surface_scratch"):
             setattr(self, n, b[n])
+        self.surface_loss_terms = b["surface_loss"]          # (`surface_loss` is the option's property)
         self.acc_mask.fill_(1)
         self.loss_mask.fill_(1)
         # whole-image gates of overlap-tile inference (forward_staged): per SE block the fp64 sums of a sweep and the gate made of them
@@ -363,6 +364,18 @@ class EngineNet(DilatedNet):
         lam = C.c_double()
         _lib.call("drs_net_get_lovasz", self.h, C.byref(lam))
         return None if lam.value == 0.0 else float(lam.value)
+
+    def _surface_loss_changed(self):
+        """hand the pair to the library's net (drs_net_set_surface_loss: the step runs the distance pre-pass before its fused classifier)"""
+        lam, clip = self._surface_loss or (0.0, 0.0)
+        _lib.call("drs_net_set_surface_loss", self.h, float(lam), float(clip))
+
+    @property
+    def surface_loss(self):
+        """(lam, clip) the library's net holds (drs_net_get_surface_loss), or None when the term is off (lam == 0)"""
+        lam, clip = C.c_double(), C.c_double()
+        _lib.call("drs_net_get_surface_loss", self.h, C.byref(lam), C.byref(clip))
+        return None if lam.value == 0.0 else (float(lam.value), float(clip.value))
 
     def set_two_streams(self, mode):
         """the backward pass of a step on two streams: None / -1 = by the library's rule (small steps), 0 never, 1 always

@@ -226,10 +226,38 @@ def load_lovasz(net, former_model_path):
             print("Lovasz term (restored from " + path + "): " + _lovasz_str(net.lovasz))
 
 
+SURFACE_LOSS_SIDE = "surface_loss_step_"
+
+
+def _surface_loss_str(s):
+    return "lambda " + "{:.6g}".format(s[0]) + " clip " + ("{:.6g}".format(s[1]) if s[1] else "none")
+
+
+def save_surface_loss(net, output_path, step):
+    """the boundary (surface) loss of the training loss, when on, as the side file `surface_loss_step_<step>.npy` beside the size
+    scores: two float64 (lam, clip) (state of the run, not of the model, as the other options of the loss are)"""
+    s = getattr(net, "surface_loss", None)
+    if s is not None:
+        np.save(output_path + SURFACE_LOSS_SIDE + str(step) + ".npy", np.asarray(s, dtype=np.float64))
+
+
+def load_surface_loss(net, former_model_path):
+    """set the pair that save_surface_loss left beside `<dir>/model-<step>[.npz]`, if any: a resumed run trains the same loss"""
+    head, sep, _ = former_model_path.rpartition("model-")
+    if not sep or not hasattr(net, "set_surface_loss"):
+        return
+    path = head + SURFACE_LOSS_SIDE + str(step_from_model_path(former_model_path)) + ".npy"
+    if os.path.isfile(path):
+        lam, clip = np.load(path).tolist()
+        net.set_surface_loss((lam, clip))
+        if getattr(getattr(net, "comm", None), "rank", 0) == 0:
+            print("Surface loss (restored from " + path + "): " + _surface_loss_str(net.surface_loss))
+
+
 def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=None, patch_chosen_values=None):
     """saver.save(sess, output_path + 'model', global_step=step) + the three .npy side files (isprs:1798-1802) + the class weights,
-    the focal gamma, the boundary weight, the Dice term, the hard mining and the Lovasz term of the loss when set (save_class_weights,
-    save_focal_gamma, save_boundary_weight, save_dice, save_hard_mining, save_lovasz)."""
+    the focal gamma, the boundary weight, the Dice term, the hard mining, the Lovasz term and the surface loss of the loss when set
+    (save_class_weights, save_focal_gamma, save_boundary_weight, save_dice, save_hard_mining, save_lovasz, save_surface_loss)."""
     np.savez(output_path + "model-" + str(step) + ".npz", **net.state_dict())
     save_class_weights(net, output_path, step)
     save_focal_gamma(net, output_path, step)
@@ -237,6 +265,7 @@ def save_checkpoint(net, output_path, step, patch_acc_loss=None, patch_occur=Non
     save_dice(net, output_path, step)
     save_hard_mining(net, output_path, step)
     save_lovasz(net, output_path, step)
+    save_surface_loss(net, output_path, step)
     if patch_acc_loss is not None:
         np.save(output_path + "patch_acc_loss_step_" + str(step) + ".npy", patch_acc_loss)
         np.save(output_path + "patch_occur_step_" + str(step) + ".npy", patch_occur)
@@ -261,6 +290,7 @@ def load_checkpoint(net, former_model_path):
     load_dice(net, former_model_path)
     load_hard_mining(net, former_model_path)
     load_lovasz(net, former_model_path)
+    load_surface_loss(net, former_model_path)
     print(BatchColors.OKBLUE + "Model restored from " + former_model_path + BatchColors.ENDC)
 
 
@@ -408,6 +438,61 @@ def setup_lovasz(net, lovasz, comm, say):
                                if on else "lambda 0 (off: the cross-entropy part alone)") +
             ("" if restored is None or restored == lam else " -- replacing the value restored from the checkpoint, " + _lovasz_str(restored)))
     return lam
+
+
+def setup_surface_loss(net, surface_loss, comm, say):
+    """The boundary (surface) loss of a training run (train's `surface_loss`; patches.check_surface_loss): every rank must hold the
+    same pair (lam, clip), asserted once over the ranks on their float64 bits.  Given, it replaces a pair restored from a checkpoint's
+    side file.  One log line names it; lam = 0 on a run that restored none is today's run and says nothing."""
+    s = P.check_surface_loss(surface_loss)
+    comm.agree([int(b) for b in np.asarray(s, dtype=np.float64).view(np.uint32)], "surface loss")
+    restored = net.surface_loss
+    net.set_surface_loss(s)
+    on = s[0] != 0.0
+    if on or restored is not None:
+        say("Surface loss: " + (_surface_loss_str(s) + " (the loss is the cross-entropy part + lambda times the mean over the pixels in the loss of the "
+                                                       "sum over classes of the softmax probability times the class's signed distance map of the patch's "
+                                                       "labels; class, focal, boundary and mining weights do not weight it)"
+                                if on else "lambda 0 (off: the cross-entropy part alone)") +
+            ("" if restored is None or restored == s else " -- replacing the pair restored from the checkpoint, " + _surface_loss_str(restored)))
+    return s
+
+
+def surface_loss_grad(logits, labels, lam, clip=0, loss_mask=None, valid=None, dice_coef=None):
+    """The per-(pixel, class) map drs_train_step makes of a step's labels and logits when the boundary (surface) loss is on (DESIGN.md
+    3g), for inspection: logits float32 [B, S, S, K] and labels uint8 [B, S, S] (tensors on the GPU, or anything np.asarray takes --
+    then on the current device), loss_mask and valid uint8 [B, S, S] or None, dice_coef float32 [B, K, 2] (drs_patch_dice_coeffs'
+    output, folded into the map) or None.  Returns (map float32 [B, S, S, K]: g_c(p), 0 where a pixel is not counted; phi2 int64
+    [B, S, S, K]: +D2 outside the class, -D2 inside, 0 where the class has no distance map in the patch or the pixel is not counted;
+    patch_loss float64 [B]) as tensors on that device.  One call of drs_patch_surface_loss."""
+    import torch
+    from . import _lib
+
+    def dev(x, dtype):
+        if x is None:
+            return None
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x))).cuda()
+        return x.to(dtype).contiguous()
+    lg, lab = dev(logits, torch.float32), dev(labels, torch.uint8)
+    if lg.dim() != 4 or lab.dim() != 3 or lg.shape[:3] != lab.shape or lab.shape[1] != lab.shape[2]:
+        raise ValueError("surface_loss_grad: logits [B, S, S, K] and labels [B, S, S] expected, got %r and %r" % (tuple(lg.shape), tuple(lab.shape)))
+    B, S, K = int(lab.shape[0]), int(lab.shape[1]), int(lg.shape[3])
+    lam, clip = P.check_surface_loss((lam, clip))
+    lm, va, dc = dev(loss_mask, torch.uint8), dev(valid, torch.uint8), dev(dice_coef, torch.float32)
+    if (lm is not None and lm.shape != lab.shape) or (va is not None and va.shape != lab.shape):
+        raise ValueError("surface_loss_grad: loss_mask and valid must have the shape of labels")
+    if dc is not None and tuple(dc.shape) != (B, K, 2):
+        raise ValueError("surface_loss_grad: dice_coef must be [B, K, 2]")
+    grad = torch.empty_like(lg)
+    phi2 = torch.empty(lg.shape, dtype=torch.int32, device=lab.device)
+    loss = torch.empty(B, dtype=torch.float64, device=lab.device)
+    nbytes = _lib.query("drs_surface_loss_scratch_bytes", B, S, K)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=lab.device)
+    with torch.cuda.device(lab.device):
+        _lib.call("drs_patch_surface_loss", lg.data_ptr(), lab.data_ptr(), None if lm is None else lm.data_ptr(),
+                  None if va is None else va.data_ptr(), B, S, K, lam, clip, None if dc is None else dc.data_ptr(), 0, phi2.data_ptr(),
+                  grad.data_ptr(), loss.data_ptr(), scratch.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+    return grad, phi2.to(torch.int64), loss
 
 
 def lovasz_grad(logits, labels, lam, loss_mask=None, dice_coef=None):
@@ -602,7 +687,7 @@ def train(training_data, training_labels, training_class_distribution, training_
           probs, resample_batch, output_path, display_step, net_type, dataset, former_model_path=None, *,
           num_classes=6, device="cuda:0", comm=None, noise="device", lr_decay_factor=0.5, tile_dtype=np.float64,
           loss_score_scaled_by_epoch=True, quiet_sizes=False, val_cache_dir=None, class_weights=None, focal_gamma=None,
-          scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None, lovasz=None):
+          scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None, lovasz=None, surface_loss=None):
     """isprs:1621-1851, same positional parameters.  Returns the trained DilatedNet.
     class_weights (opt-in; None = the reference's loss, bit for bit): "balanced" | "median" | K numbers -- per-class weights of the
     cross-entropy (setup_class_weights, DilatedNet.set_class_weights).  The loss this loop prints, and that feeds the size scores with
@@ -640,6 +725,14 @@ def train(training_data, training_labels, training_class_distribution, training_
     that feeds the size scores with update_type="loss", is then the cross-entropy part + the Dice term (if on) + the Lovasz term;
     accuracies, confusion matrices and validation do not change.  Given here, it replaces a value restored from a checkpoint's side
     file; None keeps that.  Under data parallelism nothing is added: the order is per patch, and the normaliser is unchanged.
+    surface_loss (opt-in; None or lam = 0 = today's run, bit for bit): (lam, clip) -- the boundary (surface) loss per patch, the
+    softmax probabilities against lam times the signed distance maps of the patch's labels (clipped to +-clip pixels when clip > 0),
+    is ADDED to the data term (setup_surface_loss, DilatedNet.set_surface_loss), beside whatever form the cross-entropy
+    has: class_weights, focal_gamma, boundary_weight and hard_mining do not weight it, and it is not mined.  The loss this loop
+    prints, and that feeds the size scores with update_type="loss", is then the cross-entropy part + the Dice term (if on) + the
+    Lovasz term (if on) + the surface term; accuracies, confusion matrices and validation do not change.  Given here, it replaces a
+    pair restored from a checkpoint's side file; None keeps that.  Under data parallelism nothing is added: the maps are per patch,
+    and the normaliser is unchanged.
     scale_jitter (opt-in; None = today's run, bit for bit): (lo, hi) -- every training patch is resampled at a scale drawn
     log-uniformly from [lo, hi] (patches.draw_scales, drs_crop_normalize_scaled).  The draws come from a generator of
     their own keyed by (run seed, step), so the sizes, instances and augmentation draws of the run are those of the run without it;
@@ -695,6 +788,8 @@ def train(training_data, training_labels, training_class_distribution, training_
         setup_hard_mining(net, hard_mining, comm, say)
     if lovasz is not None:
         setup_lovasz(net, lovasz, comm, say)
+    if surface_loss is not None:
+        setup_surface_loss(net, surface_loss, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = setup_scale_jitter(scale_jitter, seeds, comm, say)

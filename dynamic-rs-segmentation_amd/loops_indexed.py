@@ -85,7 +85,8 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
           current_model, lr_initial, weight_decay, batch_size, niter, net_type, distribution_type, update_type, patch_acc_loss,
           patch_occur, patch_chosen_values, probs, values, *, num_classes, void_label=-1, side_names=None, device="cuda:0",
           comm=None, display_step=50, quiet_sizes=False, quantize_f16=False, flavour="isprs", class_weights=None,
-          focal_gamma=None, scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None, lovasz=None):
+          focal_gamma=None, scale_jitter=None, boundary_weight=None, dice=None, hard_mining=None, lovasz=None,
+          surface_loss=None):
     """class_weights (opt-in; None = the reference's loss): "balanced" | "median" | K numbers, as loops.train takes them; the counts of
     the recipes leave the void label out.  The printed loss and the loss-based size scores are then the weighted ones.
     focal_gamma (opt-in; None or 0 = today's run): the focusing parameter of the focal loss, as loops.train takes it; the printed loss
@@ -101,6 +102,9 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
     of its valid pixels.
     lovasz (opt-in; None or lam = 0 = today's run): lam, as loops.train takes it; the printed loss and the loss-based size scores are
     then the cross-entropy part + the Dice term (if on) + the Lovasz term.  Contest's void pixels are outside the loss and the order.
+    surface_loss (opt-in; None or lam = 0 = today's run): (lam, clip), as loops.train takes it; the printed loss and the loss-based
+    size scores are then the cross-entropy part + the Dice and Lovasz terms (if on) + the surface term.  Contest's void pixels are
+    outside the loss: they are never a site of a distance map and carry no term.
     scale_jitter (opt-in; None = today's run): (lo, hi), as loops.train takes it -- every training patch resampled at a scale drawn
     log-uniformly from [lo, hi] by a generator of its own (patches.draw_scales), before the flip by index, coffee's float16 pass and
     contest's void mask; the test pass never jitters."""
@@ -146,6 +150,8 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
         loops.setup_hard_mining(net, hard_mining, comm, say)
     if lovasz is not None:
         loops.setup_lovasz(net, lovasz, comm, say)
+    if surface_loss is not None:
+        loops.setup_surface_loss(net, surface_loss, comm, say)
     run_seed = None
     if scale_jitter is not None:
         scale_jitter, run_seed = loops.setup_scale_jitter(scale_jitter, seeds, comm, say)
@@ -159,6 +165,7 @@ def train(training_data, training_labels, test_data, test_labels, class_distribu
             loops.save_dice(net, output_path, step)
             loops.save_hard_mining(net, output_path, step)
             loops.save_lovasz(net, output_path, step)
+            loops.save_surface_loss(net, output_path, step)
             if sized:
                 np.save(output_path + side[0] + str(step) + ".npy", patch_acc_loss)
                 np.save(output_path + side[1] + str(step) + ".npy", patch_occur)

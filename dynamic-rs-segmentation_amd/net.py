@@ -157,6 +157,7 @@ class DilatedNet(object):
         self._dice = None
         self._hard_mining = None
         self._lovasz = None
+        self._surface_loss = None
         self.debug = None
         self.timer = None
         if self.b_max * self.s_max * self.s_max >= (1 << 24):
@@ -359,6 +360,33 @@ class DilatedNet(object):
         """lam in use, or None when the term is off (never set, or lam == 0)"""
         v = self._lovasz
         return None if v is None or v == 0.0 else v
+
+    # ------------------------------------------------------------------ boundary (surface) loss of the training loss
+    def set_surface_loss(self, surface_loss):
+        """Boundary (surface) loss of the training loss (opt-in; Kervadec et al., MIDL 2019): surface_loss = (lam, clip)
+        as patches.check_surface_loss takes it, or None / lam == 0 (the step as it is, bit for bit, no new launch).  train_step then
+        adds L_surf = inv_n * sum over patches b, counted pixels p and classes c of g_c(p) P_c(p) to its data term, g_c = lam times
+        the class's signed Euclidean distance map of the patch's labels (positive outside the class, 1 - distance inside, clipped to
+        +-clip pixels when clip > 0; 0 for a class that is absent from the patch or fills it), and the matching per-(pixel, class)
+        term to the logit gradients.  A pixel is counted when it is in the loss and, where the step has an accuracy mask, set in it:
+        rotated-in fill and void pixels are never a site and carry no term.  The maps are per patch, exact, and made on the GPU each
+        step, so a sharded batch trains as the whole one does and no collective is added.  Class weights, the focal factor, the
+        boundary weight and hard mining do not weight this term, and it is not mined.  The loss train_step reports is the
+        cross-entropy part + the Dice term (if on) + the Lovasz term (if on) + L_surf; logits, pred, the confusion matrix, the L2 term
+        and every forward pass do not change.  State of the training run, not of the model: loops.save_checkpoint keeps it in a side
+        file, and an inference twin does not copy it."""
+        from .patches import check_surface_loss
+        self._surface_loss = None if surface_loss is None else check_surface_loss(surface_loss)
+        self._surface_loss_changed()
+
+    def _surface_loss_changed(self):
+        pass
+
+    @property
+    def surface_loss(self):
+        """(lam, clip) in use, or None when the term is off (never set, or lam == 0)"""
+        v = self._surface_loss
+        return None if v is None or v[0] == 0.0 else v
 
     def _touch_f32(self, name):
         """slab `name` was just written as fp32 only (crop / feed, SE and average-pool producers)."""

@@ -111,6 +111,9 @@ class OpLevelNet(DilatedNet):
         self.region_grad = torch.zeros(M * p.K, **f32)
         self.lovasz_loss = torch.zeros(B, **f64)
         self.lovasz_scratch = torch.zeros(_lib.query("drs_lovasz_scratch_bytes", B, self.s_max, p.K) // 8, **f64)
+        # the boundary (surface) loss (set_surface_loss): the patches' terms and the pre-pass's scratch (its map goes to region_grad); untouched while it is off
+        self.surface_loss_terms = torch.zeros(B, **f64)
+        self.surface_scratch = torch.zeros(_lib.query("drs_surface_loss_scratch_bytes", B, self.s_max, p.K) // 8, **f64)
 
     def workspace_bytes(self):
         tot = 0
@@ -355,7 +358,8 @@ class OpLevelNet(DilatedNet):
         dice = self.dice                  # (lam, alpha, beta, smooth) or None: off, no launch, and the Dice form without coefficients is the pixel one
         hard = self.hard_mining           # (keep, min_keep) or None: off, no launch
         lov = self.lovasz                 # lam or None: off, no launch
-        if dice is not None or hard is not None or lov is not None:
+        surf = self.surface_loss          # (lam, clip) or None: off, no launch
+        if dice is not None or hard is not None or lov is not None or surf is not None:
             # the classifier once in its inference form (logits only) for both pre-passes, then the coefficients of every (patch, class)
             # and / or the weight map of the hardest pixels from them: timed under the kind the engine accounts them under (its
             # bracket's work figure stays with the fused launch)
@@ -374,11 +378,18 @@ class OpLevelNet(DilatedNet):
             self._k("classifier_loss", 0.0, "drs_patch_lovasz_grad", _ptr(self.logits), _ptr(self.lovasz_err), _ptr(self.labels),
                       _ptr(self.loss_mask) if use_loss_mask else None, B, S, p.K, lov, None if dice is None else _ptr(self.dice_coef), None,
                       _ptr(self.region_grad), _ptr(self.lovasz_loss), _ptr(self.lovasz_scratch), self.lovasz_scratch.numel() * 8, st)
-        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_dice" if lov is None else "drs_classifier_loss_region", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
+        if surf is not None:
+            # the map of the boundary (surface) loss: added onto the Lovasz map, or written with the Dice coefficients folded in
+            self._k("classifier_loss", 0.0, "drs_patch_surface_loss", _ptr(self.logits), _ptr(self.labels),
+                      _ptr(self.loss_mask) if use_loss_mask else None, _ptr(self.acc_mask) if use_acc_mask else None, B, S, p.K,
+                      surf[0], surf[1], _ptr(self.dice_coef) if dice is not None and lov is None else None, 0 if lov is None else 1, None,
+                      _ptr(self.region_grad), _ptr(self.surface_loss_terms), _ptr(self.surface_scratch), self.surface_scratch.numel() * 8, st)
+        region = lov is not None or surf is not None
+        self._k("classifier_loss", M * p.c_last * 8.0, "drs_classifier_loss_region" if region else "drs_classifier_loss_dice", _ptr(feat), B, S, Pf, ldf, cf, p.c_last, p.K,
                 self.params[woff:].data_ptr(), self.params[boff:].data_ptr(), _ptr(self.labels), _ptr(self.loss_mask) if use_loss_mask else None,
                   _ptr(self.acc_mask) if use_acc_mask else None, 1.0 / n_glob, None if wc is None else wc.ctypes.data, float(self._focal_gamma),
                   None if bw is None and hard is None else _ptr(self.pixel_weight),
-                  _ptr(self.region_grad) if lov is not None else None if dice is None else _ptr(self.dice_coef),
+                  _ptr(self.region_grad) if region else None if dice is None else _ptr(self.dice_coef),
                   _ptr(self.logits) if want_logits else None,
                   _ptr(self.pred), _ptr(gfeat), ldg, cg, _ptr(self.dw_partial), _ptr(self.db_partial), _ptr(self.loss_partial),
                   _ptr(self.conf), st)
@@ -390,6 +401,8 @@ class OpLevelNet(DilatedNet):
             _lib.call("drs_dice_loss_add", _ptr(self.dice_loss), B, _ptr(self.scalars), st)
         if lov is not None:
             _lib.call("drs_dice_loss_add", _ptr(self.lovasz_loss), B, _ptr(self.scalars), st)
+        if surf is not None:
+            _lib.call("drs_dice_loss_add", _ptr(self.surface_loss_terms), B, _ptr(self.scalars), st)
         _lib.call("drs_l2_loss", _ptr(self.params), p.n_decay, _ptr(self.l2_scratch), self.scalars[1:].data_ptr(), st)
         # conv biases sit in front of a mean-subtracting batch norm: their gradient is identically zero
         b0, _ = p.offsets[p.layers[0].name + "/biases"]

@@ -528,6 +528,46 @@ def parse_lovasz(text):
     return check_lovasz(val)
 
 
+# ------------------------------------------------------------------- boundary (surface) loss of the training loss
+MAX_SURFACE_LAMBDA = 64.0              # the ranges drs_net_set_surface_loss takes (include/drs.h)
+MAX_SURFACE_CLIP = 32768.0
+DEFAULT_SURFACE_LOSS = (0.0, 0.0)      # off; clip 0: the distances are not clipped
+
+
+def check_surface_loss(surface_loss):
+    """The boundary (surface) loss of the training loss as the library takes it: (lam, clip) -- or (lam,), or a bare
+    number lam -- with lam finite in [0, 64] (0: off) and clip 0 (none, the default) or finite in [1, 32768] pixels.  Returns
+    (float, float).  Anything else: ValueError."""
+    t = tuple(surface_loss) if isinstance(surface_loss, (tuple, list)) else (surface_loss,)
+    what = "surface loss %r: expected lam[, clip] with lam in [0, %g] and clip 0 or in [1, %g]" % (surface_loss, MAX_SURFACE_LAMBDA,
+                                                                                                 MAX_SURFACE_CLIP)
+    if len(t) not in (1, 2) or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in t):
+        raise ValueError(what)
+    lam = float(t[0])
+    clip = float(t[1]) if len(t) == 2 else DEFAULT_SURFACE_LOSS[1]
+    if not math.isfinite(lam) or lam < 0.0 or lam > MAX_SURFACE_LAMBDA:
+        raise ValueError(what)
+    if not math.isfinite(clip) or not (clip == 0.0 or 1.0 <= clip <= MAX_SURFACE_CLIP):
+        raise ValueError(what)
+    return lam, clip + 0.0
+
+
+def parse_surface_loss(text):
+    """The value of the command lines' --surface-loss option: `lam` or `lam,clip` as check_surface_loss takes them.  Anything else
+    raises ValueError."""
+    vals = None
+    if text and text == text.strip():
+        parts = text.split(",")
+        try:
+            if len(parts) in (1, 2) and all(q and q == q.strip() for q in parts):
+                vals = [float(q) for q in parts]
+        except ValueError:
+            vals = None
+    if vals is None:
+        raise ValueError("surface loss %r: expected lam[,clip] (numbers)" % (text,))
+    return check_surface_loss(tuple(vals))
+
+
 # ------------------------------------------------------------------- per-pixel score maps of whole-tile inference
 SCORE_KINDS = ("confidence", "margin", "entropy")     # the uint8 maps of drs_stitch_finalize_scores (DESIGN.md 8a.4)
 

@@ -768,6 +768,23 @@ int drs_net_get_hard_mining(const drs_net_t* net, double* keep, int* min_keep);
  * NULL); 0 when never set. */
 int drs_net_set_lovasz(drs_net_t* net, double lam);
 int drs_net_get_lovasz(const drs_net_t* net, double* lam);
+/* Boundary (surface) loss of drs_train_step's loss (opt-in; the section "Training level: boundary (surface) loss" below states the
+ * rule): lam finite in [0, 64], clip 0 (none) or finite in [1, 32768]; lam == 0 (the default) switches it off -- no new launch, the
+ * step is the launches it was, bit for bit, the bound buffers "surface_loss" and "surface_scratch" are not touched, and neither is
+ * "region_grad" unless the Lovasz term writes it; anything else DRS_ERR_ARG, and the pair in use stays.  With lam > 0 the step runs,
+ * in this order: the boundary-weight launch if that option is on; the classifier in its inference form into the bound buffer "logits"
+ * (ONE such launch for all pre-passes); drs_patch_dice_coeffs, drs_patch_hard_weight and drs_patch_lovasz_grad, each if on;
+ * drs_patch_surface_loss(logits, labels, loss_mask if and only if DRS_USE_LOSS_MASK, acc_mask if and only if DRS_USE_ACC_MASK (where
+ * drs_patch_boundary_weight gets it), ..., lam, clip, dice_coef, accumulate, NULL, "region_grad", "surface_loss", "surface_scratch",
+ * ...) with accumulate = 1 and no dice_coef when the Lovasz term is on (its map already holds the Dice part), else "dice_coef" when
+ * the Dice term is on, else a plain write; and the classifier as drs_classifier_loss_region with the pixel map, if any, and
+ * "region_grad".  All of it is accounted under the timing kind "classifier_loss".  The sum of "surface_loss" is added into
+ * "scalars"[0] before its all-reduce, after those of "dice_loss" and "lovasz_loss" (each if on): it is then the cross-entropy part +
+ * L_dice (if on) + L_lov (if on) + L_surf; the term itself is never mined or weighted.  No collective, event or stream is added.
+ * drs_forward and drs_forward_staged have no loss and ignore it.  drs_net_get_surface_loss: the pair in use (either pointer may be
+ * NULL); (0, 0) when never set. */
+int drs_net_set_surface_loss(drs_net_t* net, double lam, double clip);
+int drs_net_get_surface_loss(const drs_net_t* net, double* lam, double* clip);
 /* per-kernel-family HIP-event timing of the launches of a step (bench.py's roofline figures); off by default */
 int drs_net_timing(drs_net_t* net, int enable);
 int drs_net_num_timing_kinds(void);
@@ -1081,6 +1098,65 @@ int drs_classifier_loss_region(const float* feat, int B, int S, int P, int ld, i
                                const float* pixel_weight, const float* region_grad, float* logits, unsigned char* pred, float* gfeat,
                                int ld_g, int coff_g, float* dw_partial, float* db_partial, double* loss_partial, unsigned int* conf,
                                void* stream);
+
+/* ==================================================================================================================
+ * Training level: boundary (surface) loss (opt-in; csrc/surface_loss.hip).  The boundary loss of Kervadec, Bouchtiba,
+ * Desrosiers, Granger, Dolz, Ben Ayed (Boundary loss for highly unbalanced segmentation, MIDL 2019; `SurfaceLoss` in their code): the
+ * softmax probability of every class integrated against the class's signed Euclidean distance map of the ground truth -- the
+ * quantity the surface-distance validation scores measure, as a term of the loss.  Per PATCH, so that the loss stays a sum over
+ * patches: a sharded batch gives the single-rank loss and gradient with no collective.  NORMATIVE: this text and the numpy statement
+ * tests/surface_loss_ref.py.
+ * Option (lam, clip): lam finite in (0, 64]; clip = 0 (none) or finite in [1, 32768] pixels.
+ * Every quantity is per patch b and independent of other patches.
+ *     A pixel is COUNTED when label < K, loss_mask is set where one is given, and valid is set where one is given.  Pixels that are
+ *         not counted (rotated-in fill, void) are never a site and carry no term.
+ *     Sites of class c: A_c = the counted pixels with y = c, O_c = the counted pixels with y != c.  If either set is empty, phi_c = 0
+ *         in the whole patch (an absent class, and a class without a contour in the patch).
+ *     Signed squared distance, exact integers; the patch's edge is no boundary and nothing reads across patches:
+ *         at p in O_c: D2 = min_{q in A_c} |p - q|^2, phi_c(p) = +sqrt(D2);
+ *         at p in A_c: D2 = min_{q in O_c} |p - q|^2, phi_c(p) = 1 - sqrt(D2)   (the published -(sqrt(D2) - 1); +0 where D2 = 1);
+ *         phi = 0 at pixels that are not counted.  On a fully counted patch this is edt(~pos) ~pos - (edt(pos) - 1) pos of the
+ *         published code, with scipy's distance_transform_edt.
+ *     Map: g_c(p) = (float)(lam clamp(phi_c(p), -clip, +clip)); the square root and the product in fp64, rounded once; exactly +0
+ *         where phi is 0.
+ *     Loss: L_surf = inv_n sum_b sum_{p counted} sum_c g_c(p) P_c(p); P_c = ex_c / se in fp32 from the fp32 logits (mx = the maximum
+ *         logit, ex_k = expf(lg_k - mx), se = sum of ex_k in ascending k, a true division), the products and sums in fp64 in a fixed
+ *         order (inv_n: the step's 1 / global pixels in the loss, as for the Dice and Lovasz terms).
+ * Gradient: dL_surf / dlogit_k = inv_n P_k (g_k - sum_c P_c g_c), ADDED to the logit gradient of whatever cross-entropy form is
+ *     active -- what drs_classifier_loss_region adds for the map g.  Class weights, the focal factor, the boundary map and the mining
+ *     map do NOT weight the term, and it is not mined.  Logits, arg-max and the confusion matrix are untouched.
+ *
+ * drs_surface_loss_scratch_bytes: the scratch drs_patch_surface_loss needs for (B, S, K) (a multiple of 16, monotone in each argument;
+ *     0 for arguments outside the ranges below): B K doubles (rounded up to 16 bytes), and above S = 128 the two column-distance
+ *     planes, 4 S S bytes (rounded up to 16) per (patch, class).
+ * drs_patch_surface_loss: logits = float [B S S][K] (what the classifier's inference form writes) or NULL -- then only the map and
+ *     phi2_out are made and patch_loss_out is written as 0; labels = uint8 [B S S]; loss_mask, valid = uint8 [B S S] or NULL.
+ *     phi2_out = int32 [B S S][K] or NULL: +D2 outside (p in O_c), -D2 inside (p in A_c), 0 where phi_c = 0 in the patch or the pixel
+ *     is not counted -- it exists so that a wrong distance and a wrong coefficient can be told apart.
+ *     grad_io = float [B S S][K].  accumulate == 0: WRITTEN, g_c(p) at counted pixels and +0 elsewhere; with dice_coef = float
+ *     [B][K][2] (drs_patch_dice_coeffs' output, 8-byte aligned) the Dice coefficient is folded in with one fp32 add at the pixels
+ *     that are in the loss (label < K and loss_mask set, whatever valid says), as drs_patch_lovasz_grad does:
+ *     grad_io[p][c] = g_c(p) + (y_p == c ? G_in[b][c] : G_out[b][c]), so that the classifier reads one map form only.
+ *     accumulate != 0: g_c(p) is ADDED to what grad_io holds with one fp32 add at counted pixels, every other entry is left alone --
+ *     how the step stacks the term on drs_patch_lovasz_grad's map.  dice_coef together with accumulate: DRS_ERR_ARG.
+ *     patch_loss_out = double [B]: sum_c sum_p g_c(p) P_c(p), the classes in ascending order; 0 for a patch with nothing counted.
+ *     One workgroup per (patch, class), which reads and writes its own patch only: the label / counted bytes, then one thread per
+ *     column leaves the distance to the nearest site of the column for both site sets (uint16, 0xFFFF: none; a sweep down and one
+ *     up), then every thread takes pixels, lanes on consecutive x, and scans its row outward from x for min_i (x - i)^2 + g[y][i]^2,
+ *     four offsets to either side per round (their reads in flight together), until a round's first offset squared alone reaches the
+ *     best so far.  Exact.  The planes and bytes stay in LDS up to S = 128 (5 S S bytes) and the
+ *     planes live in scratch above that; any S with B S S < 2^24.  No floating-point atomics, every fp64 sum in a fixed order: the
+ *     same bits on every run and every rank.  A second, tiny launch joins the classes' sums.  Scratch is never read before it is
+ *     written.
+ *     Ranges, else DRS_ERR_ARG (nothing is launched): labels, grad_io, patch_loss_out not NULL; B, S >= 1, B S S < 2^24; K in 1..8;
+ *     lam finite in (0, 64]; clip 0 or finite in [1, 32768]; scratch not NULL, 8-byte aligned, scratch_bytes >=
+ *     drs_surface_loss_scratch_bytes(B, S, K); dice_coef and patch_loss_out 8-byte aligned; logits, grad_io, phi2_out 4-byte aligned.
+ * The step joins the patches' terms to the cross-entropy sum with drs_dice_loss_add. */
+size_t drs_surface_loss_scratch_bytes(int B, int S, int K);
+int drs_patch_surface_loss(const float* logits, const unsigned char* labels, const unsigned char* loss_mask,
+                           const unsigned char* valid, int B, int S, int K, double lam, double clip, const float* dice_coef,
+                           int accumulate, int* phi2_out, float* grad_io, double* patch_loss_out, void* scratch, size_t scratch_bytes,
+                           void* stream);
 
 #ifdef __cplusplus
 }
