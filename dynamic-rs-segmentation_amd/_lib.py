@@ -94,6 +94,12 @@ SIGNATURES = {
     "drs_object_scratch_bytes": (_sz, [_i, _i]),
     "drs_object_match": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "drs_object_table": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    # ---- whole-map level: superpixels and the vote inside regions (csrc/superpixels.hip)
+    "drs_superpixel_features": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "drs_superpixel_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "drs_superpixels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "drs_region_vote_scratch_bytes": (_sz, [_i, _i]),
+    "drs_region_vote": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     # ---- whole-map level: exact distance transform and surface-distance table (csrc/distance.hip)
     "drs_distance_scratch_bytes": (_sz, [_i, _i]),
     "drs_distance_transform": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),

@@ -33,6 +33,12 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     enough, round after round until none is left (loops.sieve_labels); one `Sieve` line per map and for all maps.
     `--sieve-connectivity=4|8` (default 4; with --sieve only) says what holds a region together.  Score maps and calibration lines
     stay those of the unsieved labels
+  + optionally, anywhere, `--superpixel-vote[=size[,compactness[,iters]]]` (validate_test / generate_final_maps; any inference path,
+    after --crf and before --sieve): object-based voting: the map's image is cut into superpixels (integer SLIC; grid step `size`
+    4..32, default 8; compactness 1..40, default 10; 1..16 iterations, default 5) and every connected piece of a superpixel takes the
+    class most of its pixels voted for, ties to the lower class (loops.superpixel_vote); one `Superpixel` line per
+    map and for all maps.  `--superpixel-weight=labels|confidence` (default labels; with --superpixel-vote only): with `confidence`
+    a pixel votes with its confidence byte.  Score maps and calibration lines stay those of the unvoted labels
   + optionally, anywhere, `--object-scores[=4|8]` (validate_test; any inference path, with or without --crf / --sieve): one more line
     per map and for all maps with object-level scores -- the connected regions of each class (4-connected by default) are the objects,
     a truth object and a predicted one match when their IoU exceeds 1/2 --: per class the truth / predicted / matched counts, detection
@@ -276,6 +282,31 @@ def parse_sieve(argv, num_classes=None):
     return argv, P.check_sieve(dict(min_size=min_size, connectivity=P.SIEVE_CONNECTIVITY if conn is None else int(conn)))
 
 
+SUPERPIXEL_FLAG = "--superpixel-vote"
+SUPERPIXEL_WEIGHT_FLAG = "--superpixel-weight"
+
+
+def parse_superpixel(argv):
+    """isprs flavour: the optional `--superpixel-vote[=size[,compactness[,iters]]]` and `--superpixel-weight=labels|confidence`
+    (anywhere in argv; validate_test / generate_final_maps, which main checks).  Returns (argv without the flags, the
+    patches.SuperpixelParams of patches.check_superpixel) -- the defaults for the bare flag --, or (argv unchanged, None) without
+    either.  A malformed or out-of-range value, --superpixel-weight without --superpixel-vote, or a flag given twice, raises
+    ValueError."""
+    ranges = ", ".join("%s %d..%d" % r for r in P.SUPERPIXEL_RANGES)
+    argv, values = _take_flag(argv, SUPERPIXEL_FLAG, lambda a, v: _or_expected(
+        P.parse_superpixel, a, v, "%s or %s=size[,compactness[,iters]] (integers: %s)" % (SUPERPIXEL_FLAG, SUPERPIXEL_FLAG, ranges)),
+        bare=())
+    argv, weight = _take_flag(argv, SUPERPIXEL_WEIGHT_FLAG, _one_of(P.SUPERPIXEL_WEIGHTS, SUPERPIXEL_WEIGHT_FLAG))
+    if values is None:
+        if weight is not None:
+            raise ValueError(SUPERPIXEL_WEIGHT_FLAG + " applies to the superpixel vote only: give " + SUPERPIXEL_FLAG + " as well")
+        return argv, None
+    spec = dict(zip(("size", "compactness", "iters"), values))
+    if weight is not None:
+        spec["weight"] = weight
+    return argv, P.check_superpixel(spec)
+
+
 OBJECT_SCORES_FLAG = "--object-scores"
 
 
@@ -463,6 +494,7 @@ def main(argv=None, device=None, comm=None):
         argv, crf = parse_crf(argv)
         argv, boundary = parse_boundary_scores(argv)
         argv, sieve = parse_sieve(argv, 6)
+        argv, superpixel = parse_superpixel(argv)
         argv, objects = parse_object_scores(argv)
         argv, surface = parse_surface_scores(argv)
         argv, class_weights = parse_class_weights(argv, 6)
@@ -503,6 +535,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(BOUNDARY_FLAG + " applies to the validate_test process only")
     if sieve is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(SIEVE_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if superpixel is not None and argv[16] not in ("validate_test", "generate_final_maps"):
+        sys.exit(SUPERPIXEL_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if objects is not None and argv[16] != "validate_test":
         sys.exit(OBJECT_SCORES_FLAG + " applies to the validate_test process only")
     if surface is not None and argv[16] != "validate_test":
@@ -596,6 +630,7 @@ def main(argv=None, device=None, comm=None):
     crf_kw = {} if crf is None else dict(crf=crf)          # without the flag the loops are called as they always were
     boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
     sieve_kw = {} if sieve is None else dict(sieve=sieve)
+    superpixel_kw = {} if superpixel is None else dict(superpixel=superpixel)
     objects_kw = {} if objects is None else dict(object_scores=objects)
     surface_kw = {} if surface is None else dict(surface_scores=surface)
     if process == "validate_test":
@@ -612,12 +647,12 @@ def main(argv=None, device=None, comm=None):
                 np.save(temperature_file(output_path, step), np.array([fit["beta"]], dtype=np.float32))
         return loops.validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop,
                                    step, output_path, comm, score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                   **boundary_kw, **sieve_kw, **objects_kw, **surface_kw)
+                                   **boundary_kw, **sieve_kw, **superpixel_kw, **objects_kw, **surface_kw)
     if process == "generate_final_maps":
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
                                          score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                         **sieve_kw)
+                                         **sieve_kw, **superpixel_kw)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -1565,6 +1565,102 @@ def _sieve_str(sieve, infos):
             " ".join(str(v) for v in total("objects_after")) + "]")
 
 
+def superpixel_scale(pool, map_index):
+    """(lo, inv) of drs_superpixel_features for one map of the pool, two float32 numpy arrays [C]: per channel lo = the map's own
+    minimum and inv = 255 / (max - min) in fp32, 0 where max == min -- the bytes span what the map holds, whatever its units.  The
+    minimum and maximum are torch's (aminmax over the tile view, on the current stream); this reads them back."""
+    h, w, C = pool.h[map_index], pool.w[map_index], pool.C
+    off = int(pool.tile_off[map_index].item())
+    lo, hi = torch.aminmax(pool.tiles[off:off + h * w * C].view(h * w, C), dim=0)
+    lo, hi = lo.cpu().numpy().astype(np.float32), hi.cpu().numpy().astype(np.float32)      # rounding is monotonic: min and max of the fp32 values
+    with np.errstate(all="ignore"):
+        inv = np.where(hi == lo, np.float32(0), np.float32(255) / (hi - lo)).astype(np.float32)
+    return lo, inv
+
+
+def superpixels(pool, map_index, params, stream=None):
+    """The superpixels of one map's image in `pool` (include/drs.h): byte features at the map's own scale
+    (superpixel_scale, drs_superpixel_features), integer SLIC on them (drs_superpixels; params: what patches.check_superpixel accepts)
+    and the connected pieces of the clusters (drs_components on the 16-colouring, connectivity 4).  Returns (assign, region_label,
+    region_size, centres) as device tensors: assign int32 [h, w] = the centre id of every pixel; region_label int32 [h, w] = the
+    smallest linear index of the pixel's region; region_size int32 [h, w]; centres int32 [gh gw, C + 3] = (cx, cy, features, pixel
+    count).  stream: a raw stream handle (default: torch's current stream on the pool's device)."""
+    from . import _lib
+    params = P.check_superpixel(params)
+    h, w, C = pool.h[map_index], pool.w[map_index], pool.C
+    need = _lib.query("drs_superpixel_scratch_bytes", C, h, w, params.size)
+    if need == 0:
+        raise ValueError("superpixels: a map of %d x %d x %d is outside 1 <= h, w <= 32768, 1 <= C <= 8" % (h, w, C))
+    dev = pool.tiles.device
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        lo, inv = superpixel_scale(pool, map_index)
+        tile = pool.tiles.data_ptr() + int(pool.tile_off[map_index].item()) * (8 if pool.f64 else 4)
+        feat = torch.empty((h, w, C), dtype=torch.uint8, device=dev)
+        _lib.call("drs_superpixel_features", tile, 1 if pool.f64 else 0, C, h, w, lo.ctypes.data, inv.ctypes.data, feat.data_ptr(), st)
+        ncentres = need // (4 * (C + 3))
+        assign = torch.empty((h, w), dtype=torch.int32, device=dev)
+        colour = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        centres = torch.empty((ncentres, C + 3), dtype=torch.int32, device=dev)
+        scratch = torch.empty(need // 4, dtype=torch.int32, device=dev)
+        _lib.call("drs_superpixels", feat.data_ptr(), C, h, w, params.size, params.compactness, params.iters, assign.data_ptr(),
+                  colour.data_ptr(), centres.data_ptr(), scratch.data_ptr(), st)
+        label = torch.empty((h, w), dtype=torch.int32, device=dev)
+        size = torch.empty((h, w), dtype=torch.int32, device=dev)
+        _lib.call("drs_components", colour.data_ptr(), h, w, 4, label.data_ptr(), size.data_ptr(), st)
+    return assign, label, size, centres
+
+
+def region_vote(map_dev, label, h, w, K, weight=None, stream=None):
+    """The vote of a uint8 device map [h][w] of K classes inside the regions of `label` (drs_region_vote; include/drs.h; DESIGN.md
+    8a.11): label int32 [h][w] = the smallest linear index of every pixel's region, as drs_components writes it -- any such labelling.
+    Every region takes the class with the largest sum of `weight` (a uint8 device map [h][w]; None: 1 per pixel) over its pixels,
+    ties to the lower class; a region whose largest sum is 0 stays as it is; bytes >= K neither vote nor change.  Returns (the voted
+    map, a new uint8 device tensor shaped like map_dev, info) with info = {"regions", "changed_pixels"}; reading the two counters is
+    the one synchronisation.  stream: a raw stream handle (default: torch's current stream on the map's device)."""
+    from . import _lib
+    _byte_map("region_vote", "map", map_dev, h, w)
+    if label.dtype != torch.int32 or label.numel() != h * w or not label.is_contiguous():
+        raise ValueError("region_vote: the labels must be a contiguous int32 tensor of %d x %d elements" % (h, w))
+    if weight is not None:
+        _byte_map("region_vote", "weight", weight, h, w)
+    need = _lib.query("drs_region_vote_scratch_bytes", int(h), int(w))
+    if need == 0:
+        raise ValueError("region_vote: a map of %d x %d is outside 1 <= h, w <= 32768" % (h, w))
+    dev = map_dev.device
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        out = torch.empty_like(map_dev)
+        scratch = torch.empty(need // 8, dtype=torch.int64, device=dev)
+        counters = torch.empty(2, dtype=torch.int32, device=dev)
+        _lib.call("drs_region_vote", map_dev.data_ptr(), label.data_ptr(), None if weight is None else weight.data_ptr(), int(h), int(w),
+                  int(K), scratch.data_ptr(), out.data_ptr(), counters.data_ptr(), st)
+        regions, changed = [int(v) for v in counters.cpu().tolist()]
+    return out, {"regions": regions, "changed_pixels": changed}
+
+
+def superpixel_vote(net, pool, map_index, pred, params, confidence=None):
+    """Object-based voting of one map (opt-in): the superpixels of the map's image (superpixels) and the vote of the
+    label map `pred` (uint8 device [h, w]) inside their connected pieces (region_vote), on the net's stream.  params: what
+    patches.check_superpixel accepts; with weight "confidence" a pixel votes with its byte of `confidence` (the path's uint8
+    confidence map), else once.  Returns (the voted map, info) with info = {"regions", "changed_pixels", "centres"}."""
+    params = P.check_superpixel(params)
+    if params.weight == "confidence" and confidence is None:
+        raise ValueError("superpixel_vote: weight 'confidence' needs the path's confidence map")
+    h, w, st = pool.h[map_index], pool.w[map_index], net._stream()
+    _, label, _, centres = superpixels(pool, map_index, params, stream=st)
+    out, info = region_vote(pred, label, h, w, net.plan.K, weight=confidence if params.weight == "confidence" else None, stream=st)
+    return out, dict(info, centres=int(centres.shape[0]))
+
+
+def _superpixel_str(params, infos):
+    """the Superpixel line's text from one superpixel_vote info, or from those of all maps (counts summed)"""
+    infos = infos if isinstance(infos, list) else [infos]
+    return ("Superpixel size= " + str(params.size) + " compactness= " + str(params.compactness) + " iters= " + str(params.iters) +
+            " weight= " + params.weight + " Regions= " + str(sum(i["regions"] for i in infos)) +
+            " Changed Pixels= " + str(sum(i["changed_pixels"] for i in infos)))
+
+
 def object_table(truth_dev, pred_dev, h, w, K, ignore_label, connectivity, table=None, stream=None):
     """The object table of one (truth, prediction) pair of uint8 device maps [h][w] (include/drs.h): the connected
     components of both maps at `connectivity` (two drs_components), the match of the two labellings (drs_object_match: a truth object
@@ -1736,7 +1832,7 @@ def fit_temperature(net, testing_data, testing_labels, batch_size, mean_full, st
 def validate_test(net, testing_data, testing_labels, testing_instances, batch_size, mean_full, std_full, crop_size, step,
                   output_path=None, comm=None, pool=None, ignore_label=6, crop_sizes=None, flavour="isprs", dense_tile=None,
                   dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None, crf=None,
-                  boundary_scores=None, sieve=None, surface_scores=None, object_scores=None):
+                  boundary_scores=None, sieve=None, surface_scores=None, superpixel=None, object_scores=None):
     """isprs:1241-1344: per tile, sliding-window prediction and scores (label 6 = eroded boundary is skipped,
     isprs:1294).  Returns (all-maps confusion matrix, list of label maps as numpy).  dense_tile (an int, 0 = the default side): the
     maps come from overlap-tile inference (predict_tile_dense) instead of the windows; the scores are computed as before.  dense_tta
@@ -1791,7 +1887,18 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     [..] [..] ASSD= [..] HD95= [..] Saturated= [..] HD100= [..] NSD= [..] ... Mean ASSD= ... Mean HD95= ... Mean NSD= ...` follows the
     map's other lines, and one for all maps, from the summed table, the all-maps lines.  Returns (all-maps confusion matrix, label
     maps, extra) with extra["surface"] = metrics.surface_scores of the all-maps table, plus "table" (the int64 numpy table [2][K][4098])
-    and "per_map": [the same per map, each with its "table"].  Without surface_scores nothing changes."""
+    and "per_map": [the same per map, each with its "table"].  Without surface_scores nothing changes.
+    superpixel (opt-in; any inference path; what patches.check_superpixel accepts: size, compactness, iters, weight): object-based
+    voting (superpixel_vote).  The map the path returns -- the refined map with crf -- is voted inside the connected
+    pieces of the superpixels of the map's image BEFORE the sieve and before anything scores it; the order per map is path -> crf ->
+    superpixel vote -> sieve -> scores.  With weight "confidence" the path is asked for its confidence map whether score_maps is
+    given or not (the CRF-refined one with crf, the calibrated one under a temperature; the temperature rules stay as they are), and
+    without score_maps nothing else of the score maps appears.  Score maps and Calibration lines stay those of the UNVOTED labels, as
+    with the sieve.  Every rank votes the whole map itself and gets the same bits.  One line `---- Iter N -- Test Map M: Superpixel
+    size= s compactness= m iters= i weight= ... Regions= r Changed Pixels= p` follows the map's other lines (before the Sieve line),
+    and one for all maps with the counts summed.  Returns (all-maps confusion matrix, label maps, extra) with extra["superpixel"] =
+    {"params": the SuperpixelParams, "per_map": [superpixel_vote's info per map], "regions", "changed_pixels" (summed)}.  Without
+    superpixel nothing changes."""
     from . import _lib
     comm = comm or NoComm()
     path = InferencePath(crop_size, crop_sizes, flavour, dense_tile, dense_tta, dense_scales, dense_se)
@@ -1800,6 +1907,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
     beta = _check_temperature(temperature_beta, score_maps, crf)
     bdist = None if boundary_scores is None else P.check_boundary_distances(boundary_scores)
     sieve = None if sieve is None else P.check_sieve(sieve)
+    spx = None if superpixel is None else P.check_superpixel(superpixel)
     oconn = None if object_scores is None else P.check_object_scores(object_scores)
     stol = None if surface_scores is None else P.check_surface_tolerances(surface_scores)
     cal_tail = "" if beta is None else " Temperature= " + "{:.6f}".format(1.0 / beta)
@@ -1809,10 +1917,14 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         kinds = kinds if "confidence" in kinds else kinds + ("confidence",)
         all_hist = np.zeros((256, 2), dtype=np.int64)
         score_list, cal_list = [], []
+    # the confidence-weighted vote needs the path's confidence map, as the calibration report does: asked for, not reported
+    run_kinds = ("confidence",) if kinds is None and spx is not None and spx.weight == "confidence" else kinds
     K = net.plan.K
     if sieve is not None:
         P.sieve_thresholds(sieve, K)
         sieve_list = []
+    if spx is not None:
+        spx_list = []
     pool = pool or P.TilePool(testing_data, testing_labels, net.dev)
     all_cm = np.zeros((K, K), dtype=np.uint32)
     all_kappa = np.zeros(len(testing_data), dtype=np.float32)
@@ -1829,9 +1941,12 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         all_stable = np.zeros((2, K, MT.SURFACE_BINS + 2), dtype=np.int64)
         surface_list = []
     for k in range(len(testing_data)):
-        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
+        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, run_kinds, beta, crf)
         h, w = pool.h[k], pool.w[k]
         voted = pred                                       # the labels the posterior voted for: what the score maps describe
+        if spx is not None:
+            pred, pinfo = superpixel_vote(net, pool, k, pred, spx, confidence=smaps["confidence"] if spx.weight == "confidence" else None)
+            spx_list.append(pinfo)
         if sieve is not None:
             pred, sinfo = sieve_labels(pred, h, w, K, sieve, stream=net._stream())
             sieve_list.append(sinfo)
@@ -1872,6 +1987,8 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             boundary_list.append(MT.boundary_scores(bhist, bdist))
             if comm.rank == 0:
                 print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _boundary_str(boundary_list[-1]))
+        if spx is not None and comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _superpixel_str(spx, pinfo))
         if sieve is not None and comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test Map " + str(testing_instances[k]) + ": " + _sieve_str(sieve, sinfo))
         if oconn is not None:
@@ -1913,6 +2030,13 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _boundary_str(bnd))
         extra = dict(extra if kinds is not None else {}, boundary=bnd)
+    if spx is not None:
+        if comm.rank == 0:
+            print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _superpixel_str(spx, spx_list))
+        sp = {"params": spx, "per_map": spx_list}
+        for key in ("regions", "changed_pixels"):
+            sp[key] = sum(i[key] for i in spx_list)
+        extra = dict(extra if kinds is not None or bdist is not None else {}, superpixel=sp)
     if sieve is not None:
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _sieve_str(sieve, sieve_list))
@@ -1921,18 +2045,19 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
             sv[key] = sum(i[key] for i in sieve_list)
         for key in ("objects_before", "objects_after"):
             sv[key] = [sum(i[key][c] for i in sieve_list) for c in range(K)]
-        extra = dict(extra if kinds is not None or bdist is not None else {}, sieve=sv)
+        extra = dict(extra if kinds is not None or bdist is not None or spx is not None else {}, sieve=sv)
     if oconn is not None:
         obj = dict(MT.object_scores(all_otable), connectivity=oconn, table=all_otable, per_map=object_list)
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _objects_str(oconn, obj))
-        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None else {}, objects=obj)
+        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None or spx is not None else {}, objects=obj)
     if stol is not None:
         srf = dict(MT.surface_scores(all_stable, stol), table=all_stable, per_map=surface_list)
         if comm.rank == 0:
             print("---- Iter " + str(step) + " -- Test ALL MAPS: " + _surface_str(srf))
-        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None or oconn is not None else {}, surface=srf)
-    if kinds is not None or bdist is not None or sieve is not None or oconn is not None or stol is not None:
+        extra = dict(extra if kinds is not None or bdist is not None or sieve is not None or spx is not None or oconn is not None else {},
+                     surface=srf)
+    if kinds is not None or bdist is not None or sieve is not None or spx is not None or oconn is not None or stol is not None:
         return all_cm, maps, extra
     return all_cm, maps
 
@@ -1940,7 +2065,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
                         dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None,
-                        crf=None, sieve=None):
+                        crf=None, sieve=None, superpixel=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
@@ -1955,7 +2080,10 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     posterior refined by a local dense CRF against the image (refine_crf).  With crf a temperature_beta is accepted
     without score_maps: it scales the unary, so with a CRF it CAN change the label files.
     sieve (opt-in; any inference path; what patches.check_sieve accepts): the written and returned maps are sieved to a minimum
-    mapping unit first (sieve_labels), the refined map with crf; the score files stay those of the unsieved labels."""
+    mapping unit first (sieve_labels), the refined map with crf; the score files stay those of the unsieved labels.
+    superpixel (opt-in; any inference path; what patches.check_superpixel accepts): the written and returned maps are voted inside the
+    superpixels of each map's image first (superpixel_vote), after crf and before sieve; with weight "confidence"
+    the path is asked for its confidence map whether score_maps is given or not.  The score files stay those of the unvoted labels."""
     comm = comm or NoComm()
     path = InferencePath(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     path.check()
@@ -1963,6 +2091,10 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     beta = _check_temperature(temperature_beta, score_maps, crf)
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
     sieve = None if sieve is None else P.check_sieve(sieve)
+    spx = None if superpixel is None else P.check_superpixel(superpixel)
+    run_kinds = kinds                                      # the confidence-weighted vote needs the path's confidence map: asked for, not written
+    if spx is not None and spx.weight == "confidence" and "confidence" not in (kinds or ()):
+        run_kinds = (kinds or ()) + ("confidence",)
     if sieve is not None:
         P.sieve_thresholds(sieve, net.plan.K)
     score_list = []
@@ -1973,12 +2105,14 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     pool = P.TilePool(testing_data, None, net.dev)
     maps = []
     for k in range(len(testing_data)):
-        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, kinds, beta, crf)
+        pred, smaps = _run_path(path, net, pool, k, batch_size, mean_full, std_full, comm, run_kinds, beta, crf)
+        if spx is not None:
+            pred, _ = superpixel_vote(net, pool, k, pred, spx, confidence=smaps["confidence"] if spx.weight == "confidence" else None)
         if sieve is not None:
             pred, _ = sieve_labels(pred, pool.h[k], pool.w[k], net.plan.K, sieve, stream=net._stream())
         maps.append(pred.cpu().numpy())
         if kinds is not None:
-            score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items()})
+            score_list.append({kd: v.cpu().numpy() for kd, v in smaps.items() if kd in kinds})
         if comm.rank == 0 and output_path:
             # isprs:1950-1955: the colour map under the reference's file names (ISPRS palette, isprs:118-139), plus the class ids as .npy
             from . import datasets

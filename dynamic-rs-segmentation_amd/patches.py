@@ -789,6 +789,61 @@ def parse_sieve(text):
     return check_sieve([int(t) for t in parts]).min_size
 
 
+# ------------------------------------------------------------------- superpixel vote of whole-map labels
+SUPERPIXEL_WEIGHTS = ("labels", "confidence")
+SUPERPIXEL_RANGES = (("size", 4, 32), ("compactness", 1, 40), ("iters", 1, 16))        # the ranges include/drs.h accepts
+SuperpixelParams = collections.namedtuple("SuperpixelParams", "size compactness iters weight")
+SUPERPIXEL_DEFAULTS = SuperpixelParams(8, 10, 5, "labels")
+
+
+def check_superpixel(spec):
+    """The superpixel vote's parameters as SuperpixelParams(size, compactness, iters, weight).  spec: None or True (the defaults:
+    size 8, compactness 10, iters 5, weight "labels"), an int (the size: the grid step in pixels), a sequence of 1 to 3 ints (size,
+    compactness, iters), a dict with any of the four keys, or a SuperpixelParams.  size in 4..32, compactness in 1..40, iters in
+    1..16, weight "labels" (every pixel votes once) or "confidence" (a pixel votes with its confidence byte).  Anything else raises
+    ValueError naming the offending value."""
+    if spec is None or spec is True:
+        return SUPERPIXEL_DEFAULTS
+    if isinstance(spec, SuperpixelParams):
+        spec = spec._asdict()
+    elif isinstance(spec, (int, np.integer)) and not isinstance(spec, bool):
+        spec = {"size": spec}
+    elif isinstance(spec, (tuple, list, np.ndarray)) and not isinstance(spec, (str, bytes)):
+        if not 1 <= len(spec) <= 3:
+            raise ValueError("superpixel %r: expected 1 to 3 integers: size, compactness, iters" % (tuple(spec),))
+        spec = dict(zip(("size", "compactness", "iters"), spec))
+    if not isinstance(spec, dict):
+        raise ValueError("superpixel %r: expected a size, (size, compactness, iters), or a dict with the keys %s"
+                         % (spec, ", ".join(SuperpixelParams._fields)))
+    unknown = sorted(set(spec) - set(SuperpixelParams._fields))
+    if unknown:
+        raise ValueError("superpixel %r: expected the keys %s; unknown: %s"
+                         % (spec, ", ".join(SuperpixelParams._fields), ", ".join(map(repr, unknown))))
+    out = SUPERPIXEL_DEFAULTS._asdict()
+    for name, lo, hi in SUPERPIXEL_RANGES:
+        v = spec.get(name, out[name])
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not lo <= int(v) <= hi:
+            raise ValueError("superpixel %s %r: expected an integer in %d..%d" % (name, v, lo, hi))
+        out[name] = int(v)
+    weight = spec.get("weight", out["weight"])
+    if not isinstance(weight, str) or weight not in SUPERPIXEL_WEIGHTS:
+        raise ValueError("superpixel weight %r: expected %s" % (weight, " or ".join(SUPERPIXEL_WEIGHTS)))
+    return SuperpixelParams(out["size"], out["compactness"], out["iters"], weight)
+
+
+def parse_superpixel(text):
+    """The value of the command line's --superpixel-vote option: "size", "size,compactness" or "size,compactness,iters" as a tuple of
+    ints within check_superpixel's ranges.  An empty value, blanks, or anything that is not a plain decimal integer raise ValueError."""
+    form = "expected size[,compactness[,iters]] as integers, comma-separated (e.g. 8 or 8,10,5)"
+    parts = text.split(",") if isinstance(text, str) and text and text == text.strip() and " " not in text else []
+    for t in parts:
+        if not (t.isascii() and t.isdigit()):
+            raise ValueError("superpixel value %r of %r: %s" % (t, text, form))
+    if not 1 <= len(parts) <= 3:
+        raise ValueError("superpixel values %r: %s" % (text, form))
+    return tuple(check_superpixel([int(t) for t in parts])[:len(parts)])
+
+
 # ------------------------------------------------------------------- object-level scores of validation (DESIGN.md 8a.9)
 OBJECT_CONNECTIVITY = 4                    # what holds an object together by default: the sieve's default
 

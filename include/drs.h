@@ -914,6 +914,57 @@ int drs_distance_transform(const unsigned char* map, const unsigned char* veil, 
 size_t drs_surface_scratch_bytes(int h, int w);
 int drs_surface_histogram(const unsigned char* truth, const unsigned char* pred, int h, int w, int K, int ignore_label,
                           unsigned long long* table, void* scratch, size_t scratch_bytes, void* stream);
+/* Superpixels of a map's image and the vote of a label map inside regions (opt-in; csrc/superpixels.hip): object-
+ * based post-processing -- the image is cut into small compact colour-homogeneous segments (SLIC, Achanta et al. 2012) and every
+ * connected piece of a segment takes the class most of its pixels, or most of their confidence, voted for.  NORMATIVE: this text and
+ * the numpy statement tests/superpixel_ref.py.  After the byte features everything is integer arithmetic and every combination across
+ * workgroups an integer atomic add: every output is exact and independent of tiling and scheduling.
+ * Features: tile = the map's image [h][w][C] on the device, fp32 or fp64 (tile_is_f64 0 / 1); lo and inv = C HOST floats, copied into
+ *     the launch.  Per value v, read as fp32: t = (v - lo[c]) * inv[c], two separately rounded fp32 operations (never one fma);
+ *     feat = 0 if !(t > 0) (NaN included), 255 if t >= 255, else (int)rintf(t).  feat = uint8 [h][w][C].
+ * Grid: S the grid step, gw = max(1, w / S), gh = max(1, h / S) (floor).  The cell of a pixel: ci = min(gw - 1, x gw / w), cj likewise;
+ *     the centre of cell (ci, cj) has id = cj gw + ci.
+ * Start: cx = (2 ci + 1) w / (2 gw), cy likewise (floor); the centre's features F are the bytes of the pixel (cx, cy).
+ * Assign: the candidates of a pixel are the centres of the up to nine cells (ci + di, cj + dj), |di|, |dj| <= 1, inside the grid.  The
+ *     key of a candidate is S^2 sum_c (f_c - F_c)^2 + m^2 ((x - cx)^2 + (y - cy)^2), m the compactness; the pixel takes the candidate
+ *     with the smallest key, ties to the lower id.  The key is computed in 32 bits unsigned and is below 2^32: the colour part is at
+ *     most 8 255^2 32^2 = 532 684 800; a centre never leaves the 3 x 3 cells around its own (below), a cell is narrower than 2 S, so a
+ *     pixel is less than 6 S from a candidate per axis and the spatial part is at most 2 (6 32)^2 40^2 = 117 964 800.
+ * Update: per centre with n > 0 assigned pixels, cx, cy and every feature become the rounded mean (2 sum + n) / (2 n) (floor); a
+ *     centre with n = 0 keeps its values.  A cluster lies within the 3 x 3 cells around its centre's cell, fewer than 36 864 pixels
+ *     with x, y < 32 768: every sum is below 2^32 and is kept in 32 bits.
+ * Run: iters times {assign; update}.
+ * Outputs: assign = int32 [h][w], the ids of the LAST assign.  centres = int32 [gh gw][C + 3]: (cx, cy, f_0..f_{C-1}, n) after the last
+ *     update, n the count of the last assign.  colour = uint8 [h][w], (cj mod 4) 4 + (ci mod 4) of the assigned centre.
+ * Colour: a pixel's centre is at most one cell from the pixel's own cell, and the cells of two 4-adjacent pixels differ by at most
+ *     one: two 4-adjacent pixels with different centres have centres at most 3 cells apart per axis, so their colours differ.  The
+ *     4-connected components of colour are therefore exactly the connected pieces of the clusters: drs_components(colour, 4) labels
+ *     them.  A REGION is such a piece; stray fragments are regions of their own and nothing merges them (the sieve's job).
+ * Vote: label = what drs_components writes (the smallest pixel index of each pixel's region) -- ANY such labelling, not only
+ *     superpixels; weight = uint8 [h][w] or NULL for 1 per pixel.  Per region and class k < K: V[k] = the sum of weight over the
+ *     region's pixels whose byte is k (64-bit).  The winner is the largest V, ties to the lower class; if the largest V is 0 the region
+ *     stays as it is; otherwise every pixel of the region whose byte is < K takes the winner.  Bytes >= K never vote and never change.
+ *
+ * drs_superpixel_features: one launch.
+ * drs_superpixel_scratch_bytes: bytes of drs_superpixels' scratch (4 gh gw (C + 3): the sums per centre); 0 outside the ranges.
+ * drs_superpixels: 1 + 2 iters launches (start; per iteration the assignment with the sums, then the means).  The call initialises
+ *     its scratch: the result does not depend on what the scratch held.
+ * drs_region_vote_scratch_bytes: bytes of drs_region_vote's scratch for an h x w map (16 h w); 0 outside the ranges.
+ * drs_region_vote: from map_in to map_out (map_out == map_in, in place, is allowed).  Region sums are keyed by the region's root: K
+ *     passes (one per class, ascending) onto one 64-bit counter per root, each followed by a launch that keeps (sum, class) at the
+ *     root where it beats the best so far -- two 64-bit words per pixel, 2 K + 2 launches; the sums of a 32 x 32 tile are
+ *     aggregated per region in LDS first, one global atomic add per (region, tile).  It initialises what it reads of its scratch.  counters =
+ *     device uint32 [2], STORED: [0] the regions, [1] the pixels whose byte changed.
+ * No entry point synchronises.  Ranges, else DRS_ERR_ARG (nothing is launched, no host pointer is read): pointers not NULL (weight
+ * may be NULL); tile_is_f64 0 or 1; 1 <= C <= 8; 1 <= h, w <= 32768; 4 <= S <= 32; 1 <= m <= 40; 1 <= iters <= 16; 1 <= K <= 32. */
+int drs_superpixel_features(const void* tile, int tile_is_f64, int C, int h, int w, const float* lo, const float* inv,
+                            unsigned char* feat, void* stream);
+size_t drs_superpixel_scratch_bytes(int C, int h, int w, int S);
+int drs_superpixels(const unsigned char* feat, int C, int h, int w, int S, int m, int iters, int* assign, unsigned char* colour,
+                    int* centres, void* scratch, void* stream);
+size_t drs_region_vote_scratch_bytes(int h, int w);
+int drs_region_vote(const unsigned char* map_in, const int* label, const unsigned char* weight, int h, int w, int K, void* scratch,
+                    unsigned char* map_out, unsigned int* counters, void* stream);
 
 /* ==================================================================================================================
  * Training level: boundary-weighted cross-entropy (opt-in; csrc/boundary.hip, csrc/pointwise.hip).  A per-pixel weight
