@@ -100,6 +100,11 @@ SIGNATURES = {
     "drs_superpixels": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "drs_region_vote_scratch_bytes": (_sz, [_i, _i]),
     "drs_region_vote": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    # ---- whole-map level: polygon outlines of a label map (csrc/polygons.hip)
+    "drs_polygon_count": (_i, [_p, _i, _i, _p, _p]),
+    "drs_polygon_scratch_bytes": (_sz, [_i, _i, _i]),
+    "drs_polygon_rings": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "drs_polygon_write": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     # ---- whole-map level: exact distance transform and surface-distance table (csrc/distance.hip)
     "drs_distance_scratch_bytes": (_sz, [_i, _i]),
     "drs_distance_transform": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _sz, _p]),

@@ -39,6 +39,11 @@ isprs flavour  (isprs_dilated_random.py:1987-2042, 16 arguments):
     class most of its pixels voted for, ties to the lower class (loops.superpixel_vote); one `Superpixel` line per
     map and for all maps.  `--superpixel-weight=labels|confidence` (default labels; with --superpixel-vote only): with `confidence`
     a pixel votes with its confidence byte.  Score maps and calibration lines stay those of the unvoted labels
+  + optionally, anywhere, `--polygons[=4|8]` (generate_final_maps; any inference path, after --crf, --superpixel-vote and --sieve):
+    the map that is written is also written as polygons, `<stem>.geojson` beside `<stem>.tif` / `.npy`: one Polygon feature per
+    connected region of a class (4-connected by default; the bare flag takes --sieve-connectivity where --sieve is given), exterior
+    ring first, then its holes, on the pixel-corner lattice with collinear points dropped (loops.polygons, vectors.geojson;
+    DESIGN.md 8a.12); one `Polygons` line per map and for all maps
   + optionally, anywhere, `--object-scores[=4|8]` (validate_test; any inference path, with or without --crf / --sieve): one more line
     per map and for all maps with object-level scores -- the connected regions of each class (4-connected by default) are the objects,
     a truth object and a predicted one match when their IoU exceeds 1/2 --: per class the truth / predicted / matched counts, detection
@@ -307,6 +312,21 @@ def parse_superpixel(argv):
     return argv, P.check_superpixel(spec)
 
 
+POLYGONS_FLAG = "--polygons"
+
+
+def parse_polygons(argv, sieve=None):
+    """isprs flavour: the optional `--polygons[=4|8]` (anywhere in argv; generate_final_maps, which main checks).  Returns (argv
+    without the flag, the connectivity; patches.parse_polygons), or (argv unchanged, None) without it.  The bare flag takes the
+    connectivity of `sieve` (the SieveParams of parse_sieve) where a sieve is given -- the written polygons are then cut as the sieved
+    objects were --, else patches.POLYGON_CONNECTIVITY.  Any other value, or the flag given twice, raises ValueError."""
+    argv, conn = _take_flag(argv, POLYGONS_FLAG, lambda a, v: _or_expected(
+        P.parse_polygons, a, v, "%s or %s=4|8 (what holds a polygon together)" % (POLYGONS_FLAG, POLYGONS_FLAG)), bare=0)
+    if conn == 0:
+        conn = P.POLYGON_CONNECTIVITY if sieve is None else sieve.connectivity
+    return argv, conn
+
+
 OBJECT_SCORES_FLAG = "--object-scores"
 
 
@@ -495,6 +515,7 @@ def main(argv=None, device=None, comm=None):
         argv, boundary = parse_boundary_scores(argv)
         argv, sieve = parse_sieve(argv, 6)
         argv, superpixel = parse_superpixel(argv)
+        argv, polygons = parse_polygons(argv, sieve)
         argv, objects = parse_object_scores(argv)
         argv, surface = parse_surface_scores(argv)
         argv, class_weights = parse_class_weights(argv, 6)
@@ -537,6 +558,8 @@ def main(argv=None, device=None, comm=None):
         sys.exit(SIEVE_FLAG + " applies to the validate_test and generate_final_maps processes only")
     if superpixel is not None and argv[16] not in ("validate_test", "generate_final_maps"):
         sys.exit(SUPERPIXEL_FLAG + " applies to the validate_test and generate_final_maps processes only")
+    if polygons is not None and argv[16] != "generate_final_maps":
+        sys.exit(POLYGONS_FLAG + " applies to the generate_final_maps process only")
     if objects is not None and argv[16] != "validate_test":
         sys.exit(OBJECT_SCORES_FLAG + " applies to the validate_test process only")
     if surface is not None and argv[16] != "validate_test":
@@ -631,6 +654,7 @@ def main(argv=None, device=None, comm=None):
     boundary_kw = {} if boundary is None else dict(boundary_scores=boundary)
     sieve_kw = {} if sieve is None else dict(sieve=sieve)
     superpixel_kw = {} if superpixel is None else dict(superpixel=superpixel)
+    polygons_kw = {} if polygons is None else dict(polygons=polygons)
     objects_kw = {} if objects is None else dict(object_scores=objects)
     surface_kw = {} if surface is None else dict(surface_scores=surface)
     if process == "validate_test":
@@ -652,7 +676,7 @@ def main(argv=None, device=None, comm=None):
         return loops.generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                                          distribution_type, values, dataset, output_path, patch_acc_loss, patch_occur, comm,
                                          score_maps=score_maps, temperature_beta=temperature, **path_kw, **crf_kw,
-                                         **sieve_kw, **superpixel_kw)
+                                         **sieve_kw, **superpixel_kw, **polygons_kw)
     print(loops.BatchColors.FAIL + "Process " + process + "not found!" + loops.BatchColors.ENDC)
 
 

@@ -18,7 +18,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 MODE=${1:-incremental}
 [ -n "$DRS_FORCE_REBUILD" ] && [ "$MODE" = incremental ] && MODE=force
-SRCS="conv_mfma conv_split pointwise patches refine boundary components superpixels distance dice hard_mining lovasz surface_loss engine rccl_comm"
+SRCS="conv_mfma conv_split pointwise patches refine boundary components superpixels polygons distance dice hard_mining lovasz surface_loss engine rccl_comm"
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function"
 T0=$SECONDS
 

@@ -1565,6 +1565,67 @@ def _sieve_str(sieve, infos):
             " ".join(str(v) for v in total("objects_after")) + "]")
 
 
+def polygons(map_dev, h, w, connectivity=4, stream=None):
+    """The polygon outlines of a uint8 device map [h][w] (include/drs.h): every connected region's boundary as closed
+    rings on the pixel-corner lattice.  connectivity 4 or 8: what holds a region together (drs_components').  Components, the crack
+    count (drs_polygon_count), the rings (drs_polygon_rings, its scratch sized for exactly that count) and the two outputs
+    (drs_polygon_write, sized exactly); the host reads the counters in between.  Returns (ring_table, vertices, info): numpy int64
+    [rings][7] = (id, label, byte, first vertex, vertex count, crack count, A2), rings by ascending id; numpy int32 [vertices][2] =
+    (X, Y), ring after ring; info = {"rings", "exterior" (A2 > 0: one per region), "holes", "vertices", "cracks"}.  A non-zero status
+    of either call raises.  stream: a raw stream handle (default: torch's current stream on the map's device)."""
+    from . import _lib
+    if connectivity not in (4, 8):
+        raise ValueError("polygons: connectivity %r, expected 4 or 8" % (connectivity,))
+    if not (h >= 1 and w >= 1 and h * w <= 1 << 28):
+        raise ValueError("polygons: a map of %d x %d is outside h, w >= 1, h w <= 2^28" % (h, w))
+    if map_dev.dtype != torch.uint8 or map_dev.numel() != h * w or not map_dev.is_contiguous():
+        raise ValueError("polygons: the map must be a contiguous uint8 tensor of %d x %d elements" % (h, w))
+    dev = map_dev.device
+    h, w, connectivity = int(h), int(w), int(connectivity)
+    with _on_stream(dev, stream):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        label = torch.empty(h * w, dtype=torch.int32, device=dev)
+        size = torch.empty(h * w, dtype=torch.int32, device=dev)
+        _lib.call("drs_components", map_dev.data_ptr(), h, w, connectivity, label.data_ptr(), size.data_ptr(), st)
+        counters = torch.empty(4, dtype=torch.int64, device=dev)
+        _lib.call("drs_polygon_count", map_dev.data_ptr(), h, w, counters.data_ptr(), st)
+        cracks = int(counters[0].item())
+        scratch = torch.empty(_lib.query("drs_polygon_scratch_bytes", h, w, cracks), dtype=torch.uint8, device=dev)
+        _lib.call("drs_polygon_rings", map_dev.data_ptr(), label.data_ptr(), h, w, connectivity, cracks, scratch.data_ptr(),
+                  counters.data_ptr(), st)
+        got, rings, vertices, status = (int(v) for v in counters.cpu().tolist())
+        if status != 0 or got != cracks:
+            raise RuntimeError("polygons: drs_polygon_rings status %d with %d cracks for a capacity of %d" % (status, got, cracks))
+        table = torch.empty((rings, 7), dtype=torch.int64, device=dev)
+        verts = torch.empty((vertices, 2), dtype=torch.int32, device=dev)
+        wstatus = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.call("drs_polygon_write", scratch.data_ptr(), h, w, cracks, rings, vertices, table.data_ptr(), verts.data_ptr(),
+                  wstatus.data_ptr(), st)
+        if int(wstatus.item()) != 0:
+            raise RuntimeError("polygons: drs_polygon_write status %d for %d rings, %d vertices" % (int(wstatus.item()), rings, vertices))
+        table, verts = table.cpu().numpy(), verts.cpu().numpy()
+    exterior = int((table[:, 6] > 0).sum())
+    return table, verts, {"rings": rings, "exterior": exterior, "holes": rings - exterior, "vertices": vertices, "cracks": cracks}
+
+
+_trace_polygons = polygons                  # generate_final_maps' argument of the same name hides the function there
+
+
+def _polygons_info(table, info, K):
+    """what the Polygons line counts of one map: polygons per class (exterior rings of a byte < K), holes of those, their vertices"""
+    mine = table[:, 2] < K
+    return {"per_class": [int(((table[:, 2] == k) & (table[:, 6] > 0)).sum()) for k in range(K)],
+            "holes": int((mine & (table[:, 6] < 0)).sum()), "vertices": int(table[mine, 4].sum()), "cracks": info["cracks"]}
+
+
+def _polygons_str(connectivity, infos):
+    """the Polygons line's text from one map's _polygons_info, or from those of all maps (counts summed)"""
+    infos = infos if isinstance(infos, list) else [infos]
+    per_class = [sum(i["per_class"][k] for i in infos) for k in range(len(infos[0]["per_class"]))]
+    return ("Polygons connectivity= " + str(connectivity) + " Polygons per class= [" + " ".join(str(v) for v in per_class) + "]" +
+            " Holes= " + str(sum(i["holes"] for i in infos)) + " Vertices= " + str(sum(i["vertices"] for i in infos)))
+
+
 def superpixel_scale(pool, map_index):
     """(lo, inv) of drs_superpixel_features for one map of the pool, two float32 numpy arrays [C]: per channel lo = the map's own
     minimum and inv = 255 / (max - min) in fp32, 0 where max == min -- the bytes span what the map holds, whatever its units.  The
@@ -2065,7 +2126,7 @@ def validate_test(net, testing_data, testing_labels, testing_instances, batch_si
 def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_full, std_full, update_type,
                         distribution_type, values, dataset, output_path, patch_acc_loss=None, patch_occur=None, comm=None,
                         dense_tile=None, dense_tta=None, dense_scales=None, dense_se=None, score_maps=None, temperature_beta=None,
-                        crf=None, sieve=None, superpixel=None):
+                        crf=None, sieve=None, superpixel=None, polygons=None):
     """isprs:1854-1957: best (or fixed) patch size, sliding-window label map per tile, written as the reference's colour TIFF
     (`top_mosaic_09cm_area<i>_class.tif` / `top_potsdam_<i>_label.tif`) and as class ids (`.npy`).  dense_tile (an int, 0 = the
     default side): the maps come from overlap-tile inference (predict_tile_dense; no patch size is chosen); files as before.  dense_tta
@@ -2083,7 +2144,13 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     mapping unit first (sieve_labels), the refined map with crf; the score files stay those of the unsieved labels.
     superpixel (opt-in; any inference path; what patches.check_superpixel accepts): the written and returned maps are voted inside the
     superpixels of each map's image first (superpixel_vote), after crf and before sieve; with weight "confidence"
-    the path is asked for its confidence map whether score_maps is given or not.  The score files stay those of the unvoted labels."""
+    the path is asked for its confidence map whether score_maps is given or not.  The score files stay those of the unvoted labels.
+    polygons (opt-in; any inference path; 4 or 8, patches.check_polygons): the map that is written -- after crf, superpixel and sieve
+    -- is also written as polygons (the module's polygons(); vectors.write_geojson): rank 0 writes `<stem>.geojson`
+    beside the label files, one Polygon feature per connected region of a class, in pixel-corner coordinates, y down, and prints one
+    line `Final Map M: Polygons connectivity= c Polygons per class= [..] Holes= n Vertices= n` per map and one `Final ALL MAPS: ...`
+    with the counts summed.  Only rank 0 traces, and only where an output path is given.  The return values do not change.  Without
+    polygons nothing changes: no launch, no line, no file."""
     comm = comm or NoComm()
     path = InferencePath(dense_tile=dense_tile, dense_tta=dense_tta, dense_scales=dense_scales, dense_se=dense_se)
     path.check()
@@ -2092,6 +2159,8 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
     kinds = None if score_maps is None else P.check_score_kinds(score_maps)
     sieve = None if sieve is None else P.check_sieve(sieve)
     spx = None if superpixel is None else P.check_superpixel(superpixel)
+    pconn = None if polygons is None else P.check_polygons(polygons)
+    poly_list = []
     run_kinds = kinds                                      # the confidence-weighted vote needs the path's confidence map: asked for, not written
     if spx is not None and spx.weight == "confidence" and "confidence" not in (kinds or ()):
         run_kinds = (kinds or ()) + ("confidence",)
@@ -2125,6 +2194,15 @@ def generate_final_maps(net, testing_data, testing_instances, batch_size, mean_f
                 for kd, v in score_list[-1].items():
                     np.save(output_path + stem + "_" + kd + ".npy", v)
                     Image.fromarray(v).save(output_path + stem + "_" + kd + ".tif")
+            if pconn is not None:
+                from . import vectors
+                # `polygons` is this function's argument here (checked into pconn above): the module's polygons() by its other name
+                table, verts, pinfo = _trace_polygons(pred.reshape(-1), pool.h[k], pool.w[k], pconn, stream=net._stream())
+                vectors.write_geojson(output_path + stem + ".geojson", table, verts, net.plan.K)
+                poly_list.append(_polygons_info(table, pinfo, net.plan.K))
+                print("Final Map " + str(testing_instances[k]) + ": " + _polygons_str(pconn, poly_list[-1]))
+    if poly_list:
+        print("Final ALL MAPS: " + _polygons_str(pconn, poly_list))
     if kinds is not None:
         return maps, score_list
     return maps

@@ -844,6 +844,25 @@ def parse_superpixel(text):
     return tuple(check_superpixel([int(t) for t in parts])[:len(parts)])
 
 
+# ------------------------------------------------------------------- polygon output of whole-map labels
+POLYGON_CONNECTIVITY = 4                   # what holds a polygon together by default: the sieve's default
+
+
+def check_polygons(v):
+    """The connectivity of the polygon output as an int: 4 (the default) or 8 (drs_components').  Anything else raises ValueError
+    naming the offending value."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in (4, 8):
+        raise ValueError("polygons connectivity %r: expected 4 or 8" % (v,))
+    return int(v)
+
+
+def parse_polygons(text):
+    """The value of the command line's --polygons option: "4" or "8" as an int (check_polygons).  Anything else raises ValueError."""
+    if not isinstance(text, str) or text not in ("4", "8"):
+        raise ValueError("polygons connectivity %r: expected 4 or 8" % (text,))
+    return check_polygons(int(text))
+
+
 # ------------------------------------------------------------------- object-level scores of validation (DESIGN.md 8a.9)
 OBJECT_CONNECTIVITY = 4                    # what holds an object together by default: the sieve's default
 

@@ -965,6 +965,53 @@ int drs_superpixels(const unsigned char* feat, int C, int h, int w, int S, int m
 size_t drs_region_vote_scratch_bytes(int h, int w);
 int drs_region_vote(const unsigned char* map_in, const int* label, const unsigned char* weight, int h, int w, int K, void* scratch,
                     unsigned char* map_out, unsigned int* counters, void* stream);
+/* Polygon outlines of a label map (opt-in; csrc/polygons.hip): every region's boundary as closed rings on the pixel-
+ * corner lattice, exterior and holes told apart, collinear points dropped.  NORMATIVE: this text and the numpy statement
+ * tests/polygon_ref.py.  Integer-only: every output is exact and independent of tiling and scheduling.
+ * Input: map = uint8 [h][w] on the device (a byte is just a byte, as for drs_components); a connectivity c, 4 or 8; label = int32
+ *     [h][w] of drs_components(map, c).
+ * Geometry: pixel (y, x) covers [x, x + 1] x [y, y + 1]; corners are lattice points (X, Y), 0 <= X <= w, 0 <= Y <= h, y down.
+ * Cracks: pixel p = y w + x has four directed sides d, each with the pixel on the right-hand side of travel on screen:
+ *     d = 0 top, east (x, y) -> (x + 1, y);  1 right, south (x + 1, y) -> (x + 1, y + 1);  2 bottom, west (x + 1, y + 1) -> (x, y + 1);
+ *     3 left, north (x, y + 1) -> (x, y).  The pixel across side d is (y - 1, x), (y, x + 1), (y + 1, x), (y, x - 1).  Side d of p is a
+ *     CRACK iff the pixel across it is outside the map or carries another byte; its id is e = 4 p + d (h w <= 2^28: int32).  The map
+ *     edge IS a crack -- every ring closes --, unlike the scoring ops, where the map edge is not a boundary.
+ * Successor of crack (p, d): q = the pixel one step ahead of p in direction d; r = the pixel across side d of q (ahead-left, diagonal
+ *     to p); same(.) = inside the map and carrying p's byte.  c = 4: if !same(q) the right turn (p, d + 1), else if !same(r) straight
+ *     on (q, d), else the left turn (r, d - 1).  c = 8: if same(r) then (r, d - 1), else if same(q) then (q, d), else (p, d + 1).
+ *     d +- 1 mod 4.  The rule is a bijection on the cracks, the head of e is the tail of succ(e), and a cycle stays inside one
+ *     c-component.
+ * Rings: a ring is a cycle of succ; its id is its smallest crack id (4 label for the exterior ring of a component).  Its VERTICES are
+ *     the heads of those of its cracks e with d(succ(e)) != d(e) -- the turning points only --, in cycle order from the first such
+ *     crack at or after the ring's smallest crack.  A2 = the sum over its cracks of x0 y1 - x1 y0, tail (x0, y0), head (x1, y1), int64:
+ *     the doubled signed area; A2 > 0 an exterior ring, A2 < 0 a hole.  A ring may touch itself at a corner (a pinch at c = 8, a hole
+ *     between diagonal pixels at c = 4); that is not repaired.
+ * Outputs: ring_table = int64 [rings][7], rings by ascending id: (id, label[id >> 2], map[id >> 2], first vertex, vertex count, crack
+ *     count, A2).  vertices = int32 [vertices][2] = (X, Y), ring after ring in table order.
+ *
+ * drs_polygon_count: two launches; STORES counters[0] (device uint64) = the map's crack count.
+ * drs_polygon_scratch_bytes: bytes of the scratch for an h x w map and crack_cap cracks (about 5 h w + 74 crack_cap); 0 outside the
+ *     ranges.
+ * drs_polygon_rings: builds everything in scratch and STORES counters (device uint64 [4]) = (cracks, rings, vertices, status).  The
+ *     crack count is taken from device memory (its own scan), grids are sized by crack_cap.  If the count exceeds crack_cap: status 1,
+ *     rings = vertices = 0, nothing outside the scratch and counters is written and the scratch holds no result.  The cracks are
+ *     compacted in id order by a scan of the per-pixel counts; ring leaders and positions come from pointer doubling, at most
+ *     2 ceil(log2(crack_cap)) + 1 rounds, each a launch that reads only what the launch before it wrote, the launches after a round
+ *     that changed nothing returning at once; A2 by 64-bit integer atomic adds.  No kernel waits on another workgroup.  The call
+ *     initialises what it reads of its scratch: the result does not depend on what the scratch held.  For measurements: the uint64
+ *     words 7 and 8 of the finished scratch hold the rounds the two doublings ran.
+ * drs_polygon_write: one launch; writes ring_table and vertices from the scratch of a finished drs_polygon_rings with the same h, w,
+ *     crack_cap, and STORES status (device uint32) = 0.  If the scratch holds no result (status 1 above, or another h, w, crack_cap),
+ *     or its ring count exceeds ring_cap or its vertex count vertex_cap -- the elements the two outputs have room for --: status = 1
+ *     and no output element is written.  A wrong or stale capacity is thus a status word and never a write out of bounds.
+ * No entry point synchronises.  Ranges, else DRS_ERR_ARG (nothing is launched, no pointer is read): pointers not NULL; h, w >= 1,
+ * h w <= 2^28; connectivity 4 or 8; 1 <= crack_cap <= 4 h w; ring_cap, vertex_cap >= 0. */
+int drs_polygon_count(const unsigned char* map, int h, int w, unsigned long long* counters, void* stream);
+size_t drs_polygon_scratch_bytes(int h, int w, int crack_cap);
+int drs_polygon_rings(const unsigned char* map, const int* label, int h, int w, int connectivity, int crack_cap, void* scratch,
+                      unsigned long long* counters, void* stream);
+int drs_polygon_write(const void* scratch, int h, int w, int crack_cap, int ring_cap, int vertex_cap, long long* ring_table,
+                      int* vertices, unsigned int* status, void* stream);
 
 /* ==================================================================================================================
  * Training level: boundary-weighted cross-entropy (opt-in; csrc/boundary.hip, csrc/pointwise.hip).  A per-pixel weight
