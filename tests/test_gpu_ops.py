@@ -3,7 +3,8 @@ oracle (oracle/tf_ops.py, fp64) on the same seeded inputs; the remaining entry p
 pool, squeeze-and-excitation (training side), the term-writing batch-norm forms, softmax accumulation and drs_scale_f64 in
 test_gpu_pointwise_oplevel.py, the classifier on steep logits, exact arg-max ties, empty masks and tiny / ragged pixel counts in
 test_gpu_classifier_edges.py, the split-bf16 convolution in test_gpu_split.py, the whole-image SE gates in test_gpu_dense_se.py,
-crop / stitch / tile placement in test_gpu_patches.py and the test_gpu_dense_*.py modules.  Tolerances: fp32 kernels vs fp64 oracle, relative to the tensor's max magnitude,
+crop / stitch / tile placement in test_gpu_patches.py and the test_gpu_dense_*.py modules, the convolution at channel widths of several
+column tiles in test_gpu_conv_widths.py, the crop's device-side noise in test_gpu_device_noise.py.  Tolerances: fp32 kernels vs fp64 oracle, relative to the tensor's max magnitude,
 1e-5 for single ops (BASELINE north_star: logits within 1e-3 relative end to end); integer outputs exact."""
 import numpy as np
 import pytest
@@ -14,7 +15,7 @@ from oracle import nets as onets
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import DEV, conv_stats_moments, dev, padded, rel_err, stream, unpad   # noqa: E402
+from gpu_util import DEV, check_conv_forward_dgrad_wgrad, conv_stats_moments, dev, padded, rel_err, stream, unpad   # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -36,54 +37,8 @@ CONV_CASES = [
 
 @pytest.mark.parametrize("k,rate,cin,cout,B,S", CONV_CASES)
 def test_conv_forward_dgrad_wgrad(lib, k, rate, cin, cout, B, S):
-    rng = np.random.default_rng(k * 1000 + rate * 100 + cin + cout + S)
-    x = rng.normal(size=(B, S, S, cin)).astype(np.float32)
-    w = (rng.normal(size=(k, k, cin, cout)) / np.sqrt(k * k * cin)).astype(np.float32)
-    bias = rng.normal(size=(cout,)).astype(np.float32)
-    g = rng.normal(size=(B, S, S, cout)).astype(np.float32)
-    pb, pa = onets.same_pad(k, rate)
-    P = max(pb, pa) + 1                      # a halo wider than needed must also work
-    M = B * S * S
-    xd = padded(x, P, ld=cin + 32, coff=32, fill=7.0)      # slice of a wider slab; foreign channels are junk
-    wd, bd = dev(w), dev(bias)
-    out = torch.full((M, cout + 32), -3.0, dtype=torch.float32, device=DEV)
-    mt = lib.query("drs_conv_mtile", cout)
-    rows = (M + mt - 1) // mt
-    stats = torch.zeros(rows * cout * 2, dtype=torch.float32, device=DEV)
-    lib.call("drs_conv_forward", xd.data_ptr(), B, S, P, cin + 32, 32, wd.data_ptr(), bd.data_ptr(), k, rate, pb, cin, cout,
-             out.data_ptr(), cout + 32, 32, 0, stats.data_ptr(), stream())
-    torch.cuda.synchronize()
-    ref = T.conv2d_same(x.astype(np.float64), w.astype(np.float64), rate) + bias.astype(np.float64)
-    got = out.cpu().numpy()
-    assert rel_err(got[:, 32:].reshape(B, S, S, cout), ref) < 1e-5
-    assert np.all(got[:, :32] == -3.0)                      # neighbouring channels untouched
-    st = conv_stats_moments(lib, stats, M, mt, cout)
-    r2 = ref.reshape(-1, cout)
-    assert np.abs(st[:, 0] - r2.sum(axis=0)).max() < 1e-5 * np.abs(r2).sum(axis=0).max()
-    assert rel_err(st[:, 1], (r2 ** 2).sum(axis=0)) < 1e-5
-    # accumulate mode
-    lib.call("drs_conv_forward", xd.data_ptr(), B, S, P, cin + 32, 32, wd.data_ptr(), None, k, rate, pb, cin, cout,
-             out.data_ptr(), cout + 32, 32, 1, None, stream())
-    torch.cuda.synchronize()
-    ref2 = ref + T.conv2d_same(x.astype(np.float64), w.astype(np.float64), rate)
-    assert rel_err(out.cpu().numpy()[:, 32:].reshape(B, S, S, cout), ref2) < 1e-5
-
-    # gradients
-    gx_ref, gw_ref = T.conv2d_same_bwd(x.astype(np.float64), w.astype(np.float64), rate, g.astype(np.float64))
-    gd = padded(g, P, ld=cout, coff=0)
-    wt = torch.zeros(k * k * cin * cout, dtype=torch.float32, device=DEV)
-    lib.call("drs_filter_flip_transpose", wd.data_ptr(), wt.data_ptr(), k, cin, cout, stream())
-    gx = torch.zeros(M * cin, dtype=torch.float32, device=DEV)
-    lib.call("drs_conv_forward", gd.data_ptr(), B, S, P, cout, 0, wt.data_ptr(), None, k, rate, pa, cout, cin, gx.data_ptr(),
-             cin, 0, 0, None, stream())
-    nsplit = lib.query("drs_conv_wgrad_splits", B, S, k, cin, cout)
-    slab = torch.zeros(nsplit * k * k * cin * cout, dtype=torch.float32, device=DEV)
-    gw = torch.zeros(k * k * cin * cout, dtype=torch.float32, device=DEV)
-    lib.call("drs_conv_wgrad", xd.data_ptr(), B, S, P, cin + 32, 32, gd.data_ptr(), P, cout, 0, k, rate, pb, cin, cin, cout,
-             slab.data_ptr(), gw.data_ptr(), stream())
-    torch.cuda.synchronize()
-    assert rel_err(gx.cpu().numpy().reshape(B, S, S, cin), gx_ref) < 1e-5
-    assert rel_err(gw.cpu().numpy().reshape(k, k, cin, cout), gw_ref) < 1e-5
+    """(the body lives in gpu_util.check_conv_forward_dgrad_wgrad, shared with test_gpu_conv_widths.py)"""
+    check_conv_forward_dgrad_wgrad(lib, k, rate, cin, cout, B, S)
 
 
 @pytest.mark.parametrize("k,rate,cin,cout,B,S", [(3, 8, 64, 128, 3, 20), (3, 7, 64, 64, 2, 33), (4, 3, 64, 128, 5, 9), (5, 2, 32, 64, 2, 16),
@@ -398,7 +353,11 @@ def test_bn_eval_coeffs(lib):
 
 @pytest.mark.parametrize("C,K,B,S,P,masked", [(256, 6, 2, 9, 0, False), (448, 2, 1, 12, 6, False), (256, 7, 2, 8, 0, True),
                                              (64, 6, 1, 31, 1, False), (448, 6, 2, 13, 6, True), (128, 4, 3, 10, 0, False), (128, 3, 1, 17, 2, False),
-                                             (256, 8, 5, 21, 0, True), (192, 5, 1, 40, 1, False)])
+                                             (256, 8, 5, 21, 0, True), (192, 5, 1, 40, 1, False),
+                                             # C = 320 / 384: classifier_mfma_kernel<5, ...> / <6, ...> (K >= 4) and
+                                             # classifier_loss_kernel<5, ...> / <6, ...> (K = 2, 3: the vector-ALU form), each in the
+                                             # training and the inference form; ragged last tiles, the 384 rows in a haloed slab
+                                             (320, 6, 2, 9, 0, False), (384, 6, 2, 9, 2, True), (320, 2, 1, 12, 0, False), (384, 3, 2, 8, 1, True)])
 def test_classifier_loss(lib, C, K, B, S, P, masked):
     rng = np.random.default_rng(C + K)
     M = B * S * S
@@ -436,6 +395,9 @@ def test_classifier_loss(lib, C, K, B, S, P, masked):
     lg_ref = f64 @ w.astype(np.float64) + bias.astype(np.float64)
     ce, gl = T.softmax_ce(lg_ref, y, lm)
     lg = logits.cpu().numpy().reshape(B, S, S, K)
+    print("C %d K %d M %d: logits %.2e gfeat %.2e dw %.2e loss %.2e" % (
+        C, K, M, rel_err(lg, lg_ref), rel_err(gfeat.cpu().numpy().reshape(B, S, S, C), gl @ w.astype(np.float64).T),
+        rel_err(dw.cpu().numpy().reshape(C, K), f64.reshape(-1, C).T @ gl.reshape(-1, K)), abs(ls.item() / n - ce) / max(1.0, abs(ce))))
     assert rel_err(lg, lg_ref) < 1e-5
     ph = pred.cpu().numpy().reshape(B, S, S)
     np.testing.assert_array_equal(ph, lg.argmax(axis=3))             # first maximum of the device's own logits
@@ -668,8 +630,12 @@ def test_filter_gradient_chunk_walk_over_patch_sides(lib, S, B, shape):
 
 
 @pytest.mark.parametrize("C,K,B,S,P,mode", [pytest.param(*c, "plain", id="-".join(map(str, c))) for c in
-                                            [(256, 6, 3, 21, 0), (128, 4, 2, 17, 2), (64, 7, 1, 40, 1), (192, 8, 5, 9, 0), (256, 6, 16, 25, 0)]] +
-                         [(128, 4, 2, 17, 2, "weighted"), (256, 6, 3, 21, 0, "weighted"), (128, 4, 2, 17, 2, "focal"), (256, 6, 3, 21, 0, "focal")])
+                                            [(256, 6, 3, 21, 0), (128, 4, 2, 17, 2), (64, 7, 1, 40, 1), (192, 8, 5, 9, 0), (256, 6, 16, 25, 0),
+                                             # CQ = 5 / 6 (C = 320 / 384): above C = 256 there is no LDS-DMA form, variant 3 falls back to
+                                             # classifier_mfma_kernel<5 / 6, ...> and must equal variant 2 bit for bit
+                                             (320, 6, 2, 17, 2), (384, 4, 3, 9, 0)]] +
+                         [(128, 4, 2, 17, 2, "weighted"), (256, 6, 3, 21, 0, "weighted"), (128, 4, 2, 17, 2, "focal"), (256, 6, 3, 21, 0, "focal"),
+                          (320, 6, 2, 17, 2, "focal"), (384, 4, 3, 9, 0, "weighted")])      # the same two instantiations in the LM != 0 modes
 def test_classifier_forms_agree(lib, C, K, B, S, P, mode):
     """The classifier block exists in a vector-ALU form (2-3 classes), a register-staged MFMA form and an LDS-DMA MFMA form (features
     brought in once, one tile ahead; up to C = 256).  The two MFMA forms run the same products in the same order: bitwise equal,

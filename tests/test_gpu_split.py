@@ -12,7 +12,7 @@ from oracle import nets as onets
 
 pytestmark = pytest.mark.gpu
 
-from gpu_util import DEV, conv_stats_moments, dev, padded, rel_err, stream   # noqa: E402
+from gpu_util import DEV, GUARD, conv_stats_moments, dev, guard_intact, guarded, padded, rel_err, stream   # noqa: E402
 
 # two terms (bf16x3) drop the t1*u1 partial product: 2^-16 = 1.5e-5 of a product.  Over sums of hundreds of products the errors average
 # well below 1e-5 of the tensor's maximum; a sum of a FEW products (a 5 x 5 patch under a rate-6 filter: most taps meet the halo) keeps
@@ -70,7 +70,15 @@ CASES = [
     (5, 1, 32, 64, 3, 9), (5, 2, 64, 64, 2, 12), (4, 3, 64, 128, 2, 11), (4, 4, 128, 128, 2, 10),
     (3, 5, 128, 192, 2, 13), (3, 6, 192, 192, 1, 15), (3, 7, 192, 256, 1, 16), (3, 8, 256, 256, 2, 17),
     (4, 2, 64, 128, 2, 8), (3, 4, 128, 256, 1, 9), (3, 6, 320, 128, 1, 14), (4, 4, 128, 64, 1, 12), (3, 5, 32, 64, 1, 25),
+    # widths of several column tiles, M = 300 (ragged 128-row M tiles); the filter gradient's rows k*k*cin = 576 are 4 1/2 row tiles.
+    # drs_conv_wgrad_split has two arms, wgrad_dma(nterms, Pg, cout) = Pg > 0 && (nterms == 2 || cout >= 128): rows in WGRAD_BOTH_ARMS
+    # run it at Pg = P (the LDS-DMA arm, both term counts) and at Pg = 0 (the register-staged arm)
+    (3, 2, 64, 320, 3, 10),     # forward 5 x 64; wgrad Pg = P: 2 x 128 + a 64-wide rest at o_base = 256; Pg = 0: 5 x 64 (2 terms), 2 x 128 + 64 (3 terms)
+    (3, 2, 64, 384, 3, 10),     # forward 3 x 128; wgrad 3 x 128, no rest (Pg = P: the LDS-DMA arm)
+    (3, 2, 64, 448, 3, 10),     # forward 7 x 64; wgrad Pg = P: 3 x 128 + a 64-wide rest at o_base = 384; Pg = 0: 7 x 64 (2 terms), 3 x 128 + 64 (3 terms)
+    (3, 2, 320, 64, 3, 10),     # input gradient N = 320: 5 x 64; wgrad one 64-wide tile, 23 row tiles (the last ragged: 2880 rows)
 ]
+WGRAD_BOTH_ARMS = (320, 448)
 
 
 @pytest.mark.parametrize("ns", [2, 3])
@@ -122,14 +130,26 @@ def test_conv_split_forward_dgrad_wgrad(lib, k, rate, cin, cout, B, S, ns):
     if cin % 64 == 0:       # the input-gradient GEMM has N = cin; narrower layers stay on the exact-fp32 kernel
         lib.call("drs_conv_forward_split", gp.data_ptr(), B, S, P, cout, 0, wg.data_ptr(), None, k, rate, pa, cout, cin,
                  gx.data_ptr(), cin, 0, 0, None, ns, stream())
-    nsplit = lib.query("drs_conv_wgrad_split_splits", B, S, k, cin, cout, P, ns)
-    slab = torch.zeros(nsplit * nw, dtype=torch.float32, device=DEV)
-    gw = torch.zeros(nw, dtype=torch.float32, device=DEV)
-    lib.call("drs_conv_wgrad_split", xp.data_ptr(), B, S, P, cin + 32, 32, gp.data_ptr(), P, cout, 0, k, rate, pb, cin,
-             cin, cout, slab.data_ptr(), gw.data_ptr(), ns, stream())
     torch.cuda.synchronize()
     e_dg = rel_err(gx.cpu().numpy().reshape(B, S, S, cin), gx_ref) if cin % 64 == 0 else 0.0
-    e_wg = rel_err(gw.cpu().numpy().reshape(k, k, cin, cout), gw_ref)
+    e_wg = 0.0
+    for Pg in ((P, 0) if cout in WGRAD_BOTH_ARMS else (P,)):
+        gpg = gp if Pg == P else planes(lib, padded(g, Pg, ld=cout, coff=0), ns)[0]
+        nsplit = lib.query("drs_conv_wgrad_split_splits", B, S, k, cin, cout, Pg, ns)
+        # the slab [split][k*k*cin][cout] starts out as GUARD everywhere: the planes the call wrote are the splits it used, which the
+        # query must cover; the guard rows after the last plane must stay untouched
+        slab = guarded(nsplit * k * k * cin, cout, GUARD, 128)
+        gw = torch.zeros(nw, dtype=torch.float32, device=DEV)
+        lib.call("drs_conv_wgrad_split", xp.data_ptr(), B, S, P, cin + 32, 32, gpg.data_ptr(), Pg, cout, 0, k, rate, pb, cin,
+                 cin, cout, slab.data_ptr(), gw.data_ptr(), ns, stream())
+        torch.cuda.synchronize()
+        assert guard_intact(slab, nsplit * k * k * cin)
+        used = int((slab[:nsplit * k * k * cin].view(nsplit, -1) != GUARD).any(dim=1).sum())
+        assert 1 <= used <= nsplit
+        assert bool((slab[:used * k * k * cin] != GUARD).all())      # ... and those planes are written whole: the sum reads every element
+        e = rel_err(gw.cpu().numpy().reshape(k, k, cin, cout), gw_ref)
+        print("k%d r%d %3d->%3d terms %d Pg %d: wgrad %.2e (%d of %d splits)" % (k, rate, cin, cout, ns, Pg, e, used, nsplit))
+        e_wg = max(e_wg, e)
     print("k%d r%d %3d->%3d terms %d: fwd %.2e dgrad %.2e wgrad %.2e" % (k, rate, cin, cout, ns, e_fwd, e_dg, e_wg))
     assert e_dg < tol
     assert e_wg < tol
